@@ -32,6 +32,10 @@ Order of a run (every phase is stated in the JSON line):
   5. N = 1: secondary legs (cfg 2 on Set R, cfg 3 / cfg 4 / cfg 5 at full size on this one GPU), HBM
      traffic of the launch from two rocprofv3 --pmc child passes of this script, CPU baseline.
 
+`--dump-outputs DIR` writes what the last timed step computed (the (core, accessory) matrix, or a fixed, seeded
+sample of it when it is larger than 64 MB) to DIR/*.npy right after the timed region, so that two builds can be
+compared output for output on identical inputs.
+
 Prints ONE JSON line on rank 0.
 """
 import argparse
@@ -52,7 +56,7 @@ CFG2_N = 1000
 CFG3_N = 100_000
 CPU_SAMPLE_MAX_N = 20_000      # cpu_baseline: largest triangle the CPU leg times ("a 20k-sample slice of cfg3")
 K4, SS64_CFG45 = [13, 17, 21, 25, 29], 32          # BASELINE configs[3], [4]
-HBM_PEAK_GBS = 8000.0          # MI355X HBM3E spec, /opt/skills/guides/MI355X_MICROARCH.md
+HBM_PEAK_GBS = 8000.0          # MI355X HBM3E spec
 # Vector-ALU peak of the chip (the resource that binds this kernel: 32-bit integer bitwise work, no
 # MFMA shape).  MI355X_MICROARCH.md "Execution model": a wave64 VALU instruction issues over 2 cycles
 # on a SIMD-32; 256 CUs x 4 SIMDs; datasheet clock 2.4 GHz  ->  256*4*32*2.4e9 lane-operations/s
@@ -252,6 +256,33 @@ def valu_block(pairs_per_launch, avg_kernel_s, nk, ss64, clock, counted=None):
     return blk
 
 
+DUMP_MAX_BYTES = 64 << 20       # --dump-outputs: at most this many bytes of .npy payload in all
+DUMP_SAMPLE_PAIRS = 1 << 21     # pairs sampled when the whole output is larger (float32 x 2 + float64 index = 32 MB)
+DUMP_SEED = 20240607
+
+
+def dump_outputs(torch, np, out_dir, result, total_pairs):
+    """--dump-outputs DIR: what the timed path returned to its caller in its last step -- the (core, accessory) f32 matrix
+    of the condensed triangle -- as DIR/core_acc.npy [pairs, 2] float32; a larger output as a fixed, seeded sample of
+    DUMP_SAMPLE_PAIRS pairs (sorted condensed indices in DIR/core_acc_pair_index.npy, float64) so that the files stay
+    under DUMP_MAX_BYTES.  `result`: a device or host tensor [total_pairs, 2] float32.  -> a description for the JSON line."""
+    os.makedirs(out_dir, exist_ok=True)
+    if total_pairs * 2 * 4 <= DUMP_MAX_BYTES:
+        vals = result.cpu().numpy()
+        idx = None
+    else:
+        idx = np.sort(np.random.default_rng(DUMP_SEED).choice(total_pairs, DUMP_SAMPLE_PAIRS, replace=False)).astype(np.int64)
+        vals = result[torch.from_numpy(idx).to(result.device)].cpu().numpy()
+    np.save(os.path.join(out_dir, "core_acc.npy"), np.ascontiguousarray(vals, dtype=np.float32))
+    files = ["core_acc.npy"]
+    if idx is not None:
+        np.save(os.path.join(out_dir, "core_acc_pair_index.npy"), idx.astype(np.float64))
+        files.append("core_acc_pair_index.npy")
+    return {"dir": os.path.abspath(out_dir), "files": files, "pairs": int(vals.shape[0]),
+            "sampled": idx is not None, "what": "(core, accessory) of the timed path's last step"
+            + ("" if idx is None else f", {DUMP_SAMPLE_PAIRS} pairs sampled with seed {DUMP_SEED}")}
+
+
 def sampled(ctx, run, interval_us, expect_s=1.0, enabled=True):
     """run() with the one-wave clock sampler next to it (skl_clock_sampler_*): -> the clock reading, or None.
     run() must leave its work on the context's stream; it is waited for with a STREAM synchronisation (a
@@ -422,6 +453,9 @@ def main():
     ap.add_argument("--no-clock-sampler", action="store_true", help="roofline pass without the concurrent clock sampler")
     ap.add_argument("--no-traffic", action="store_true",
                     help="N = 1: quote the committed HBM traffic instead of measuring it with two rocprofv3 --pmc child passes")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed to DIR/*.npy (<= 64 MB; larger "
+                         "outputs as a fixed, seeded sample)")
     ap.add_argument("--traffic-probe", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--no-gather", action="store_true", help="skip assembling the output on rank 0")
     ap.add_argument("--gather", choices=["rccl", "host"], default="rccl",
@@ -437,6 +471,8 @@ def main():
     ap.add_argument("--no-overlap", action="store_true",
                     help="N > 1: finish each step's gather before the next step's kernel (default: one step of overlap)")
     args = ap.parse_args()
+    if args.steps < 0 or args.warmup < -1:
+        ap.error("--steps and --warmup must not be negative")
     if args.traffic_probe:
         return traffic_probe(args)
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ and "RANK" not in os.environ:
@@ -615,6 +651,18 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
 
+    # ---- untimed: the output of the last timed step, before any later pass rewrites a buffer ----
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        if hostbuf is not None:
+            result = hostbuf.assembled()
+        elif dist is not None and args.no_gather:      # nothing assembled: rank 0's own band is what it received
+            result = bands[(step_no[0] - 1) % len(bands)]
+        else:
+            result = full
+        dumped = dump_outputs(torch, np, args.dump_outputs, result, result.shape[0])
+        del result
+
     # ---- 3. the roofline pass: fixed size, every launch bracketed; then once more with the clock sampler beside it ----
     # (bands[0] is rank 0's slice of `full` when nothing is gathered: the passes rewrite it with the same values)
     avg_kernel_s, launches, pass_wall_s, _none = roofline_pass(ctx, local_launch, roofline_launches, sampler_interval_us, sampler=False)
@@ -738,6 +786,7 @@ def main():
                 **({"cold_pairs_per_s": cold["pairs_per_s"], "cold": cold} if cold else {}),
                 **({"n1_same_workload": n1_same} if n1_same else {}),
                 **({"host_gather_pinned": bool(hostbuf.pinned)} if hostbuf is not None else {}),
+                **({"dumped_outputs": dumped} if dumped else {}),
             },
             "roofline": {
                 # The resource that binds: the vector ALU.  HBM does not: see

@@ -1,5 +1,5 @@
 import sys, os, time, json
-sys.path.insert(0, os.environ.get("GRAFT_REPO_ROOT", "/root/repo"))
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 from sketchlib.rust_amd import capi, synth
 dev = torch.device("cuda", 0)

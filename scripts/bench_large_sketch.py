@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Throughput at the reference's "SNP level" sketch sizes (`-s 100000` ... `-s 1000000`, /root/reference/src/lib.rs:41-42:
+"""Throughput at the reference's "SNP level" sketch sizes (`-s 100000` ... `-s 1000000`, the reference's src/lib.rs:41-42:
 sketchsize64 = 1 563 ... 15 625) on one MI355X, Set U, inputs resident in HBM: the chunk-split kernel walking a k-mer
 length in segments (round 4) against the one-column fallback these sizes took until round 3 (pair_kernel_ksplit,
 still reachable through the A/B library's SKL_KERNEL=ksplit).  One JSON line per (mode, kernel).

@@ -2,7 +2,7 @@
 """cfg 2 step time (n = 1 000, core/accessory, Set U) of the library as the environment selects it: the probe behind
 profiles/r05_fused_epilogue.md (SKL_LIBRARY = the A/B build, SKL_FUSE_EPILOGUE=1, SKL_FUSE_VARIANT = timing-only ablations)."""
 import sys, json, time, os
-sys.path.insert(0, os.environ.get("GRAFT_REPO_ROOT", "/root/repo"))
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 from sketchlib.rust_amd import capi, synth
 n=1000; K=[15,19,23,27,31]

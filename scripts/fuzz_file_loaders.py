@@ -39,7 +39,7 @@ def frame(raw):
     return out
 fx=os.path.abspath('tests/golden/reference_fixtures')
 tmp='/tmp/skifuzz'; shutil.rmtree(tmp,ignore_errors=True); os.makedirs(tmp)
-env={**os.environ,'ASAN_OPTIONS':'detect_leaks=0','LD_LIBRARY_PATH':'/root/repo/sketchlib.rust_amd/csrc/_build'}
+env={**os.environ,'ASAN_OPTIONS':'detect_leaks=0','LD_LIBRARY_PATH':os.path.abspath('sketchlib.rust_amd/csrc/_build')}
 def run(cmd,t=20):
     try:
         r=subprocess.run(cmd,capture_output=True,env=env,cwd=tmp,timeout=t); return r.returncode, r.stderr.decode('utf-8','replace')

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Generates tests/golden/generated/* from the reference's test genomes.
 
-Run in the build container (needs /root/reference; the GPU box never runs this):
+Runs on the CPU from the reference's test genomes stored in tests/golden/reference_fixtures:
     python tests/golden/make_generated_fixtures.py
 
 1. Pins oracle/sketcher.py: re-sketches the four genomes with the parameters of the
@@ -21,10 +21,10 @@ ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)
 sys.path.insert(0, ROOT)
 from oracle import sketcher  # noqa: E402
 
-REF_IN = "/root/reference/tests/test_files_in"
 GENOMES = ["14412_3#82.contigs_velvet.fa.gz", "14412_3#84.contigs_velvet.fa.gz", "R6.fa.gz", "TIGR4.fa.gz"]
 OUT = os.path.join(ROOT, "tests", "golden", "generated")
 FIX = os.path.join(ROOT, "tests", "golden", "reference_fixtures")
+REF_IN = FIX
 
 
 def main():

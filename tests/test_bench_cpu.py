@@ -87,3 +87,23 @@ def test_counted_lengths_and_the_roofline_block_of_an_early_break_launch():
     part = bench.valu_block(499500, 1.0e-4, 5, 64, None, counted=3)
     assert part["k_mer_lengths_counted"] == 3 and abs(part["frac"] - 0.6 * full["frac"]) < 1e-12
     assert abs(part["frac_as_if_every_length_were_counted"] - full["frac"]) < 1e-12 and "frac_as_if_every_length_were_counted" not in full
+
+
+def test_dump_outputs_whole_and_sampled(tmp_path):
+    """--dump-outputs: a small output is written whole; a larger one as the same seeded sample every time, under 64 MB."""
+    import torch
+
+    b = _bench()
+    small = torch.arange(499500 * 2, dtype=torch.float32).reshape(-1, 2)
+    info = b.dump_outputs(torch, np, str(tmp_path / "a"), small, small.shape[0])
+    assert info["files"] == ["core_acc.npy"] and not info["sampled"]
+    got = np.load(tmp_path / "a" / "core_acc.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, small.numpy())
+    big = torch.arange(9_000_000 * 2, dtype=torch.float32).reshape(-1, 2)
+    for d in ("b", "c"):
+        info = b.dump_outputs(torch, np, str(tmp_path / d), big, big.shape[0])
+        assert info["sampled"] and info["pairs"] == b.DUMP_SAMPLE_PAIRS
+    vals, idx = np.load(tmp_path / "b" / "core_acc.npy"), np.load(tmp_path / "b" / "core_acc_pair_index.npy")
+    assert idx.dtype == np.float64 and np.all(np.diff(idx) > 0) and np.array_equal(vals[:, 0], 2 * idx)
+    assert np.array_equal(idx, np.load(tmp_path / "c" / "core_acc_pair_index.npy"))
+    assert sum(f.stat().st_size for f in (tmp_path / "b").iterdir()) <= b.DUMP_MAX_BYTES

@@ -1,5 +1,5 @@
 """Sketches beyond 65 535 bins -- the sizes the reference recommends "for SNP level resolution"
-(`-s 100000` ... `-s 1000000`, /root/reference/src/lib.rs:41-42: sketchsize64 = 1 563 ... 15 625) -- through the C ABI:
+(`-s 100000` ... `-s 1000000`, the reference's src/lib.rs:41-42: sketchsize64 = 1 563 ... 15 625) -- through the C ABI:
 the chunk-split kernel walks such a k-mer length in segments of 1 016 chunks (pair_kslice_walk.inc) instead of
 falling back to the one-column kernel.  Bin-match counts bit-exact, f32 Jaccard / ANI bit-exact, core/accessory
 within 1e-6 (bit-exact without completeness), self / cross / row bands / kNN (row by row and one evaluation)."""

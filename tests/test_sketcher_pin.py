@@ -1,18 +1,15 @@
-"""oracle/sketcher.py against the reference's committed sketches (needs the reference's
-FASTA files, i.e. the build container; skipped elsewhere -- the generated fixture it
-produced is committed and covered by test_oracle_golden.py)."""
+"""oracle/sketcher.py against the reference's committed sketches, from the reference's test
+genomes stored under tests/golden/reference_fixtures (the generated fixture it produced is
+committed and covered by test_oracle_golden.py too)."""
 import hashlib
 import os
 
 import numpy as np
-import pytest
 
 from conftest import GOLDEN, REF_FIXTURES
 
-REF_IN = "/root/reference/tests/test_files_in"
+REF_IN = REF_FIXTURES
 GENOMES = ["14412_3#82.contigs_velvet.fa.gz", "14412_3#84.contigs_velvet.fa.gz", "R6.fa.gz", "TIGR4.fa.gz"]
-
-pytestmark = pytest.mark.skipif(not os.path.isdir(REF_IN), reason="reference genomes not available here")
 
 
 def test_sketcher_reproduces_committed_skd():
