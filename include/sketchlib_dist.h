@@ -273,7 +273,8 @@ int skl_knn_merge_states(skl_ctx *ctx, size_t n_states, size_t rows, size_t knn,
  * cannot be merged -- but a heap can travel.  Participant r owns the column window [lo_r, hi_r) (windows ascending with r;
  * cut them at n * sqrt(r / R) so that the pair counts balance, ROUNDED TO BAND BOUNDARIES: col_lo and col_hi must be multiples
  * of band_rows -- col_hi may also be n -- or the call fails with SKL_ERR_INVALID_ARG: a window starting inside a band would
- * lose candidates) and, for every row band b = rows [b * band_rows, ...) that
+ * lose candidates; so every cut but the last lies at or below n rounded down to a band boundary, and participants between
+ * that cut and n get the EMPTY window [cut, cut)) and, for every row band b = rows [b * band_rows, ...) that
  * starts below hi_r, in ascending order, calls skl_self_dists_knn_window: the band's rows take the columns
  * [max(band start, lo_r), hi_r) as candidates, the window's rows below the band take the band's samples.  Before a band
  * whose rows lie below lo_r, participant r receives those rows' heaps from participant r - 1 (which has finished that band);
@@ -281,7 +282,9 @@ int skl_knn_merge_states(skl_ctx *ctx, size_t n_states, size_t rows, size_t knn,
  * (skl_knn_heaps_finalize).  Rows of a participant's own window start empty (skl_knn_heaps_clear).  The heap arrays are the
  * caller's (device memory): h_key f32 / h_id u32 / h_d1 f32 (CoreAcc only) [n][knn] in heap order, h_len u32 [n], thr u32 [n]
  * (order-preserving image of the heap's maximum once it is full, 0xFFFFFFFF before).  Tile pruning applies as in the
- * single-device call.  sketchlib.rust_amd/multi_gpu.py (self_knn_once_reference) is the driver over torch.distributed. */
+ * single-device call.  An empty window (col_lo == col_hi <= n, aligned or not) holds no pair: the call (and the _logged one
+ * below) returns SKL_OK at once, launches nothing and leaves the heaps and logs as they are.
+ * sketchlib.rust_amd/multi_gpu.py (self_knn_once_reference) is the driver over torch.distributed. */
 int skl_self_dists_knn_window(skl_ctx *ctx, const skl_sketches *s, const skl_dist_params *p, size_t knn,
                               size_t band_rows, size_t band, size_t col_lo, size_t col_hi,
                               float *h_key, uint32_t *h_id, float *h_d1, uint32_t *h_len, uint32_t *thr);

@@ -13,7 +13,8 @@ One rank per GPU over RCCL; every rank holds the whole slab.
 SKL_BENCH_BACKEND=gloo (debugging aid): messages staged through host memory, ranks dealt to the GPUs there are (several
 ranks may share one).  Rank 0 prints one JSON line: wall
 time of the slowest rank (barrier on both sides), pair distances defined per second, and with
---check the comparison against rank 0 recomputing its shard alone, row by row.
+--check the comparison of every rank's row shard with the same rows recomputed alone, row by row, on that rank (true only
+if every rank's shard matches).
 """
 import argparse
 import json
@@ -105,11 +106,17 @@ def main():
             "pair_distances_defined": args.n * (args.n - 1),
             "pairs_per_s": args.n * (args.n - 1) / float(wall.item()),
             "band_rows": capi.knn_band_rows(sk, p, world)}
-    if args.check and rank == 0:
-        ridx, rd0, rd1 = capi.self_dists_knn(ctx, sk, p, args.knn, r0, r1)   # row by row, this shard only
-        line["shard_equals_row_by_row"] = bool((idx.cpu().numpy().astype("uint64") == ridx).all() and
-                                               (d0.cpu().numpy() == rd0).all() and
-                                               (d1 is None or (d1.cpu().numpy() == rd1).all()))
+    if args.check:   # every rank its own shard, row by row; the verdict holds only if it holds on every rank
+        ok = True
+        if r1 > r0:
+            ridx, rd0, rd1 = capi.self_dists_knn(ctx, sk, p, args.knn, r0, r1)
+            ok = bool((idx.cpu().numpy().astype("uint64") == ridx).all() and
+                      (d0.cpu().numpy() == rd0).all() and
+                      (d1 is None or (d1.cpu().numpy() == rd1).all()))
+        verdict = torch.tensor([int(ok)], dtype=torch.int32, device=torch.device("cpu") if gloo else device)
+        if dist is not None:
+            dist.all_reduce(verdict, op=dist.ReduceOp.MIN)
+        line["shard_equals_row_by_row"] = bool(verdict.item())
     if rank == 0:
         print(json.dumps(line), flush=True)
     if dist is not None:

@@ -133,9 +133,9 @@ struct KnnCross {
     const skl_sketches *cols = nullptr;   // null: the symmetric form
     bool self_rows = false;               // rows and columns are the same sample set: a row is not its own candidate
     size_t row_lo = 0, row_hi = ~(size_t)0;   // rows of the call (bands are clipped to them)
-    // (symmetric form, one band per call -- skl_self_dists_knn_window: every list the band meets already holds knn candidates,
-    // as from a whole-matrix call's second band on: the early break of the core/accessory keys may start with the call's
-    // first band)
+    // (symmetric form, one band per call -- skl_self_dists_knn_window: every list the band's TURNED copy reaches already holds
+    // knn candidates, as from a whole-matrix call's second band on: the early break of the core/accessory keys may start with
+    // the call's first band.  The band's own rows are not covered -- under accept logs they may start empty: knn_window_impl)
     bool lists_hold_knn = false;
 };
 
@@ -859,6 +859,9 @@ static int knn_window_impl(skl_ctx *ctx, const skl_sketches *s, const skl_dist_p
     if (n < 2 || knn == 0 || knn > n - 1) return fail(SKL_ERR_INVALID_ARG, "knn=%zu must be in [1, %zu]", knn, n ? n - 1 : 0);
     if (knn > (size_t)REFHEAP_LDS_MAX) return fail(SKL_ERR_INVALID_ARG, "the travelling heaps live in LDS while they are fed: knn=%zu exceeds %u", knn, REFHEAP_LDS_MAX);
     if (band_rows == 0 || band * band_rows >= n || col_lo > col_hi || col_hi > n) return fail(SKL_ERR_INVALID_ARG, "row band / column window out of range");
+    // (an empty window holds no pair: nothing to evaluate and nothing to refuse -- a caller that cuts its own windows may hand one
+    // to a participant past the last band boundary below n -- so no launch, heaps and logs untouched)
+    if (col_lo == col_hi) return SKL_OK;
     // (a window that starts inside a band would give that band's rows turned candidates on this window's owner which the heaps
     // arriving from the upstream participant then overwrite: candidates silently lost)
     if (col_lo % band_rows != 0 || (col_hi % band_rows != 0 && col_hi != n)) {
@@ -880,7 +883,13 @@ static int knn_window_impl(skl_ctx *ctx, const skl_sketches *s, const skl_dist_p
     // (the counters run on over the bands of a window: skl_ctx_knn_prune_stats reports everything since the last kNN
     // call of another kind -- no read-back, no reset here: this call must not stall the hand-over of the heaps)
     KnnCross form;   // (the symmetric form)
-    form.lists_hold_knn = band >= 1 && band_rows >= knn;   // (bands 0 .. band - 1 of this window, or the windows before it, have fed every list)
+    // Every list the band's TURNED copy reaches -- the window's rows [max(b1, col_lo), col_hi) -- holds knn candidates: bands
+    // 0 .. band - 1 of this call's sequence gave each of them band_rows >= knn, on this participant, so this holds for heaps that
+    // started empty on the window (the _logged form) as well.  It says nothing of the band's OWN rows: below col_lo they start
+    // empty under logs.  It need not: it only feeds plain_marks_nothing, which epilogue.hip applies to the turned side, while
+    // the own rows' records are stored and marked by the row-side test against the row's own threshold (thr_row: "not full"
+    // lets a (1, 1) in), so a row with fewer than knn candidates still takes its plain pairs.
+    form.lists_hold_knn = band >= 1 && band_rows >= knn;
     return knn_symmetric_bands(ctx, s, p, knn, band_rows, one, false, st, col_lo, col_hi, form);
 }
 

@@ -331,11 +331,13 @@ def self_knn_once(ctx, sk, p, knn, rank, world, dist, device):
 def knn_window_cuts(n, band_rows, world):
     """Column windows [cuts[r], cuts[r + 1]) per rank: cut where the pair counts balance -- rank r evaluates the pairs (i, j),
     i < j, whose column j lies in its window, ~ (hi^2 - lo^2) / 2 of them -- on band boundaries (a band's rows are then
-    either all inside a window or all outside it)."""
+    either all inside a window or all outside it).  Every cut but the last is clamped to the last band boundary at or below n, not
+    to n: a window may not start inside a band, so ranks between that boundary and n get empty windows and the last one the rest."""
+    last = n // band_rows * band_rows
     cuts = [0]
     for r in range(1, world):
         c = int(round(n * (r / world) ** 0.5 / band_rows)) * band_rows
-        cuts.append(min(max(c, cuts[-1]), n))
+        cuts.append(min(max(c, cuts[-1]), last))
     cuts.append(n)
     return cuts
 

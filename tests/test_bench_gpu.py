@@ -190,7 +190,7 @@ def test_knn_multi_canonical_all_to_all_with_one_rank(gpu_ctx):
 @pytest.mark.parametrize("world,coreacc,port", [(2, False, 29631), (3, True, 29633), (4, False, 29635)])
 def test_knn_reference_order_travelling_heaps_with_several_ranks_on_the_one_gpu(gpu_ctx, world, coreacc, port):
     """The reference's tie order over `world` ranks, every pair evaluated once (skl_self_dists_knn_window + heaps handed
-    from rank to rank band by band, multi_gpu.self_knn_once_reference), all ranks on the box's one GPU over gloo: rank 0's
+    from rank to rank band by band, multi_gpu.self_knn_once_reference), all ranks on the box's one GPU over gloo: every rank's
     row shard equals the single-device row-by-row replay of the same rows (ids, order, distances)."""
     args = ["scripts/bench_knn_multi.py", "--samples", "12000", "--knn", "20", "--clustered", "--check", "--ties", "reference"]
     line = _torchrun_world(world, args + (["--coreacc"] if coreacc else []), port)
@@ -202,11 +202,22 @@ def test_knn_reference_order_travelling_heaps_with_several_ranks_on_the_one_gpu(
 def test_knn_reference_order_decoupled_windows_with_several_ranks_on_the_one_gpu(gpu_ctx, world, coreacc, port):
     """The same lists with no rank waiting for another (round 6): every rank runs its column window against heaps it has cleared
     itself, logs what they take (skl_self_dists_knn_window_logged), the logs are exchanged and replayed in window order
-    (skl_knn_heaps_replay; multi_gpu.self_knn_once_reference_decoupled) -- all ranks on the box's one GPU over gloo: rank 0's
+    (skl_knn_heaps_replay; multi_gpu.self_knn_once_reference_decoupled) -- all ranks on the box's one GPU over gloo: every rank's
     row shard equals the single-device row-by-row replay of the same rows (ids, order, distances)."""
     args = ["scripts/bench_knn_multi.py", "--samples", "12000", "--knn", "20", "--clustered", "--check", "--ties", "reference", "--decoupled"]
     line = _torchrun_world(world, args + (["--coreacc"] if coreacc else []), port) if world > 1 else _torchrun(args + (["--coreacc"] if coreacc else []), port)
     assert line["n_gpus"] == world and line["ties"] == "reference" and "decoupled" in line["mode"]
+    assert line["shard_equals_row_by_row"] is True
+
+
+def test_knn_reference_order_decoupled_windows_past_the_last_band_boundary(gpu_ctx):
+    """8 000 samples over 3 ranks at the library's own band height (skl_knn_band_rows): n is no band multiple and the window cuts
+    stop at the last band boundary below it, so a rank between gets an empty window and the last one the rest -- every rank's
+    row shard equals the single-device row-by-row replay of the same rows."""
+    args = ["scripts/bench_knn_multi.py", "--samples", "8000", "--knn", "20", "--clustered", "--check", "--ties", "reference", "--decoupled"]
+    line = _torchrun_world(3, args, 29651)
+    assert line["n_gpus"] == 3 and line["ties"] == "reference" and "decoupled" in line["mode"]
+    assert 8000 % line["band_rows"] != 0
     assert line["shard_equals_row_by_row"] is True
 
 

@@ -207,12 +207,16 @@ def test_gloo_knn_every_pair_once_exchange(oracle, tmp_path, world):
     assert res.stdout.count("KNN_ONCE_OK") == world
 
 
-@pytest.mark.parametrize("n,band_rows,world", [(1000000, 2048, 8), (700, 64, 3), (97, 10, 2), (50, 64, 4), (1000, 16, 1)])
+@pytest.mark.parametrize("n,band_rows,world", [(1000000, 2048, 8), (700, 64, 3), (97, 10, 2), (50, 64, 4), (1000, 16, 1),
+                                                (118, 64, 3), (47, 16, 4), (8000, 4208, 3), (8000, 4208, 4), (7338, 4096, 8),
+                                                (128, 64, 3), (64, 64, 3), (10, 64, 2), (200, 16, 20)])
 def test_knn_window_cuts(n, band_rows, world):
-    """Column windows of the travelling-heaps pipeline: ascending, on band boundaries, balanced by pair count."""
+    """Column windows of the travelling-heaps pipeline: ascending, balanced by pair count, and every cut but the last on a band
+    boundary -- n itself only when it is one (skl_self_dists_knn_window refuses a window that starts inside a band; ranks past
+    the last boundary below n get empty windows)."""
     cuts = multi_gpu.knn_window_cuts(n, band_rows, world)
     assert len(cuts) == world + 1 and cuts[0] == 0 and cuts[-1] == n and cuts == sorted(cuts)
-    assert all(c % band_rows == 0 or c == n for c in cuts[:-1])
+    assert all(c % band_rows == 0 for c in cuts[:-1]), cuts
     if n >= 100 * band_rows * world:      # rank r evaluates ~ (hi^2 - lo^2) / 2 pairs
         area = [(cuts[r + 1] ** 2 - cuts[r] ** 2) / 2 for r in range(world)]
         assert max(area) / min(area) < 1.05
@@ -228,9 +232,12 @@ dist.init_process_group("gloo")
 rank, world = dist.get_rank(), dist.get_world_size()
 mode = sys.argv[1]
 form = sys.argv[2] if len(sys.argv) > 2 else "travelling"     # travelling | decoupled | overflow
-n, kmers, ss64, knn, band_rows = 131, [17, 21, 25], 4, 7, 16
+n = int(sys.argv[3]) if len(sys.argv) > 3 else 131
+band_rows = int(sys.argv[4]) if len(sys.argv) > 4 else 16
+kmers, ss64, knn = [17, 21, 25], 4, 7
 bins = synth.set_r(n, kmers, ss64, n_clusters=3)
-bins[40] = bins[7]; bins[99] = bins[7]; bins[100] = bins[7]       # exact ties inside a cluster
+for t in ((40, 99, 100) if n > 100 else (n // 3, n - 2, n - 1)):
+    bins[t] = bins[7]                                             # exact ties inside a cluster
 s = O.Sketches(bins, n, kmers, ss64)
 coreacc = mode == "coreacc"
 dtype, k_idx = (O.COREACC, 0) if coreacc else (O.JACCARD, 1)
@@ -274,7 +281,13 @@ def log_taken(lg, row, took, ids, keys, d1):
         lg["len"][row] = m + 1
 
 def stage(band, lo, hi, h, lg=None):
-    # stand-in for skl_self_dists_knn_window[_logged] (the GPU half), from the oracle's distances and its resumable BinaryHeap
+    # stand-in for skl_self_dists_knn_window[_logged] (the GPU half), from the oracle's distances and its resumable BinaryHeap;
+    # it refuses what the C ABI refuses -- and, stricter than the ABI (which lets an empty window through anywhere), a window the
+    # driver did not cut on band boundaries: knn_window_cuts must never produce one
+    if not (0 <= band and band * band_rows < n and 0 <= lo <= hi <= n):
+        raise ValueError("row band %%d / column window [%%d, %%d) out of range (n = %%d)" %% (band, lo, hi, n))
+    if lo %% band_rows != 0 or (hi %% band_rows != 0 and hi != n):
+        raise ValueError("column window [%%d, %%d) must be cut on band boundaries (band_rows = %%d)" %% (lo, hi, band_rows))
     b0, b1 = band * band_rows, min(n, (band + 1) * band_rows)
     c_first, t_first = max(b0, lo), max(b1, lo)
     if c_first >= hi:
@@ -378,6 +391,23 @@ def test_gloo_reference_order_decoupled_windows(oracle, tmp_path, world, mode, f
         [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={world}",
          "--master-addr", "127.0.0.1", "--master-port", str(29600 + world + (10 if mode == "coreacc" else 0) + (20 if form == "overflow" else 0)),
          str(script), mode, form],
+        env=env, capture_output=True, text=True, timeout=600)
+    assert res.returncode == 0, res.stdout[-2000:] + res.stderr[-3000:]
+    assert res.stdout.count("HEAPS_OK") == world
+
+
+@pytest.mark.parametrize("form,port", [("travelling", 29651), ("decoupled", 29652)])
+def test_gloo_reference_order_with_a_rank_past_the_last_band_boundary(oracle, tmp_path, form, port):
+    """n = 47, band_rows = 16, 4 ranks: the last band boundary below n is 32, so rank 2 gets the empty window [32, 32) and rank 3
+    the window [32, 47) -- a window cut at n (47 is no band boundary) is refused by the stand-in as by the C ABI.  Both forms
+    of the driver, ids, order and distances = the oracle's."""
+    world = 4
+    script = tmp_path / "heap_worker.py"
+    script.write_text(HEAP_WORKER)
+    env = dict(os.environ, MASTER_ADDR="127.0.0.1", OMP_NUM_THREADS="1")
+    res = subprocess.run(
+        [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={world}",
+         "--master-addr", "127.0.0.1", "--master-port", str(port), str(script), "jaccard", form, "47", "16"],
         env=env, capture_output=True, text=True, timeout=600)
     assert res.returncode == 0, res.stdout[-2000:] + res.stderr[-3000:]
     assert res.stdout.count("HEAPS_OK") == world
