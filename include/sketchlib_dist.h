@@ -343,6 +343,28 @@ int skl_self_dists_knn_shared_bins(skl_ctx *ctx, const skl_sketches *s, const sk
                                    size_t knn, const uint16_t *skq, size_t sketch_size,
                                    uint64_t *out_idx, float *out_d0, uint64_t *out_n_candidates);
 
+/* ---- inverted query (src/inverted.rs:229-269): Inverted::query_against_inverted_index, all_shared_bins,
+ *      any_shared_bins for many queries at once ----
+ * An index held on the device: `bins` is the dense form of a `.ski` ([n_samples][sketch_size] u16, the `.skq`
+ * layout, row = .ski sample index; a .ski written by `inverted build` holds exactly one value per (sample, bin)).
+ * count(q, s) = #{ b : bins[s][b] == query_bins[q][b] }; the query is NOT excluded.
+ *   SKL_INVQ_MATCH_COUNT: out = u32 [n_queries][n_samples], the counts (query_against_inverted_index, :229-241)
+ *   SKL_INVQ_ANY_BINS:    out = u64 [n_queries][ceil(n_samples / 64)], bit s % 64 of word s / 64 set iff count > 0
+ *                         (any_shared_bins, :259-268)
+ *   SKL_INVQ_ALL_BINS:    the same bitmap, bit set iff count == sketch_size (all_shared_bins, :243-257)
+ * Host pointers.  Queries run in bands sized by a device-memory budget (SKL_INVQ_BAND_BYTES, default 1 GiB), so
+ * n_queries x n_samples never has to fit at once; skl_inverted_band_queries tells how many queries one band takes.
+ * Destroy an index before its context.  At most 2^32 - 257 samples per index. */
+typedef struct skl_inverted skl_inverted;
+#define SKL_INVQ_MATCH_COUNT 0
+#define SKL_INVQ_ANY_BINS 1
+#define SKL_INVQ_ALL_BINS 2
+int skl_inverted_create(skl_ctx *ctx, const uint16_t *bins, size_t n_samples, size_t sketch_size, skl_inverted **out);
+int skl_inverted_destroy(skl_inverted *ix);
+int skl_inverted_query(skl_ctx *ctx, const skl_inverted *ix, const uint16_t *query_bins, size_t n_queries, int mode,
+                       void *out);
+size_t skl_inverted_band_queries(skl_ctx *ctx, const skl_inverted *ix, int mode);
+
 /* GPU sketching: bin minima of `canonical ntHash % SIGN_MOD` over every
  * valid k-mer of DNA samples -- Sketch::get_signs_no_densify (src/sketch/mod.rs:156-176) over
  * NtHashIterator (src/hashing/nthash_iterator.rs:325-523), all samples and k-mer lengths of a

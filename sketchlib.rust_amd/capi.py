@@ -109,6 +109,10 @@ _SIG = [
                                              _P, _P, _P, C.c_int]),
     ("skl_knn_merge_states", C.c_int, [_P, C.c_size_t, C.c_size_t, C.c_size_t, _P, _P, _P, C.c_int, C.c_int,
                                        _P, _P, _P, C.c_int]),
+    ("skl_inverted_create", C.c_int, [_P, _P, C.c_size_t, C.c_size_t, C.POINTER(_P)]),
+    ("skl_inverted_destroy", C.c_int, [_P]),
+    ("skl_inverted_query", C.c_int, [_P, _P, _P, C.c_size_t, C.c_int, _P]),
+    ("skl_inverted_band_queries", C.c_size_t, [_P, _P, C.c_int]),
     ("skl_sketch_signs", C.c_int, [_P, _P, _P, _P, _P, C.c_size_t, _P, C.c_size_t, C.c_uint64, C.c_int, _P]),
     ("skl_sketch_signs_packed", C.c_int, [_P, _P, _P, _P, _P, C.c_size_t, _P, C.c_size_t, C.c_uint64, C.c_int, _P]),
     ("skl_self_binmatch", C.c_int, [_P, _P, _P, C.c_int]),
@@ -589,6 +593,58 @@ def self_dists_knn_shared_bins(ctx, s, p, knn, skq):
     _check(load().skl_self_dists_knn_shared_bins(ctx._h, s._h, C.byref(p), knn, skq.ctypes.data, skq.shape[1],
                                                  idx.ctypes.data, d0.ctypes.data, C.byref(total)))
     return idx, d0, int(total.value)
+
+
+INVQ_MATCH_COUNT, INVQ_ANY_BINS, INVQ_ALL_BINS = 0, 1, 2
+
+
+class Inverted:
+    """skl_inverted: the dense bins of an inverted index ([n_samples, sketch_size] u16, row = .ski sample index)
+    resident on the device (src/inverted.rs:229-269)."""
+
+    def __init__(self, ctx, bins):
+        bins = np.ascontiguousarray(bins, dtype=np.uint16)
+        assert bins.ndim == 2
+        self.ctx = ctx
+        self.n, self.sketch_size = bins.shape
+        self._h = _P()
+        _check(load().skl_inverted_create(ctx._h, bins.ctypes.data if bins.size else None, self.n, self.sketch_size,
+                                          C.byref(self._h)))
+
+    def band_queries(self, mode=INVQ_MATCH_COUNT):
+        """Queries one band of skl_inverted_query takes under the context's memory budget."""
+        return int(load().skl_inverted_band_queries(self.ctx._h, self._h, int(mode)))
+
+    def query(self, queries, mode=INVQ_MATCH_COUNT):
+        """queries: [n_queries, sketch_size] u16.  MATCH_COUNT -> uint32 [n_queries, n] bin-match counts;
+        ANY_BINS / ALL_BINS -> uint64 [n_queries, ceil(n / 64)] bitmaps (count > 0 / count == sketch_size)."""
+        queries = np.ascontiguousarray(queries, dtype=np.uint16)
+        assert queries.ndim == 2 and queries.shape[1] == self.sketch_size
+        nq = queries.shape[0]
+        if mode == INVQ_MATCH_COUNT:
+            out = np.zeros((nq, self.n), dtype=np.uint32)
+        else:
+            out = np.zeros((nq, (self.n + 63) // 64), dtype=np.uint64)
+        _check(load().skl_inverted_query(self.ctx._h, self._h, queries.ctypes.data if queries.size else None, nq,
+                                         int(mode), out.ctypes.data if out.size else None))
+        return out
+
+    def close(self):
+        if self._h:
+            load().skl_inverted_destroy(self._h)
+            self._h = _P()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def unpack_bitmap(bits, n):
+    """[n_queries, ceil(n / 64)] uint64 bitmaps -> bool [n_queries, n] (bit s % 64 of word s // 64)."""
+    b = np.ascontiguousarray(bits, dtype="<u8").view(np.uint8).reshape(bits.shape[0], -1)
+    return np.unpackbits(b, axis=1, bitorder="little")[:, :n].astype(bool)
 
 
 def sketch_signs(ctx, codes, code_begin, offsets, offset_begin, kmers, num_bins, rc=True):

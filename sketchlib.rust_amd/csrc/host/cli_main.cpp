@@ -6,6 +6,7 @@
 // the host threads that format the dense text output; the distances themselves run on the
 // GPU.  `--device` is the one addition.
 #include <atomic>
+#include <charconv>
 #include <mutex>
 #include <future>
 #include <thread>
@@ -228,7 +229,7 @@ void write_whole(const DistanceMatrix &d, TextSink &sink, size_t n, const DistAr
 // orderly exit.
 // (called by main() AFTER its last line of output -- the verbose "Complete in" line -- with the command's exit code; a
 // failed flush of the listing (ENOSPC, EPIPE) turns a success into exit code 1 and takes the orderly way out)
-bool g_listing_complete = false;   // set by run_dist / run_inverted once the listing is written
+bool g_listing_complete = false;   // set by run_dist / run_inverted / run_inverted_query once the listing is written
 
 int leave_after_success(int rc)
 {
@@ -526,11 +527,206 @@ int run_sketch(int argc, char **argv, int first, bool verbose, bool quiet)
     return 0;
 }
 
-// ---- `sketchlib inverted build|precluster` (src/cli.rs:329-461, src/lib.rs:485-600,682-789) ----
+// ---- `sketchlib inverted query` (src/cli.rs:380-412, src/lib.rs:605-680) ----
+// Queries are sketched on host threads the way the index was built (Inverted::sketch_queries, inverted.rs:118-140),
+// then matched against every indexed sample on the GPU (skl_inverted_query, csrc/inv_query.hip), one band of
+// queries at a time: band i + 1 computes while band i is formatted on --threads threads and written.  Rows come in
+// input order (the reference's come in whatever order its threads finish).
+int run_inverted_query(int argc, char **argv, int first, bool verbose, bool quiet)
+{
+    g_usage = "sketchlib inverted query [OPTIONS] <SKI> <SEQ_FILES|-f <FILE_LIST>>";
+    std::optional<std::string> ski, file_list, output;
+    std::vector<std::string> seq_files;
+    int mode = SKL_INVQ_MATCH_COUNT;
+    std::string mode_name = "match-count";
+    size_t threads = 1;
+    int device = 0;
+    for (int i = first; i < argc; ++i) {
+        const std::string arg = argv[i];
+        auto value = [&](const std::string &flag) -> std::string {
+            if (i + 1 >= argc) usage_error("a value is required for '" + flag + "' but none was supplied");
+            return argv[++i];
+        };
+        if (arg == "-v" || arg == "--verbose") verbose = true;
+        else if (arg == "--quiet") quiet = true;
+        else if (arg == "-f") file_list = value("-f <FILE_LIST>");
+        else if (arg == "-o") output = value("-o <OUTPUT>");
+        else if (arg == "--query-type") {
+            mode_name = value("--query-type <QUERY_TYPE>");
+            if (mode_name == "match-count") mode = SKL_INVQ_MATCH_COUNT;
+            else if (mode_name == "all-bins") mode = SKL_INVQ_ALL_BINS;
+            else if (mode_name == "any-bins") mode = SKL_INVQ_ANY_BINS;
+            else usage_error("invalid value '" + mode_name + "' for '--query-type <QUERY_TYPE>'\n  [possible values: match-count, all-bins, any-bins]");
+        }
+        else if (arg == "--threads") threads = std::max<size_t>(1, parse_usize("--threads <THREADS>", value(arg)));
+        else if (arg == "--min-count" || arg == "--min-qual") (void)value(arg);   // reads input only (out of scope)
+        else if (arg == "--device") device = (int)parse_usize("--device <D>", value(arg));
+        else if (arg.size() > 1 && arg[0] == '-') usage_error("unexpected argument '" + arg + "' found");
+        else if (!ski) ski = arg;
+        else seq_files.push_back(arg);
+    }
+    if (!ski) usage_error("the following required arguments were not provided:\n  <SKI>");
+    if (seq_files.empty() == !file_list.has_value()) {
+        usage_error("exactly one of <SEQ_FILES>... or -f <FILE_LIST> must be given");
+    }
+    const Logger log{verbose && !quiet, !quiet};
+    const bool timing = std::getenv("SKL_CLI_TIMING") != nullptr;
+    const auto t_start = std::chrono::steady_clock::now();
+    auto since_start = [&] { return std::chrono::duration<double>(std::chrono::steady_clock::now() - t_start).count(); };
+    // (as in `precluster`: the device comes up while the .ski is read; a device that failed to come up is only reported
+    // where it is first needed, after every error of the .ski and of the inputs)
+    std::future<std::unique_ptr<Device>> dev_starting =
+        std::async(std::launch::async, [device] { return std::make_unique<Device>(device); });
+    const std::string prefix = strip_sketch_extension(*ski);
+    const Inverted inv = Inverted::load(prefix);   // `?` in the reference: Error, exit 1
+    log.info("Read inverted index: " + std::to_string(inv.sample_names.size()) + " samples, k=" +
+             std::to_string(inv.kmer_size) + ", sketch size " + std::to_string(inv.sketch_size()));
+    if (inv.hash_type != "DNA") {
+        std::cerr << "error: this build queries DNA indices only (" << prefix << ".ski has hash_type " << inv.hash_type << ")\n";
+        return 2;
+    }
+    const size_t n = inv.sample_names.size(), S = inv.sketch_size();
+    const std::vector<uint16_t> index_bins = inv.dense_bins(prefix + ".ski");
+    const double t_load = since_start();
+
+    log.info("Getting input queries");
+    const std::vector<InputFastx> inputs = file_list ? read_rfile(*file_list) : read_input_fastas(seq_files);
+    log.info("Parsed " + std::to_string(inputs.size()) + " samples in input query list");
+    log.info("Sketching input queries");
+    const size_t nq = inputs.size();
+    std::vector<uint16_t> query_bins(nq * S);
+    try {
+        std::atomic<size_t> next{0};
+        std::exception_ptr err;
+        std::mutex mu;
+        auto work = [&] {
+            try {
+                for (;;) {
+                    const size_t i = next.fetch_add(1);
+                    if (i >= nq) break;
+                    const std::vector<uint16_t> q = sketch_sample_inverted(inputs[i], inv.kmer_size, S, inv.rc);
+                    std::copy(q.begin(), q.end(), query_bins.begin() + i * S);
+                }
+            } catch (...) {
+                std::lock_guard<std::mutex> lk(mu);
+                err = std::current_exception();
+            }
+        };
+        std::vector<std::thread> pool;
+        for (size_t t = 1; t < std::min(threads, nq); ++t) pool.emplace_back(work);
+        work();
+        for (auto &t : pool) t.join();
+        if (err) std::rethrow_exception(err);
+    } catch (const std::exception &e) {
+        throw Panic(e.what());   // the reference panics on unreadable / empty input
+    }
+    const double t_sketch = since_start();
+
+    std::unique_ptr<TextSink> sink;
+    if (output) {
+        try {
+            sink = std::make_unique<FileSink>(*output);
+        } catch (const std::exception &e) {
+            throw Panic(e.what());
+        }
+    } else {
+        sink = std::make_unique<StreamSink>(std::cout);
+    }
+    auto write = [&](const std::string &text) {
+        if (!text.empty()) sink->finish(sink->begin(text.data(), text.size()), text.data(), text.size());
+    };
+
+    const std::unique_ptr<Device> dev_owner = dev_starting.get();
+    Device &dev = *dev_owner;
+    skl_inverted *ix = nullptr;
+    if (skl_inverted_create(dev.ctx(), index_bins.data(), n, S, &ix) != SKL_OK) throw std::runtime_error(skl_last_error());
+    std::unique_ptr<skl_inverted, int (*)(skl_inverted *)> ix_owner(ix, skl_inverted_destroy);
+    const double t_device = since_start();
+
+    log.info("Running queries in mode: " + mode_name);
+    {
+        std::string header = "Query";
+        if (mode == SKL_INVQ_MATCH_COUNT) {
+            for (const auto &name : inv.sample_names) header += "\t" + name;
+        } else {
+            header += "\tMatches";
+        }
+        write(header + "\n");
+    }
+    // bands of queries: 256 MB of results on the host at a time (at least one query)
+    const size_t words64 = (n + 63) / 64;
+    const size_t row_bytes = std::max<size_t>(1, mode == SKL_INVQ_MATCH_COUNT ? n * sizeof(uint32_t) : words64 * sizeof(uint64_t));
+    const size_t band = std::max<size_t>(1, std::min<size_t>(nq, (256ull << 20) / row_bytes));
+    auto compute = [&](size_t q0) {
+        const size_t rows = std::min(band, nq - q0);
+        std::vector<uint64_t> buf((rows * row_bytes + 7) / 8);
+        if (skl_inverted_query(dev.ctx(), ix, query_bins.data() + q0 * S, rows, mode, buf.data()) != SKL_OK) {
+            throw std::runtime_error(skl_last_error());
+        }
+        return buf;
+    };
+    double t_query = 0, t_write = 0;
+    std::future<std::vector<uint64_t>> pending;
+    if (nq) pending = std::async(std::launch::async, compute, (size_t)0);
+    for (size_t q0 = 0; q0 < nq; q0 += band) {
+        const auto t0 = std::chrono::steady_clock::now();
+        const std::vector<uint64_t> buf = pending.get();
+        if (q0 + band < nq) pending = std::async(std::launch::async, compute, q0 + band);
+        const auto t1 = std::chrono::steady_clock::now();
+        const size_t rows = std::min(band, nq - q0);
+        // format the band's rows on `threads` threads, in contiguous pieces, then write the pieces in order
+        const size_t n_pieces = std::min(rows, threads);
+        std::vector<std::string> pieces(n_pieces);
+        auto format = [&](size_t piece) {
+            std::string &o = pieces[piece];
+            char num[16];
+            for (size_t r = rows * piece / n_pieces; r < rows * (piece + 1) / n_pieces; ++r) {
+                o += inputs[q0 + r].first;
+                if (mode == SKL_INVQ_MATCH_COUNT) {
+                    const uint32_t *c = reinterpret_cast<const uint32_t *>(buf.data()) + r * n;
+                    for (size_t s = 0; s < n; ++s) {
+                        num[0] = '\t';
+                        const auto res = std::to_chars(num + 1, num + sizeof num, c[s]);
+                        o.append(num, res.ptr);
+                    }
+                } else {
+                    const uint64_t *bits = buf.data() + r * words64;
+                    char sep = '\t';
+                    for (size_t w = 0; w < words64; ++w) {
+                        for (uint64_t b = bits[w]; b; b &= b - 1) {   // ascending .ski index (RoaringBitmap order)
+                            o += sep;
+                            o += inv.sample_names[w * 64 + (size_t)__builtin_ctzll(b)];
+                            sep = ',';
+                        }
+                    }
+                }
+                o += '\n';
+            }
+        };
+        std::vector<std::thread> pool;
+        for (size_t t = 1; t < n_pieces; ++t) pool.emplace_back(format, t);
+        format(0);
+        for (auto &t : pool) t.join();
+        for (const auto &piece : pieces) write(piece);
+        const auto t2 = std::chrono::steady_clock::now();
+        t_query += std::chrono::duration<double>(t1 - t0).count();
+        t_write += std::chrono::duration<double>(t2 - t1).count();
+    }
+    std::cout.flush();
+    if (timing) {
+        std::fprintf(stderr, "TIMING inverted query: load=%.3fs sketch=%.3fs device=%.3fs query=%.3fs write=%.3fs\n",
+                     t_load, t_sketch - t_load, t_device - t_sketch, t_query, t_write);
+    }
+    g_listing_complete = true;
+    return 0;
+}
+
+// ---- `sketchlib inverted build|query|precluster` (src/cli.rs:329-461, src/lib.rs:485-789) ----
 int run_inverted(int argc, char **argv, int first, bool verbose, bool quiet)
 {
-    if (first >= argc) usage_error("'sketchlib inverted' requires a subcommand: build | precluster");
+    if (first >= argc) usage_error("'sketchlib inverted' requires a subcommand: build | query | precluster");
     const std::string sub = argv[first];
+    if (sub == "query") return run_inverted_query(argc, argv, first + 1, verbose, quiet);
     auto next_value = [&](int &i, const std::string &flag) -> std::string {
         if (i + 1 >= argc) usage_error("a value is required for '" + flag + "' but none was supplied");
         return argv[++i];
@@ -646,7 +842,7 @@ int run_inverted(int argc, char **argv, int first, bool verbose, bool quiet)
         return 0;
     }
     if (sub != "precluster") {
-        std::cerr << "error: unrecognized subcommand 'inverted " << sub << "' (this build provides `inverted build` and `inverted precluster`)\n";
+        std::cerr << "error: unrecognized subcommand 'inverted " << sub << "' (this build provides `inverted build`, `inverted query` and `inverted precluster`)\n";
         return 2;
     }
     g_usage = "sketchlib inverted precluster [OPTIONS] <SKI> <--skd <SKD>|--count>";
@@ -808,7 +1004,8 @@ int main(int argc, char **argv)
         std::cout << "Usage: sketchlib [OPTIONS] <COMMAND>\n\nCommands:\n"
                      "  sketch  Create sketches from input data (DNA assemblies, CPU)\n"
                      "  dist    Calculate pairwise distances using sketches (GPU)\n"
-                     "  inverted build|precluster  Inverted index of single-k sketches; kNN restricted to its candidates (GPU)\n";
+                     "  inverted build|query|precluster  Inverted index of single-k sketches; match queries against it (GPU);\n"
+                     "                                   kNN restricted to its candidates (GPU)\n";
         return sub >= argc ? 2 : 0;
     }
     if (strcmp(argv[sub], "sketch") == 0) {
@@ -850,7 +1047,7 @@ int main(int argc, char **argv)
     }
     if (strcmp(argv[sub], "dist") != 0) {
         std::cerr << "error: unrecognized subcommand '" << argv[sub]
-                  << "' (this build provides `sketch` (DNA assemblies, CPU), `dist` (GPU) and `inverted build|precluster`)\n";
+                  << "' (this build provides `sketch` (DNA assemblies, CPU), `dist` (GPU) and `inverted build|query|precluster`)\n";
         return 2;
     }
     DistArgs args = parse_dist(argc, argv, sub + 1);

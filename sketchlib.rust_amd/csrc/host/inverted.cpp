@@ -371,6 +371,31 @@ uint64_t Inverted::any_shared_bin_pairs(size_t threads) const
     return total.load();
 }
 
+std::vector<uint16_t> Inverted::dense_bins(const std::string &path) const
+{
+    const size_t S = index.size(), n = n_samples;
+    std::vector<uint16_t> out(n * S, 0);
+    std::vector<uint32_t> seen_in(n, 0);   // seen_in[s] == b + 1: sample s already has a value at bin b
+    for (size_t b = 0; b < S; ++b) {
+        size_t held = 0;
+        for (const auto &kv : index[b]) {
+            for (uint32_t s : kv.second) {   // (load() has checked every id against n_samples)
+                if (seen_in[s] == b + 1) {
+                    throw std::runtime_error(path + ": sample " + std::to_string(s) + " has more than one value at bin " + std::to_string(b));
+                }
+                seen_in[s] = (uint32_t)(b + 1);
+                out[(size_t)s * S + b] = kv.first;
+            }
+            held += kv.second.size();
+        }
+        if (held != n) {
+            throw std::runtime_error(path + ": bin " + std::to_string(b) + " holds " + std::to_string(held) + " of " +
+                                     std::to_string(n) + " samples (an index from `inverted build` has one value per sample and bin)");
+        }
+    }
+    return out;
+}
+
 // ---------------------------------------------------------------------------
 // .skq
 // ---------------------------------------------------------------------------

@@ -56,6 +56,10 @@ class Inverted {
                          std::vector<uint32_t> &out) const;
     // Number of distinct sample pairs sharing at least one bin (inverted.rs:271-300).
     uint64_t any_shared_bin_pairs(size_t threads) const;
+    // The index as the dense [n_samples][sketch_size] u16 matrix of the .skq layout, row = .ski sample index: a .ski
+    // written by `build` holds exactly one value per (sample, bin) (sketches are densified, inverted.rs:467-499).
+    // Throws std::runtime_error naming `path` if it does not.
+    std::vector<uint16_t> dense_bins(const std::string &path) const;
 };
 
 // Inverted::sketch_files_inverted for one single-entry sample (inverted.rs:303-395):

@@ -522,4 +522,31 @@ hipError_t launch_merge_states(const MergeStatesArgs &args, hipStream_t stream);
 hipError_t launch_topk_finalize(const uint32_t *run_key, const uint32_t *run_idx, const float *run_d1, uint64_t items,
                                 int ani_undo, uint64_t *out_idx, float *out_d0, float *out_d1, hipStream_t stream);
 
+// `inverted query` (inv_query.hip): u16 bins -> 16 bit planes per 32-bin word, then equality counts
+// of queries against every indexed sample.  Plane word (row, w, p) lives at
+// planes[(row0 + row) * stride_row + w * stride_word + p * stride_plane]: the index ([w][p][s]) takes
+// stride_row 1, stride_word 16 n, stride_plane n; the queries ([w][q][p]) 16, 16 nq_pad, 1.
+constexpr int IQ_QTILE = 64;   // queries per workgroup (inv_query.hip: why 64)
+constexpr int IQ_QTAIL = 8;    // ... for the queries of a band past its last full tile
+constexpr uint64_t IQ_MAX_BLOCKS = (1ull << 24) - 1;   // workgroups per launch (grid x 256 threads < 2^32)
+enum InvQueryMode : uint32_t { INVQ_COUNTS = 0, INVQ_ANY = 1, INVQ_ALL = 2 };
+struct InvPlanesArgs {
+    const uint16_t *bins;     // [rows][sketch_size]
+    uint32_t rows, sketch_size, words;
+    uint64_t row0, stride_row, stride_word, stride_plane;
+    uint32_t *planes;
+};
+struct InvQueryArgs {
+    const uint32_t *ref_planes;   // [words * 16][n]
+    const uint32_t *q_planes;     // [words][nq_pad][16], nq_pad = nq rounded up to IQ_QTILE, padding zero
+    uint32_t n, nq, nq_pad, words, sketch_size, tail_mask;
+    uint32_t q_first, n_qtiles;   // (set by launch_inv_query) first query of the launch, tiles per sample block
+    uint32_t mode;                // InvQueryMode
+    uint32_t *counts;             // INVQ_COUNTS: [nq][n]
+    uint64_t *bits;               // INVQ_ANY / INVQ_ALL: [nq][n_words64], bit s % 64 of word s / 64
+    uint64_t n_words64;
+};
+hipError_t launch_inv_planes(const InvPlanesArgs &a, hipStream_t stream);
+hipError_t launch_inv_query(const InvQueryArgs &a, hipStream_t stream);
+
 }  // namespace skl
