@@ -20,15 +20,17 @@ Order of a run (every phase is stated in the JSON line):
   1. PRECONDITIONING (`config.preconditioning_s`, default 1 s, untimed): the workload's own launch,
      back to back.  The chip's clock takes tens of milliseconds of sustained load to settle (the first
      launches after idle run 10-20 % slower), and the driver's 5 + 20 steps of a 0.16 ms launch are over
-     in 4 ms -- without this the line measures the clock ramp, not the kernel.
+     in 4 ms -- without this the line measures the clock ramp, not the kernel.  (--full, N = 1, small
+     launches: the same W + K steps are run and timed once BEFORE it, as the cold figure.)
   2. W warm-up steps, barrier + device sync, EXACTLY K timed steps, barrier + device sync -> `value`.
+A plain run ends here: it writes --dump-outputs and prints the line.  With `--full` it goes on:
   3. ROOFLINE PASS (fixed size, independent of K and W; default 100 launches at cfg 2, 3 for the large
      workloads): every launch bracketed by HIP events on the launch stream -> `roofline.kernel_avg_ms`;
      then the same launches once more with a one-wave sampler on a second stream that reads the shader
      clock the chip holds DURING them (`roofline.in_kernel_clock`: same launches, same launch history
      as the timed region; the kernel time of that pass is reported beside it).
   4. Untimed checks: sampled pairs of the timed output against the oracle; N > 1: the assembled matrix
-     against bands recomputed on rank 0.
+     against bands recomputed on rank 0, and the N = 1 figure of the same workload.
   5. N = 1: secondary legs (cfg 2 on Set R, cfg 3 / cfg 4 / cfg 5 at full size on this one GPU), HBM
      traffic of the launch from two rocprofv3 --pmc child passes of this script, CPU baseline.
 
@@ -448,6 +450,11 @@ def main():
                     help="U = random-bin sketches (north-star workload), R = related clusters (n <= 20000)")
     ap.add_argument("--precondition-s", type=float, default=1.0,
                     help="seconds of the workload's own launch, back to back, before the warm-up steps (untimed; 0: none)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run everything the headline figure does not need: the roofline passes, "
+                         "the checks against the oracle (N > 1: and of the assembled matrix), the N = 1 figure of an N > 1 "
+                         "workload, the secondary legs, the HBM traffic passes and the CPU baseline; N = 1: the cold figure "
+                         "before the preconditioning.  The options below that name these parts act only with --full")
     ap.add_argument("--roofline-launches", type=int, default=0,
                     help="launches of the fixed kernel-timing pass after the timed region (default: 100 for cfg2, 3 for large n)")
     ap.add_argument("--no-clock-sampler", action="store_true", help="roofline pass without the concurrent clock sampler")
@@ -480,7 +487,7 @@ def main():
 
     # The timed region runs the library in its default configuration: pair-kernel launches are NOT bracketed
     # with HIP events (skl_ctx_timing_enable is off unless asked for).  The roofline's kernel time comes from
-    # the fixed pass after it, where every launch is bracketed.
+    # the fixed pass after it (--full), where every launch is bracketed.
 
     import numpy as np
     import torch
@@ -605,9 +612,9 @@ def main():
 
     # ---- 0. COLD figure (N = 1, small launches): the driver's own W + K steps as the first launches after the slab
     # upload, before any preconditioning -- what a one-off `sketchlib dist` on 1 000 genomes sees.  Reported beside
-    # `value` (config.cold_pairs_per_s); never `value` itself.
+    # `value` (config.cold_pairs_per_s); never `value` itself.  --full only.
     cold = None
-    if dist is None and small_launch and args.precondition_s > 0:
+    if args.full and dist is None and small_launch and args.precondition_s > 0:
         for _ in range(warmup):
             local_launch()
         ctx.synchronize()
@@ -663,11 +670,12 @@ def main():
         dumped = dump_outputs(torch, np, args.dump_outputs, result, result.shape[0])
         del result
 
-    # ---- 3. the roofline pass: fixed size, every launch bracketed; then once more with the clock sampler beside it ----
+    # ---- 3. (--full) the roofline pass: fixed size, every launch bracketed; then once more with the clock sampler beside it ----
     # (bands[0] is rank 0's slice of `full` when nothing is gathered: the passes rewrite it with the same values)
-    avg_kernel_s, launches, pass_wall_s, _none = roofline_pass(ctx, local_launch, roofline_launches, sampler_interval_us, sampler=False)
+    if args.full:
+        avg_kernel_s, launches, pass_wall_s, _none = roofline_pass(ctx, local_launch, roofline_launches, sampler_interval_us, sampler=False)
     clock = None
-    if not args.no_clock_sampler and not under_profiler():
+    if args.full and not args.no_clock_sampler and not under_profiler():
         _k2, _l2, w2, clock = roofline_pass(ctx, local_launch, roofline_launches, sampler_interval_us, sampler=True,
                                             expect_s=pass_wall_s * roofline_launches)
         if clock is not None:
@@ -676,11 +684,11 @@ def main():
             clock["note"] = ("read in a second pass of the same launches (wall time per launch beside it: the sampler does not slow "
                              "them); frac_at_in_kernel_clock = frac x 2.4 / this clock")
 
-    # ---- 4. untimed: what was timed is what the reference computes ----
+    # ---- 4. (--full) untimed: what was timed is what the reference computes ----
     checksum = None
     verified = None
     n1_same = None
-    if rank == 0:
+    if rank == 0 and args.full:
         if hostbuf is not None:   # the assembled matrix lives in host memory: bring it to the device for the checks
             # (rank by rank: a copy may not span this rank's page-locked slice AND pageable memory)
             whole = hostbuf.assembled()
@@ -725,10 +733,6 @@ def main():
 
     out = None
     if rank == 0:
-        ncols = 2
-        b_pair = algorithmic_bytes_per_pair(nk, SS64, ncols)
-        achieved_gbs = (b_pair * my_pairs / avg_kernel_s) / 1e9 if avg_kernel_s > 0 else 0.0
-        valu = valu_block(my_pairs, avg_kernel_s, nk, SS64, clock, counted_lengths(kernel_name, nk))
         names = {"cfg2": "BASELINE configs[1]: 1k synthetic genomes all-vs-all",
                  "cfg3": "BASELINE configs[2]: 100k synthetic genomes all-vs-all (~5e9 pairs)"}
         gather_txt = ""
@@ -770,7 +774,8 @@ def main():
                 "preconditioning": (f"{precond_launches} back-to-back launches of this workload before the warm-up steps, untimed "
                                     "(the clock needs tens of ms of sustained load to settle; the driver's 25 steps last 4 ms)"
                                     if precond_launches else "none"),
-                "output_checksum_first_1e8_pairs": checksum,
+                "full": bool(args.full),
+                **({"output_checksum_first_1e8_pairs": checksum} if args.full else {}),
                 "early_break": {
                     "k_mer_lengths_counted_for_every_pair": counted_lengths(kernel_name, nk), "of": nk,
                     "decided_over_blocks_of_sample_ids": list(eb_plan["blocks"]), "blocks_disagree": eb_plan["mixed"],
@@ -788,7 +793,13 @@ def main():
                 **({"host_gather_pinned": bool(hostbuf.pinned)} if hostbuf is not None else {}),
                 **({"dumped_outputs": dumped} if dumped else {}),
             },
-            "roofline": {
+        }
+        if args.full:
+            ncols = 2
+            b_pair = algorithmic_bytes_per_pair(nk, SS64, ncols)
+            achieved_gbs = (b_pair * my_pairs / avg_kernel_s) / 1e9 if avg_kernel_s > 0 else 0.0
+            valu = valu_block(my_pairs, avg_kernel_s, nk, SS64, clock, counted_lengths(kernel_name, nk))
+            out["roofline"] = {
                 # The resource that binds: the vector ALU.  HBM does not: see
                 # hbm_no_reuse below.
                 "bound": "valu",
@@ -810,13 +821,13 @@ def main():
                     "peak_GBs": HBM_PEAK_GBS,
                     "reuse_factor": achieved_gbs / HBM_PEAK_GBS,
                 },
-            },
-        }
-        print(f"[bench] primary: {out['value']:.4g} pairs/s, kernel {avg_kernel_s * 1e3:.4f} ms", file=sys.stderr)
+            }
+        print(f"[bench] primary: {out['value']:.4g} pairs/s"
+              + (f", kernel {avg_kernel_s * 1e3:.4f} ms" if args.full else ""), file=sys.stderr)
 
-    # ---- 5. N = 1 secondary legs (untimed by the driver's metric; each reports its own rate) ----
+    # ---- 5. (--full) N = 1 secondary legs (untimed by the driver's metric; each reports its own rate) ----
     single = rank == 0 and world == 1 and dist is None
-    if single and workload == "cfg2" and not args.no_secondary:
+    if args.full and single and workload == "cfg2" and not args.no_secondary:
         sk.close()
         del full, bands, bins
         torch.cuda.empty_cache()
@@ -825,7 +836,7 @@ def main():
                                                     cpu_too=not args.no_cpu_baseline)
         torch.cuda.empty_cache()
 
-    if rank == 0:
+    if rank == 0 and args.full:
         # HBM traffic of the launch (N = 1): measured now by two rocprofv3 --pmc child passes, else the committed figure
         traffic = None
         if single and not args.no_traffic and not under_profiler():
@@ -842,7 +853,7 @@ def main():
         dist.destroy_process_group()
     if rank == 0:
         # (after the process group is gone: the other ranks have exited and their host threads are not in the way)
-        if not args.no_cpu_baseline:
+        if args.full and not args.no_cpu_baseline:
             sk = bins = full = bands = None        # (device memory is not needed any more)
             out["cpu_baseline"] = cpu_baseline(n, KMERS, SS64, args.dataset)
         print(json.dumps(out), flush=True)

@@ -6,8 +6,8 @@ cd "$R"
 OUT=$R/gpurun_out/round_r05
 mkdir -p "$OUT"
 AB=$R/sketchlib.rust_amd/csrc/_build_ab/libsketchlib_dist_hip.so
-python3 bench.py > "$OUT/bench_default.json" 2> "$OUT/bench_default.err"
-python3 bench.py --steps 20 --warmup 5 --secondary none --no-cpu-baseline > "$OUT/bench_driver_args.json" 2> "$OUT/bench_driver_args.err"
+python3 bench.py --full > "$OUT/bench_default.json" 2> "$OUT/bench_default.err"
+python3 bench.py --full --steps 20 --warmup 5 --secondary none --no-cpu-baseline > "$OUT/bench_driver_args.json" 2> "$OUT/bench_driver_args.err"
 bash scripts/profile_bench.sh r05_cfg2 > "$OUT/profile_cfg2.log" 2>&1
 # the fused epilogue that lost (A/B library): two launches / fused / fused without the epilogue's work / fused, loads + stores only
 { python3 scripts/fuse_probe.py; for v in 0 1 2 4; do SKL_LIBRARY=$AB SKL_FUSE_EPILOGUE=1 SKL_FUSE_VARIANT=$v python3 scripts/fuse_probe.py; done; SKL_LIBRARY=$AB python3 scripts/fuse_probe.py; } > "$OUT/fuse_probe.txt" 2>/dev/null

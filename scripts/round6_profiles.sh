@@ -6,8 +6,8 @@ cd "$R"
 OUT=$R/gpurun_out/round_r06
 mkdir -p "$OUT"
 AB=$R/sketchlib.rust_amd/csrc/_build_ab/libsketchlib_dist_hip.so
-python3 bench.py > "$OUT/bench_default.json" 2> "$OUT/bench_default.err"
-python3 bench.py --steps 20 --warmup 5 --secondary none --no-cpu-baseline > "$OUT/bench_driver_args.json" 2> "$OUT/bench_driver_args.err"
+python3 bench.py --full > "$OUT/bench_default.json" 2> "$OUT/bench_default.err"
+python3 bench.py --full --steps 20 --warmup 5 --secondary none --no-cpu-baseline > "$OUT/bench_driver_args.json" 2> "$OUT/bench_driver_args.err"
 # cfg 2: kernel stats + HBM traffic + SQ / TCC / stall counters of the pair kernel and the epilogue
 bash scripts/profile_bench.sh r06_cfg2 > "$OUT/profile_cfg2.log" 2>&1
 # the early break as the product library decides it: every case of the probe

@@ -7,10 +7,10 @@ cd "$R"
 TAG=$1
 OUT=$R/gpurun_out/round_$TAG
 mkdir -p "$OUT"
-python3 bench.py > "$OUT/bench_default.json" 2> "$OUT/bench_default.err"
-python3 bench.py --dataset R --no-secondary > "$OUT/bench_cfg2_R.json" 2> "$OUT/bench_cfg2_R.err"
-python3 bench.py --n 16000 --steps 20 --warmup 3 --no-cpu-baseline > "$OUT/bench_n16000.json" 2> "$OUT/bench_n16000.err"
-python3 bench.py --workload cfg3 --no-cpu-baseline > "$OUT/bench_cfg3_1gpu.json" 2> "$OUT/bench_cfg3_1gpu.err"
+python3 bench.py --full > "$OUT/bench_default.json" 2> "$OUT/bench_default.err"
+python3 bench.py --full --dataset R --no-secondary > "$OUT/bench_cfg2_R.json" 2> "$OUT/bench_cfg2_R.err"
+python3 bench.py --full --n 16000 --steps 20 --warmup 3 --no-cpu-baseline > "$OUT/bench_n16000.json" 2> "$OUT/bench_n16000.err"
+python3 bench.py --full --workload cfg3 --no-cpu-baseline > "$OUT/bench_cfg3_1gpu.json" 2> "$OUT/bench_cfg3_1gpu.err"
 bash scripts/profile_bench.sh ${TAG}_cfg2 > "$OUT/profile_cfg2.log" 2>&1
 bash scripts/profile_bench.sh ${TAG}_n16000 --n 16000 --steps 6 --warmup 2 > "$OUT/profile_n16000.log" 2>&1
 T=scripts/microbench/_build/kslice_trace

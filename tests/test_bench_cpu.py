@@ -56,6 +56,21 @@ def test_plain_gpus_2_starts_its_own_ranks_and_fails_only_for_want_of_a_gpu():
     assert res.returncode != 0 and not [l for l in res.stdout.splitlines() if l.startswith("{")]
 
 
+def test_full_is_an_option_of_its_own():
+    """--full (everything beyond the headline figure) parses, off by default.  Parsing only: a negative --steps stops the run
+    right after the parser, before torch is imported or a GPU touched."""
+    import subprocess
+    import sys
+
+    for extra in ([], ["--full"]):
+        res = subprocess.run([sys.executable, "bench.py", "--gpus", "1", "--steps", "-1", "--warmup", "1"] + extra, cwd=ROOT,
+                             capture_output=True, text=True, timeout=120)
+        assert res.returncode == 2 and "must not be negative" in res.stderr, res.stderr[-2000:]
+        assert "unrecognized arguments" not in res.stderr
+    assert "--full" in subprocess.run([sys.executable, "bench.py", "--help"], cwd=ROOT, capture_output=True, text=True,
+                                      timeout=120).stdout
+
+
 def test_cpu_baseline_sample_is_bounded():
     b = _bench()
     assert b.CPU_SAMPLE_MAX_N == 20_000      # cfg 3's CPU leg: 2e8 pairs, not 5e9

@@ -6,6 +6,7 @@ import json
 import os
 import subprocess
 import sys
+import time
 
 import pytest
 
@@ -49,7 +50,7 @@ def test_bench_with_several_ranks_on_the_one_gpu(gpu_ctx, world, gather, port):
     one-wave kernels of several processes on ONE GPU time-slice each other for minutes.)"""
     extra = ["--no-clock-sampler"] if world > 3 else []
     line = _torchrun_world(world, ["bench.py", "--gpus", str(world), "--samples", "4000", "--steps", "3", "--warmup", "1",
-                                   "--gather", gather, "--no-cpu-baseline", "--precondition-s", "0.05", "--msg-mib", "8"] + extra, port)
+                                   "--gather", gather, "--no-cpu-baseline", "--precondition-s", "0.05", "--msg-mib", "8", "--full"] + extra, port)
     assert line["n_gpus"] == world and line["scaling"] == "strong" and line["config"]["n_samples"] == 4000
     assert f"{world} row band(s)" in line["config"]["partition"]
     assert ("shared, pinned host buffer" if gather == "host" else "gather to rank 0") in line["config"]["partition"]
@@ -61,11 +62,12 @@ def test_bench_with_several_ranks_on_the_one_gpu(gpu_ctx, world, gather, port):
 def test_plain_bench_gpus_2_launches_itself(gpu_ctx):
     """`python bench.py --gpus 2 ...` as typed -- no torch.distributed.run in front, WORLD_SIZE unset: bench.py starts the
     two ranks itself as a fresh child process (here over gloo, both on the one GPU) and relays rank 0's JSON line, which
-    carries the CPU baseline and the N = 1 figure of the same workload."""
+    with --full carries the CPU baseline and the N = 1 figure of the same workload."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "TORCHELASTIC_RUN_ID")}
     env["SKL_BENCH_BACKEND"] = "gloo"
     res = subprocess.run([sys.executable, "bench.py", "--gpus", "2", "--samples", "4000", "--steps", "3", "--warmup", "1",
-                          "--precondition-s", "0.05", "--msg-mib", "8"], cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
+                          "--precondition-s", "0.05", "--msg-mib", "8", "--full"], cwd=ROOT, env=env, capture_output=True, text=True,
+                         timeout=900)
     assert res.returncode == 0, (res.stdout[-2000:], res.stderr[-4000:])
     line = _last_json(res.stdout)
     assert line["n_gpus"] == 2 and line["scaling"] == "strong" and line["config"]["n_samples"] == 4000
@@ -78,7 +80,7 @@ def test_plain_bench_gpus_2_launches_itself(gpu_ctx):
 
 def test_bench_line_on_the_drivers_arguments(gpu_ctx):
     """`--steps 20 --warmup 5` is what the driver passes: the roofline's kernel time must not depend on it."""
-    res = subprocess.run([sys.executable, "bench.py", "--gpus", "1", "--steps", "20", "--warmup", "5", "--no-cpu-baseline",
+    res = subprocess.run([sys.executable, "bench.py", "--gpus", "1", "--steps", "20", "--warmup", "5", "--full", "--no-cpu-baseline",
                           "--no-secondary"], cwd=ROOT, capture_output=True, text=True, timeout=900)
     assert res.returncode == 0, res.stderr[-4000:]
     line = _last_json(res.stdout)
@@ -105,6 +107,27 @@ def test_bench_line_on_the_drivers_arguments(gpu_ctx):
     # HBM bytes per launch measured by the two rocprofv3 --pmc child passes of this run
     tr = rf["traffic"]
     assert tr["source"].startswith("live:") and 4.0e7 < tr["bytes"] < 2.0e9, tr
+
+
+def test_plain_bench_line_is_the_headline_alone(gpu_ctx):
+    """The driver's arguments without --full: set-up, preconditioning, warm-up, the timed steps and the line, nothing more --
+    no cold figure, roofline passes, oracle checks, secondary legs, traffic passes or CPU baseline -- and at most 30 s of
+    the whole process outside its warm-up and timed steps."""
+    t0 = time.perf_counter()
+    res = subprocess.run([sys.executable, "bench.py", "--gpus", "1", "--steps", "20", "--warmup", "5"], cwd=ROOT,
+                         capture_output=True, text=True, timeout=600)
+    wall = time.perf_counter() - t0
+    assert res.returncode == 0, res.stderr[-4000:]
+    line = _last_json(res.stdout)
+    assert line["metric"] == "sketch-pair distances/sec (whole node); achieved HBM GB/s vs roofline"
+    assert line["unit"] == "pairs/s" and line["higher_is_better"] is True and line["dtype"] == "u32"
+    assert line["n_gpus"] == 1 and line["steps"] == 20 and line["warmup"] == 5 and line["config"]["pairs"] == 499500
+    assert abs(line["value"] * line["ms_per_step"] / 1e3 - 499500) < 1e-6 * 499500
+    assert line["config"]["full"] is False and 0.5 <= line["config"]["preconditioning_s"] <= 3.0
+    assert "roofline" not in line and "cpu_baseline" not in line
+    for key in ("cold", "verified_pairs", "secondary", "output_checksum_first_1e8_pairs"):
+        assert key not in line["config"], key
+    assert wall - 25 * line["ms_per_step"] / 1e3 < 30.0, wall
 
 
 def test_bench_dumps_what_its_last_step_computed(skl, gpu_ctx, tmp_path):
@@ -151,7 +174,7 @@ def test_clock_sampler_reads_a_plausible_clock(skl, gpu_ctx):
 
 def test_bench_rccl_path_with_one_rank(gpu_ctx):
     line = _torchrun(["bench.py", "--gpus", "1", "--workload", "cfg3", "--samples", "6000", "--steps", "3", "--warmup", "1",
-                      "--loopback", "--no-cpu-baseline", "--msg-mib", "16"], 29611)     # 144 MB band = 9 messages
+                      "--loopback", "--full", "--no-cpu-baseline", "--msg-mib", "16"], 29611)     # 144 MB band = 9 messages
     assert line["n_gpus"] == 1 and line["config"]["n_samples"] == 6000
     assert "RCCL" in line["config"]["partition"] and "overlapped" in line["config"]["partition"] and "16 MiB" in line["config"]["partition"]
     assert line["config"]["verified_pairs"] >= 2000 and line["config"]["max_abs_err"] <= 1e-6
@@ -160,7 +183,7 @@ def test_bench_rccl_path_with_one_rank(gpu_ctx):
 
 def test_bench_host_gather_with_one_rank(gpu_ctx):
     line = _torchrun(["bench.py", "--gpus", "1", "--workload", "cfg3", "--samples", "6000", "--steps", "3", "--warmup", "1",
-                      "--gather", "host", "--no-cpu-baseline"], 29613)
+                      "--gather", "host", "--full", "--no-cpu-baseline"], 29613)
     assert "shared, pinned host buffer" in line["config"]["partition"]
     assert line["config"]["verified_pairs"] >= 2000 and line["config"]["max_abs_err"] <= 1e-6
 
@@ -170,7 +193,7 @@ def test_rccl_loopback_gather_at_cfg3_full_size(gpu_ctx):
     0 to itself over RCCL in 1 GiB messages (38 send/recv pairs per step, two rotating band buffers), and the
     assembled matrix is compared band by band with what rank 0 computes alone."""
     line = _torchrun(["bench.py", "--gpus", "1", "--workload", "cfg3", "--steps", "2", "--warmup", "1", "--loopback",
-                      "--no-cpu-baseline", "--precondition-s", "0"], 29614)
+                      "--full", "--no-cpu-baseline", "--precondition-s", "0"], 29614)
     assert line["config"]["n_samples"] == 100000 and line["config"]["pairs"] == 4999950000
     assert "RCCL" in line["config"]["partition"] and "1024 MiB" in line["config"]["partition"]
     assert line["config"]["verified_pairs"] >= 2000 and line["config"]["max_abs_err"] <= 1e-6
