@@ -387,6 +387,35 @@ int skl_sketch_signs_packed(skl_ctx *ctx, const uint32_t *packed, const uint64_t
                             const uint64_t *offsets, const uint64_t *offset_begin, size_t n_samples,
                             const size_t *kmers, size_t nk, uint64_t num_bins, int rc, uint64_t *out_signs);
 
+/* Read sketching with a k-mer count filter.  The reference offers a window's sign to its count
+ * filter only if the sign is below the current minimum of its bin (Sketch::bin_sign, src/sketch/mod.rs:198-210;
+ * the filter: src/hashing/bloom_filter.rs), and a bin's minimum only ever falls.  So under any bin state the
+ * caller has already reached -- however stale -- a window whose sign is >= its bin's value is never offered and
+ * can be dropped; replaying only the other windows ("survivors") in stream order through the same filter gives
+ * the reference's bins bit for bit.
+ *
+ * skl_reads_create uploads a batch of read sets once: `packed`, code_begin, offsets, offset_begin as for
+ * skl_sketch_signs_packed, in the reference's padded two-file layout (nthash_iterator.rs:205-251: each file
+ * starts on a multiple of 4 positions, codes cut at the number of valid bases; csrc/host/sketch.cpp
+ * load_sample).  A window [p, p+k) is valid iff p + k <= the sample's code count and no offset o has
+ * p < o < p+k.  Stream (s, ki) = sample s at kmers[ki], index s * nk + ki.
+ *
+ * skl_reads_survivors: for every stream, the valid windows with start in [win_begin[s], win_end[s]) whose
+ * sign (canonical -- rc != 0 -- ntHash % SIGN_MOD) is strictly below thresholds[stream][bin], bin = sign /
+ * ceil(SIGN_MOD / num_bins).  out_survivors[stream][0 .. capacity) receives (window start, sign) pairs in
+ * no particular order; out_counts[stream] is the number of survivors, which may exceed capacity: the records
+ * of such a stream are incomplete and the call must be repeated with capacity >= that count (nothing else
+ * changes between the two calls).  Thresholds of all u64::MAX keep every valid window.  Host pointers.
+ * Without a visible device skl_reads_create returns SKL_ERR_NO_DEVICE (pass ctx = NULL): there is no CPU path. */
+typedef struct skl_reads skl_reads;
+int skl_reads_create(skl_ctx *ctx, const uint32_t *packed, const uint64_t *code_begin, const uint64_t *offsets,
+                     const uint64_t *offset_begin, size_t n_samples, const size_t *kmers, size_t nk,
+                     uint64_t num_bins, int rc, skl_reads **out);
+int skl_reads_survivors(skl_reads *r, const uint64_t *win_begin, const uint64_t *win_end,
+                        const uint64_t *thresholds, uint64_t capacity, uint64_t *out_survivors,
+                        uint64_t *out_counts);
+int skl_reads_destroy(skl_reads *r);
+
 /* Candidate-list form of skl_self_dists_knn: the device half of self_dists_knn_precluster
  * (src/distances/mod.rs:399-553).  Row i is compared only with the samples
  * cand[row_offsets[i] .. row_offsets[i+1]) (ascending sample ids, i itself excluded) -- what

@@ -115,6 +115,9 @@ _SIG = [
     ("skl_inverted_band_queries", C.c_size_t, [_P, _P, C.c_int]),
     ("skl_sketch_signs", C.c_int, [_P, _P, _P, _P, _P, C.c_size_t, _P, C.c_size_t, C.c_uint64, C.c_int, _P]),
     ("skl_sketch_signs_packed", C.c_int, [_P, _P, _P, _P, _P, C.c_size_t, _P, C.c_size_t, C.c_uint64, C.c_int, _P]),
+    ("skl_reads_create", C.c_int, [_P, _P, _P, _P, _P, C.c_size_t, _P, C.c_size_t, C.c_uint64, C.c_int, C.POINTER(_P)]),
+    ("skl_reads_survivors", C.c_int, [_P, _P, _P, _P, C.c_uint64, _P, _P]),
+    ("skl_reads_destroy", C.c_int, [_P]),
     ("skl_self_binmatch", C.c_int, [_P, _P, _P, C.c_int]),
     ("skl_cross_binmatch", C.c_int, [_P, _P, _P, _P, C.c_int]),
     ("skl_self_dists_all_host", C.c_int, [_P, C.c_size_t, C.c_size_t, _P, C.c_size_t,
@@ -693,6 +696,48 @@ def sketch_signs_packed(ctx, packed, code_begin, offsets, offset_begin, kmers, n
                                           kmers.ctypes.data, kmers.size, num_bins, int(rc), out.ctypes.data))
     return out
 
+
+
+class Reads:
+    """skl_reads: a batch of read sets resident on the device, in the reference's padded layout (packed as
+    pack_codes packs them), for skl_reads_survivors.  ctx=None asks without a device."""
+
+    def __init__(self, ctx, packed, code_begin, offsets, offset_begin, kmers, num_bins, rc=True):
+        packed = np.ascontiguousarray(packed, dtype=np.uint32)
+        self.code_begin = np.ascontiguousarray(code_begin, dtype=np.uint64)
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        offset_begin = np.ascontiguousarray(offset_begin, dtype=np.uint64)
+        kmers = np.ascontiguousarray(kmers, dtype=np.uintp)
+        self.n, self.nk, self.num_bins = self.code_begin.size - 1, kmers.size, int(num_bins)
+        self._h = _P()
+        _check(load().skl_reads_create(ctx._h if ctx is not None else None, packed.ctypes.data if packed.size else None,
+                                       self.code_begin.ctypes.data, offsets.ctypes.data if offsets.size else None,
+                                       offset_begin.ctypes.data, self.n, kmers.ctypes.data, self.nk, self.num_bins,
+                                       int(rc), C.byref(self._h)))
+
+    def survivors(self, win_begin, win_end, thresholds, capacity):
+        """-> (records uint64 [n * nk, capacity, 2] of (window start, sign), counts uint64 [n * nk]); a stream whose
+        count exceeds capacity holds only `capacity` of its survivors."""
+        win_begin = np.ascontiguousarray(win_begin, dtype=np.uint64)
+        win_end = np.ascontiguousarray(win_end, dtype=np.uint64)
+        thresholds = np.ascontiguousarray(thresholds, dtype=np.uint64)
+        assert win_begin.size == self.n and win_end.size == self.n and thresholds.size == self.n * self.nk * self.num_bins
+        recs = np.zeros((self.n * self.nk, int(capacity), 2), dtype=np.uint64)
+        counts = np.zeros(self.n * self.nk, dtype=np.uint64)
+        _check(load().skl_reads_survivors(self._h, win_begin.ctypes.data, win_end.ctypes.data, thresholds.ctypes.data,
+                                          int(capacity), recs.ctypes.data if recs.size else None, counts.ctypes.data))
+        return recs, counts
+
+    def close(self):
+        if self._h:
+            load().skl_reads_destroy(self._h)
+            self._h = _P()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 # ---- raw counts ----
 

@@ -445,7 +445,7 @@ int run_dist(const DistArgs &a)
     return 0;
 }
 
-// ---- `sketchlib sketch` (src/cli.rs:121-183, src/lib.rs:242-301), DNA assemblies ----
+// ---- `sketchlib sketch` (src/cli.rs:121-183, src/lib.rs:242-301), DNA assemblies and read sets ----
 struct SketchArgs {
     std::vector<std::string> seq_files;
     std::optional<std::string> file_list, output;
@@ -455,7 +455,43 @@ struct SketchArgs {
     size_t threads = 1;
     bool verbose = false, quiet = false;
     int gpu = -1;   // --gpu [D]: hash and take bin minima on device D (default: CPU)
+    uint16_t min_count = 5;   // DEFAULT_MINCOUNT, cli.rs:12-15 (read sets only)
+    uint8_t min_qual = 20;    // DEFAULT_MINQUAL (read sets only; compared with the raw quality byte)
 };
+
+// a u16 / u8 option as clap parses it: out of range is a usage error
+size_t parse_bounded(const std::string &flag, const std::string &v, size_t max)
+{
+    const size_t x = parse_usize(flag, v);
+    if (x > max || v.size() > 20) usage_error("invalid value '" + v + "' for '" + flag + "': " + v + " is not in 0..=" + std::to_string(max));
+    return x;
+}
+
+void print_sketch_help()
+{
+    std::cout <<
+        "Create sketches from input data\n\n"
+        "Usage: sketchlib sketch [OPTIONS] -o <OUTPUT> <--k-vals <K_VALS>|--k-seq <K_SEQ>> <SEQ_FILES|-f <FILE_LIST>>\n\n"
+        "A sample whose first file starts with a FASTQ record is a read set (one or two files, e.g. a pair); its\n"
+        "k-mers pass a count filter (--min-count) and its bases a quality filter (--min-qual).  FASTA samples\n"
+        "ignore both.\n\n"
+        "Options:\n"
+        "  -f <FILE_LIST>                  File listing sample names and their files (name<TAB>file[<TAB>file])\n"
+        "  -o <OUTPUT>                     Output prefix (.skm / .skd)\n"
+        "  -k, --k-vals <K_VALS>           K-mer lengths (comma separated)\n"
+        "      --k-seq <K_SEQ>             K-mer lengths as start,end,step\n"
+        "  -s, --sketch-size <SIZE>        Bins per k-mer length [default: 1000]\n"
+        "      --single-strand             Ignore the reverse complement\n"
+        "      --min-count <MIN_COUNT>     Read sets: minimum k-mer count [default: 5]\n"
+        "      --min-qual <MIN_QUAL>       Read sets: minimum quality byte of a base, compared raw (no Phred offset)\n"
+        "                                  [default: 20]\n"
+        "      --threads <THREADS>         Number of CPU threads [default: 1]\n"
+        "      --gpu                       Hash on the GPU (device 0); read sets replay the count filter on the host\n"
+        "      --device <D>                The same on device D\n"
+        "  -v, --verbose                   Show progress messages\n"
+        "      --quiet                     Don't show any messages\n"
+        "  -h, --help                      Print help\n";
+}
 
 std::vector<size_t> parse_list(const std::string &flag, const std::string &v)
 {
@@ -483,7 +519,8 @@ int run_sketch(int argc, char **argv, int first, bool verbose, bool quiet)
             if (i + 1 >= argc) usage_error("a value is required for '" + flag + "' but none was supplied");
             return argv[++i];
         };
-        if (arg == "-v" || arg == "--verbose") a.verbose = true;
+        if (arg == "-h" || arg == "--help") { print_sketch_help(); std::exit(0); }
+        else if (arg == "-v" || arg == "--verbose") a.verbose = true;
         else if (arg == "--quiet") a.quiet = true;
         else if (arg == "-f") a.file_list = value("-f <FILE_LIST>");
         else if (arg == "-o") a.output = value("-o <OUTPUT>");
@@ -496,9 +533,11 @@ int run_sketch(int argc, char **argv, int first, bool verbose, bool quiet)
         else if (arg == "--device") a.gpu = (int)parse_usize("--device <D>", value(arg));
         else if (arg == "--seq-type") {
             const std::string v = value(arg);
-            if (v != "dna") { std::cerr << "error: this build sketches DNA assemblies only (--seq-type " << v << ")\n"; return 2; }
+            if (v != "dna") { std::cerr << "error: this build sketches DNA only (--seq-type " << v << ")\n"; return 2; }
         }
-        else if (arg == "--min-count" || arg == "--min-qual" || arg == "--level") (void)value(arg);
+        else if (arg == "--min-count") a.min_count = (uint16_t)parse_bounded("--min-count <MIN_COUNT>", value(arg), 0xFFFF);
+        else if (arg == "--min-qual") a.min_qual = (uint8_t)parse_bounded("--min-qual <MIN_QUAL>", value(arg), 0xFF);
+        else if (arg == "--level") (void)value(arg);
         else if (arg.size() > 1 && arg[0] == '-') usage_error("unexpected argument '" + arg + "' found");
         else a.seq_files.push_back(arg);
     }
@@ -517,9 +556,9 @@ int run_sketch(int argc, char **argv, int first, bool verbose, bool quiet)
         if (a.gpu >= 0) {
             log.info("Hashing on GPU " + std::to_string(a.gpu));
             Device dev(a.gpu);
-            sketch_files_gpu(dev, *a.output, inputs, kmers, a.sketch_size, !a.single_strand, a.threads);
+            sketch_files_gpu(dev, *a.output, inputs, kmers, a.sketch_size, !a.single_strand, a.threads, a.min_count, a.min_qual);
         } else {
-            sketch_files(*a.output, inputs, kmers, a.sketch_size, !a.single_strand, a.threads);
+            sketch_files(*a.output, inputs, kmers, a.sketch_size, !a.single_strand, a.threads, a.min_count, a.min_qual);
         }
     } catch (const std::exception &e) {
         throw Panic(e.what());   // the reference panics on unreadable / empty input
@@ -1002,7 +1041,7 @@ int main(int argc, char **argv)
     }
     if (sub >= argc || strcmp(argv[sub], "-h") == 0 || strcmp(argv[sub], "--help") == 0) {
         std::cout << "Usage: sketchlib [OPTIONS] <COMMAND>\n\nCommands:\n"
-                     "  sketch  Create sketches from input data (DNA assemblies, CPU)\n"
+                     "  sketch  Create sketches from input data (DNA assemblies and read sets; CPU, or GPU with --gpu)\n"
                      "  dist    Calculate pairwise distances using sketches (GPU)\n"
                      "  inverted build|query|precluster  Inverted index of single-k sketches; match queries against it (GPU);\n"
                      "                                   kNN restricted to its candidates (GPU)\n";
@@ -1047,7 +1086,7 @@ int main(int argc, char **argv)
     }
     if (strcmp(argv[sub], "dist") != 0) {
         std::cerr << "error: unrecognized subcommand '" << argv[sub]
-                  << "' (this build provides `sketch` (DNA assemblies, CPU), `dist` (GPU) and `inverted build|query|precluster`)\n";
+                  << "' (this build provides `sketch` (DNA assemblies and read sets), `dist` (GPU) and `inverted build|query|precluster`)\n";
         return 2;
     }
     DistArgs args = parse_dist(argc, argv, sub + 1);

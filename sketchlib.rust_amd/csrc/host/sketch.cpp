@@ -1,5 +1,6 @@
 #include "sketch.hpp"
 #include "inverted.hpp"
+#include "read_filter.hpp"
 
 #include <zlib.h>
 
@@ -8,7 +9,9 @@
 #include <atomic>
 #include <cstring>
 #include <fstream>
+#include <memory>
 #include <mutex>
+#include <string_view>
 #include <stdexcept>
 #include <thread>
 
@@ -121,15 +124,108 @@ void add_fasta(const std::string &path, Sequence &s)
 
 namespace {
 
-// Bin minima of hash % SIGN_MOD over every valid k-mer (get_signs, sketch/mod.rs:132-153);
-// canonical hash = min(forward, reverse-complement) when rc (nthash_iterator.rs:62-68).
-// A window [s, s+k) is valid iff no offset o satisfies s < o < s+k (next_iterator, :325-346).
-void bin_minima(const Sequence &seq, size_t k, bool rc, std::vector<uint64_t> &signs)
+// needletail's format peek (nthash_iterator.rs:94-108): the first record of a file decides FASTA / FASTQ
+bool first_record_is_fastq(const std::string &path)
+{
+    gzFile f = gzopen(path.c_str(), "rb");
+    if (!f) throw std::runtime_error("Invalid path/file: " + path);
+    char buf[4096];
+    const int n = gzread(f, buf, sizeof buf);
+    gzclose(f);
+    for (int i = 0; i < n; ++i) {
+        if (buf[i] == '\n' || buf[i] == '\r' || buf[i] == ' ' || buf[i] == '\t') continue;
+        return buf[i] == '@';
+    }
+    return false;
+}
+
+// One FASTQ file into `s` (add_dna_seq, nthash_iterator.rs:205-251), four-line records: a base is kept
+// iff valid_base(b) && q[i] >= min_qual on the RAW quality byte (no -33 offset); a rejected base counts
+// as non-ACGT and pushes an offset, and so does every record end.  Positions continue from
+// s.codes.size().
+void add_fastq(const std::string &path, uint8_t min_qual, Sequence &s)
+{
+    const std::string data = read_maybe_gz(path);
+    const size_t n = data.size();
+    size_t i = 0;
+    auto next_line = [&](std::string_view &out) -> bool {
+        if (i >= n) return false;
+        const void *nl = std::memchr(data.data() + i, '\n', n - i);
+        const size_t e = nl ? (size_t)((const char *)nl - data.data()) : n;
+        out = std::string_view(data.data() + i, e - i);
+        if (!out.empty() && out.back() == '\r') out.remove_suffix(1);
+        i = e < n ? e + 1 : n;
+        return true;
+    };
+    auto bad = [&](const char *what) {
+        return std::runtime_error("Invalid FASTA/Q record in " + path + ": " + what);
+    };
+    s.codes.reserve(s.codes.size() + n / 2);
+    uint64_t counts[5] = {0, 0, 0, 0, 0};
+    std::string_view head, seq, plus, qual;
+    for (;;) {
+        bool more;
+        while ((more = next_line(head)) && head.empty()) {
+        }
+        if (!more) break;
+        if (head[0] != '@') throw bad("a record must start with '@'");
+        if (!next_line(seq) || !next_line(plus) || !next_line(qual)) throw bad("truncated record");
+        if (plus.empty() || plus[0] != '+') throw bad("the third line of a record must start with '+'");
+        if (qual.size() != seq.size()) throw bad("quality and sequence lengths differ");
+        for (size_t b = 0; b < seq.size(); ++b) {
+            const uint8_t base = (uint8_t)seq[b];
+            if (valid_base(base) && (uint8_t)qual[b] >= min_qual) {
+                const uint8_t code = encode_base(base);
+                s.codes.push_back(code);
+                ++counts[code];
+            } else {
+                ++counts[4];
+                s.offsets.push_back(s.codes.size());
+            }
+        }
+        s.offsets.push_back(s.codes.size());
+    }
+    for (int b = 0; b < 4; ++b) s.acgt[b] += counts[b];
+    s.non_acgt += counts[4];
+}
+
+}  // namespace
+
+void load_sample(const InputFastx &input, uint8_t min_qual, Sequence &s)
+{
+    const auto &files = input.second;
+    if (files.empty() || !first_record_is_fastq(files[0])) {
+        for (const auto &file : files) add_fasta(file, s);
+        return;
+    }
+    if (files.size() > 2) throw std::runtime_error("Input files are reads, but there are more than two input files");
+    s.reads = true;
+    for (const auto &file : files) {
+        // each file's last partial byte is left-aligned (nthash_iterator.rs:245-250): the next file starts on a whole
+        // byte, 0-3 bases of code 0 after the last base of this one
+        s.codes.resize((s.codes.size() + 3) / 4 * 4, 0);
+        if (first_record_is_fastq(file)) add_fastq(file, min_qual, s);
+        else add_fasta(file, s);
+    }
+    // the iterator stops at seq_len() = the number of valid bases (nthash_iterator.rs:74-76), in the padded
+    // coordinates: what lies past it is never hashed, and breaks past it cut no window
+    uint64_t total = 0;
+    for (uint64_t c : s.acgt) total += c;
+    s.codes.resize((size_t)total);
+    while (!s.offsets.empty() && s.offsets.back() > total) s.offsets.pop_back();
+}
+
+namespace {
+
+// Every valid k-mer's sign (hash % SIGN_MOD), in the order NtHashIterator yields them
+// (nthash_iterator.rs:470-520): f(start, sign) for each window start in ascending order; canonical
+// hash = min(forward, reverse-complement) when rc (nthash_iterator.rs:62-68).  A window [s, s+k) is
+// valid iff s + k <= codes.size() and no offset o satisfies s < o < s+k (next_iterator, :325-346).
+// Returns whether there was any valid window.
+template <class F>
+bool for_each_window(const Sequence &seq, size_t k, bool rc, F &&f)
 {
     const size_t n = seq.codes.size();
-    const uint64_t num_bins = signs.size();
-    const uint64_t bin_size = (SIGN_MOD + num_bins - 1) / num_bins;
-    if (n < k) throw std::runtime_error("K-mer larger than smallest valid sequence");
     // srol^(k-1) of each seed: the weight of the oldest base (forward) / newest base (reverse)
     uint64_t top_f[4], top_r[4];
     for (int b = 0; b < 4; ++b) {
@@ -162,9 +258,7 @@ void bin_minima(const Sequence &seq, size_t k, bool rc, std::vector<uint64_t> &s
         size_t s = start;
         for (;;) {
             const uint64_t h = rc ? std::min(fh, rh) : fh;
-            const uint64_t sign = h % SIGN_MOD;
-            uint64_t &slot = signs[sign / bin_size];
-            if (sign < slot) slot = sign;
+            f(s, h % SIGN_MOD);
             any = true;
             if (s + k >= run_end) break;
             const uint8_t old_b = seq.codes[s], new_b = seq.codes[s + k];
@@ -174,6 +268,19 @@ void bin_minima(const Sequence &seq, size_t k, bool rc, std::vector<uint64_t> &s
         }
         start = run_end;
     }
+    return any;
+}
+
+// Bin minima of the signs of every valid k-mer (get_signs, sketch/mod.rs:132-153).
+void bin_minima(const Sequence &seq, size_t k, bool rc, std::vector<uint64_t> &signs)
+{
+    const uint64_t num_bins = signs.size();
+    const uint64_t bin_size = (SIGN_MOD + num_bins - 1) / num_bins;
+    if (seq.codes.size() < k) throw std::runtime_error("K-mer larger than smallest valid sequence");
+    const bool any = for_each_window(seq, k, rc, [&](size_t, uint64_t sign) {
+        uint64_t &slot = signs[sign / bin_size];
+        if (sign < slot) slot = sign;
+    });
     if (!any) throw std::runtime_error("K-mer larger than smallest valid sequence");
 }
 
@@ -275,32 +382,56 @@ std::vector<size_t> parse_kmers(const std::vector<size_t> &k_vals, const std::ve
 }
 
 SketchResult sketch_sample(const InputFastx &input, const std::vector<size_t> &kmers, uint64_t sketch_size,
-                           bool rc)
+                           bool rc, uint16_t min_count, uint8_t min_qual)
 {
     Sequence seq;
-    for (const auto &file : input.second) add_fasta(file, seq);
+    load_sample(input, min_qual, seq);
     uint64_t total = 0;
     for (uint64_t c : seq.acgt) total += c;
     if (total == 0) throw std::runtime_error(input.first + " has no valid sequence");
     const uint64_t ss64 = (sketch_size + 63) / 64;  // num_bins, sketch/mod.rs:49-54
     const uint64_t num_bins = ss64 * 64;
+    const uint64_t bin_size = (SIGN_MOD + num_bins - 1) / num_bins;
     SketchResult out;
     out.usigs.assign((size_t)(ss64 * BBITS * kmers.size()), 0);
     bool densified = false;
+    std::vector<uint64_t> first_signs;   // signs[0] per k, for a read set's length estimate
+    std::unique_ptr<KmerFilter> filter;
+    if (seq.reads) filter.reset(new KmerFilter(min_count));
     for (size_t ki = 0; ki < kmers.size(); ++ki) {
         std::vector<uint64_t> signs((size_t)num_bins, UINT64_MAX);
-        bin_minima(seq, kmers[ki], rc, signs);
+        if (filter) {   // every window through the count filter, in stream order (get_signs, sketch/mod.rs:132-153)
+            filter->clear();
+            const bool any = for_each_window(seq, kmers[ki], rc, [&](size_t, uint64_t sign) {
+                offer_sign(signs.data(), bin_size, *filter, sign);
+            });
+            check_read_signs(any, signs, input.first, kmers[ki], min_count);
+        } else {
+            bin_minima(seq, kmers[ki], rc, signs);
+        }
         densified |= densify_bin(signs);
+        first_signs.push_back(signs[0]);
         fill_usigs(out.usigs.data() + ki * ss64 * BBITS, signs);
     }
     out.meta.name = input.first;
     out.meta.rc = rc;
-    out.meta.reads = false;
-    out.meta.seq_length = total;
+    out.meta.reads = seq.reads;
+    out.meta.seq_length = seq.reads ? reads_seq_length(first_signs) : total;
     out.meta.densified = densified;
     for (int b = 0; b < 4; ++b) out.meta.acgt[b] = seq.acgt[b];
     out.meta.non_acgt = seq.non_acgt;
     return out;
+}
+
+void check_read_signs(bool any_window, const std::vector<uint64_t> &signs, const std::string &name, size_t k,
+                      uint16_t min_count)
+{
+    if (!any_window) throw std::runtime_error("K-mer larger than smallest valid sequence");
+    // (the reference's densify_bin never returns on an all-empty sketch)
+    if (std::all_of(signs.begin(), signs.end(), [](uint64_t v) { return v == UINT64_MAX; })) {
+        throw std::runtime_error("no k-mer of " + name + " reached --min-count " + std::to_string(min_count) + " at k=" +
+                                 std::to_string(k) + ": every bin is empty");
+    }
 }
 
 std::vector<uint16_t> sketch_sample_inverted(const InputFastx &input, size_t k, uint64_t sketch_size, bool rc)
@@ -319,7 +450,8 @@ std::vector<uint16_t> sketch_sample_inverted(const InputFastx &input, size_t k, 
 }
 
 MultiSketch sketch_files(const std::string &output_prefix, const std::vector<InputFastx> &inputs,
-                         const std::vector<size_t> &kmers, uint64_t sketch_size, bool rc, size_t threads)
+                         const std::vector<size_t> &kmers, uint64_t sketch_size, bool rc, size_t threads,
+                         uint16_t min_count, uint8_t min_qual)
 {
     const uint64_t ss64 = (sketch_size + 63) / 64;
     const size_t sample_words = (size_t)(ss64 * BBITS * kmers.size());
@@ -333,7 +465,7 @@ MultiSketch sketch_files(const std::string &output_prefix, const std::vector<Inp
             const size_t i = next.fetch_add(1);
             if (i >= inputs.size()) break;
             try {
-                results[i] = sketch_sample(inputs[i], kmers, sketch_size, rc);
+                results[i] = sketch_sample(inputs[i], kmers, sketch_size, rc, min_count, min_qual);
             } catch (const std::exception &e) {
                 results[i].meta.name.clear();
                 results[i].usigs.clear();

@@ -31,8 +31,17 @@ struct Sequence {
     std::vector<size_t> offsets;
     uint64_t acgt[4] = {0, 0, 0, 0};
     uint64_t non_acgt = 0;
+    bool reads = false;   // FASTQ input: codes / offsets in the padded two-file layout of load_sample
 };
 void add_fasta(const std::string &path, Sequence &s);
+// A sample's files (NtHashIterator::new, nthash_iterator.rs:94-141).  FASTA: add_fasta per file (concatenated
+// without padding).  Reads (the first record of the first file is FASTQ; more than two files is an error): bases
+// kept iff valid and quality byte >= min_qual, each file starting on a multiple of 4 positions (the 0-3 bases
+// between are code 0), codes cut at the number of valid bases and offsets past it dropped.
+void load_sample(const InputFastx &input, uint8_t min_qual, Sequence &s);
+// A read set's k-mer length gave no window at all, or no k-mer passed the count filter: the error to raise.
+void check_read_signs(bool any_window, const std::vector<uint64_t> &signs, const std::string &name, size_t k,
+                      uint16_t min_count);
 bool densify_bin(std::vector<uint64_t> &signs);                     // sketch/mod.rs:237-258
 void fill_usigs(uint64_t *usigs, const std::vector<uint64_t> &signs);  // sketch/mod.rs:215-223
 
@@ -41,20 +50,23 @@ struct SketchResult {
     std::vector<uint64_t> usigs;  // [k][chunk][plane]
 };
 
-// Sketch::new (src/sketch/mod.rs:74-129) for one sample.
+// Sketch::new (src/sketch/mod.rs:74-129) for one sample.  min_count / min_qual apply to read sets only
+// (defaults 5 / 20, cli.rs:12-15).
 SketchResult sketch_sample(const InputFastx &input, const std::vector<size_t> &kmers, uint64_t sketch_size,
-                           bool rc);
+                           bool rc, uint16_t min_count = 5, uint8_t min_qual = 20);
 
 // sketch_files (src/sketch/mod.rs:283-391): writes <output_prefix>.skd and .skm; samples
 // keep their input order (what the reference yields with --threads 1).
 MultiSketch sketch_files(const std::string &output_prefix, const std::vector<InputFastx> &inputs,
-                         const std::vector<size_t> &kmers, uint64_t sketch_size, bool rc, size_t threads);
+                         const std::vector<size_t> &kmers, uint64_t sketch_size, bool rc, size_t threads,
+                         uint16_t min_count = 5, uint8_t min_qual = 20);
 
 class Device;
 // The same with the hashing / bin-minimum loop on the GPU (SURVEY 8f row f4,
 // skl_sketch_signs): FASTA parsing, densification, transpose and the file writers stay on the
 // host.  Output files are byte-identical to sketch_files'.
 MultiSketch sketch_files_gpu(Device &dev, const std::string &output_prefix, const std::vector<InputFastx> &inputs,
-                             const std::vector<size_t> &kmers, uint64_t sketch_size, bool rc, size_t threads);
+                             const std::vector<size_t> &kmers, uint64_t sketch_size, bool rc, size_t threads,
+                         uint16_t min_count = 5, uint8_t min_qual = 20);
 
 }  // namespace skl_host

@@ -1,17 +1,21 @@
-// sketch_gpu.cpp -- `sketchlib sketch --gpu`: FASTA parsing on host threads, hashing and bin
-// minima on the device (skl_sketch_signs), densify / transpose / file writers on the host.
+// sketch_gpu.cpp -- `sketchlib sketch --gpu`: FASTA / FASTQ parsing on host threads, hashing and bin
+// minima on the device (skl_sketch_signs), densify / transpose / file writers on the host.  Read sets
+// with a count filter (min_count >= 2) hash on the device too (skl_reads_survivors), in chunks of window
+// starts, and the host replays the survivors through the filter.
 #include <algorithm>
 #include <atomic>
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <exception>
 #include <memory>
 #include <mutex>
 #include <stdexcept>
 #include <thread>
 
 #include "distances.hpp"
+#include "read_filter.hpp"
 #include "sketch.hpp"
 #include "sketchlib_dist.h"
 
@@ -34,10 +38,166 @@ void parallel_for(size_t n, size_t threads, F f)
     work();
     for (auto &t : pool) t.join();
 }
+
+// one sample's one-byte codes -> ceil(len / 16) u32 words, code c at bits 2 (c % 16) of word c / 16
+void pack_codes(const std::vector<uint8_t> &c, uint32_t *out)
+{
+    const size_t whole = c.size() / 16;
+    for (size_t w = 0; w < whole; ++w) {
+        uint64_t lo, hi;
+        memcpy(&lo, c.data() + 16 * w, 8);
+        memcpy(&hi, c.data() + 16 * w + 8, 8);
+        auto squeeze = [](uint64_t v) -> uint32_t {   // 8 bytes of 2 significant bits -> 16 bits
+            v &= 0x0303030303030303ull;
+            v = (v | (v >> 6)) & 0x000F000F000F000Full;
+            v = (v | (v >> 12)) & 0x000000FF000000FFull;
+            v = (v | (v >> 24)) & 0xFFFFull;
+            return (uint32_t)v;
+        };
+        out[w] = squeeze(lo) | (squeeze(hi) << 16);
+    }
+    if (c.size() % 16) {
+        uint32_t word = 0;
+        for (size_t x = 16 * whole; x < c.size(); ++x) word |= (uint32_t)(c[x] & 3u) << (2u * (uint32_t)(x - 16 * whole));
+        out[whole] = word;
+    }
+}
+
+struct ReadsTiming {
+    double gpu = 0, replay_wait = 0;
+    uint64_t chunks = 0, window_starts = 0, survivors = 0;
+};
+
+// Bin minima after the count filter for the read sets `idx`.  Chunk j covers window starts
+// [pos_j, pos_j + len_j) of every sample and stream; its survivors are taken under the bins the replay had reached
+// before chunk j - 1's replay, so the kernel of chunk j runs while the host replays chunk j - 1.  The first chunk
+// (every bin empty: everything survives) is short and the chunks double up to the cap (SKL_READS_CHUNK_WINDOWS).
+// signs: [idx.size()][nk][num_bins]; any_window: [idx.size()][nk], whether the stream had a valid window at all.
+void reads_signs_gpu(Device &dev, const std::vector<Sequence> &seqs, const std::vector<size_t> &idx,
+                     const std::vector<size_t> &kmers, uint64_t num_bins, bool rc, uint16_t min_count, size_t threads,
+                     std::vector<uint64_t> &signs, std::vector<char> &any_window, ReadsTiming &tm)
+{
+    const size_t nk = kmers.size(), streams = idx.size() * nk;
+    const uint64_t bin_size = (SIGN_MOD + num_bins - 1) / num_bins;
+    const bool log_chunks = std::getenv("SKL_CLI_TIMING") != nullptr;
+    uint64_t cap_len = 1ull << 20;
+    if (const char *e = std::getenv("SKL_READS_CHUNK_WINDOWS")) cap_len = std::max<uint64_t>(1, std::strtoull(e, nullptr, 10));
+    signs.assign(streams * num_bins, UINT64_MAX);
+    any_window.assign(streams, 0);
+    std::vector<uint64_t> code_begin(idx.size() + 1, 0), word_begin(idx.size() + 1, 0), offset_begin(idx.size() + 1, 0), offsets;
+    uint64_t max_len = 0;
+    for (size_t i = 0; i < idx.size(); ++i) {
+        const Sequence &s = seqs[idx[i]];
+        code_begin[i + 1] = code_begin[i] + s.codes.size();
+        word_begin[i + 1] = word_begin[i] + (s.codes.size() + 15) / 16;
+        offsets.insert(offsets.end(), s.offsets.begin(), s.offsets.end());
+        offset_begin[i + 1] = offsets.size();
+        max_len = std::max<uint64_t>(max_len, s.codes.size());
+    }
+    std::vector<uint32_t> packed(std::max<uint64_t>(word_begin[idx.size()], 1));
+    parallel_for(idx.size(), threads, [&](size_t i) { pack_codes(seqs[idx[i]].codes, packed.data() + word_begin[i]); });
+    skl_reads *h = nullptr;
+    if (skl_reads_create(dev.ctx(), packed.data(), code_begin.data(), offsets.data(), offset_begin.data(), idx.size(),
+                         kmers.data(), nk, num_bins, rc ? 1 : 0, &h) != SKL_OK) {
+        throw std::runtime_error(skl_last_error());
+    }
+    struct Release {
+        skl_reads *h;
+        ~Release() { skl_reads_destroy(h); }
+    } release{h};
+    std::vector<std::unique_ptr<KmerFilter>> filters(streams);
+    for (auto &f : filters) f.reset(new KmerFilter(min_count));
+    // survivors of one chunk: records [streams][capacity][2] and counts
+    struct Chunk {
+        std::vector<uint64_t> recs, counts;
+        uint64_t capacity = 0;
+        bool live = false;
+    };
+    auto replay = [&](Chunk &c) {
+        if (!c.live) return;
+        parallel_for(streams, threads, [&](size_t st) {
+            const uint64_t m = c.counts[st];
+            if (m == 0) return;
+            any_window[st] = 1;   // (under all-empty bins every valid window survives)
+            const uint64_t *rec = c.recs.data() + st * c.capacity * 2;
+            std::vector<std::pair<uint64_t, uint64_t>> order(m);   // (window start, sign)
+            for (uint64_t x = 0; x < m; ++x) order[x] = {rec[2 * x], rec[2 * x + 1]};
+            std::sort(order.begin(), order.end());   // stream order: by window start
+            uint64_t *bins = signs.data() + st * num_bins;
+            for (const auto &o : order) offer_sign(bins, bin_size, *filters[st], o.second);
+        });
+        c.live = false;
+    };
+    const auto t0 = std::chrono::steady_clock::now();
+    auto secs = [&] { return std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count(); };
+    Chunk chunk[2];
+    uint64_t len = std::min<uint64_t>(cap_len, 1ull << 14), capacity = len;
+    std::vector<uint64_t> win_begin(idx.size()), win_end(idx.size());
+    size_t cur = 0;
+    for (uint64_t pos = 0; pos < max_len; pos += len, len = std::min(cap_len, 2 * len)) {
+        std::fill(win_begin.begin(), win_begin.end(), pos);
+        std::fill(win_end.begin(), win_end.end(), pos + len);
+        const std::vector<uint64_t> thresholds = signs;   // the replay's state before the previous chunk is replayed
+        Chunk &prev = chunk[cur ^ 1], &c = chunk[cur];
+        std::exception_ptr replay_error;
+        std::thread replayer([&] {
+            try {
+                replay(prev);
+            } catch (...) {
+                replay_error = std::current_exception();
+            }
+        });
+        const double g0 = secs();
+        capacity = std::min(capacity, len);
+        for (;;) {   // a stream with more survivors than room: the same call again with room for all of them
+            c.capacity = capacity;
+            c.recs.resize(streams * capacity * 2);
+            c.counts.assign(streams, 0);
+            const int rc_ = skl_reads_survivors(h, win_begin.data(), win_end.data(), thresholds.data(), capacity, c.recs.data(),
+                                                c.counts.data());
+            if (rc_ != SKL_OK) {
+                replayer.join();
+                throw std::runtime_error(skl_last_error());
+            }
+            const uint64_t most = *std::max_element(c.counts.begin(), c.counts.end());
+            if (most <= capacity) break;
+            capacity = most;
+        }
+        const double g1 = secs();
+        replayer.join();
+        if (replay_error) std::rethrow_exception(replay_error);
+        tm.gpu += g1 - g0;
+        tm.replay_wait += secs() - g1;
+        c.live = true;
+        uint64_t found = 0, most = 0, starts = 0;
+        for (uint64_t x : c.counts) {
+            found += x;
+            most = std::max(most, x);
+        }
+        for (size_t i = 0; i < idx.size(); ++i) {
+            const uint64_t n_i = code_begin[i + 1] - code_begin[i];
+            starts += pos < n_i ? std::min(len, n_i - pos) * nk : 0;
+        }
+        if (log_chunks) {
+            std::fprintf(stderr, "READS chunk %llu: window starts [%llu, %llu) x %zu streams, survivors %llu of %llu (%.3g)\n",
+                         (unsigned long long)tm.chunks, (unsigned long long)pos, (unsigned long long)(pos + len), streams,
+                         (unsigned long long)found, (unsigned long long)starts, starts ? (double)found / (double)starts : 0.0);
+        }
+        tm.chunks += 1;
+        tm.window_starts += starts;
+        tm.survivors += found;
+        capacity = std::max<uint64_t>(4096, 2 * most);   // next chunk's first guess
+        cur ^= 1;
+    }
+    const double r0 = secs();
+    replay(chunk[cur ^ 1]);
+    tm.replay_wait += secs() - r0;
+}
 }  // namespace
 
 MultiSketch sketch_files_gpu(Device &dev, const std::string &output_prefix, const std::vector<InputFastx> &inputs,
-                             const std::vector<size_t> &kmers, uint64_t sketch_size, bool rc, size_t threads)
+                             const std::vector<size_t> &kmers, uint64_t sketch_size, bool rc, size_t threads,
+                             uint16_t min_count, uint8_t min_qual)
 {
     const size_t n = inputs.size(), nk = kmers.size();
     const uint64_t ss64 = (sketch_size + 63) / 64;   // num_bins, sketch/mod.rs:49-54
@@ -60,7 +220,7 @@ MultiSketch sketch_files_gpu(Device &dev, const std::string &output_prefix, cons
                 const size_t i = next.fetch_add(1);
                 if (i >= n) break;
                 try {
-                    for (const auto &file : inputs[i].second) add_fasta(file, seqs[i]);
+                    load_sample(inputs[i], min_qual, seqs[i]);
                     uint64_t total = 0;
                     for (uint64_t c : seqs[i].acgt) total += c;
                     if (total == 0) throw std::runtime_error(inputs[i].first + " has no valid sequence");
@@ -78,15 +238,55 @@ MultiSketch sketch_files_gpu(Device &dev, const std::string &output_prefix, cons
     }
 
     t_parse = since();
-    // 2. hash + bin minima on the device, in batches of at most ~4 G bases
     std::vector<uint64_t> bins(sample_words * n, 0);
     std::vector<SketchMeta> meta(n);
+    // densify + transpose + metadata of sample `at` from its [nk][num_bins] signs (host threads)
+    std::string finish_error;
+    std::mutex finish_mu;
+    auto finish = [&](size_t at, const uint64_t *sample_signs, const char *any_window) {
+        try {
+            const Sequence &s = seqs[at];
+            bool densified = false;
+            std::vector<uint64_t> first_signs;
+            for (size_t ki = 0; ki < nk; ++ki) {
+                const uint64_t *src = sample_signs + ki * num_bins;
+                std::vector<uint64_t> sg(src, src + num_bins);
+                if (any_window) {
+                    check_read_signs(any_window[ki] != 0, sg, inputs[at].first, kmers[ki], min_count);
+                } else if (std::all_of(sg.begin(), sg.end(), [](uint64_t v) { return v == UINT64_MAX; })) {
+                    throw std::runtime_error("K-mer larger than smallest valid sequence");   // as the CPU path
+                }
+                densified |= densify_bin(sg);
+                first_signs.push_back(sg[0]);
+                fill_usigs(bins.data() + at * sample_words + ki * ss64 * BBITS, sg);
+            }
+            SketchMeta &m = meta[at];
+            m.name = inputs[at].first;
+            m.rc = rc;
+            m.reads = s.reads;
+            uint64_t total = 0;
+            for (uint64_t c : s.acgt) total += c;
+            m.seq_length = s.reads ? reads_seq_length(first_signs) : total;
+            m.densified = densified;
+            for (int x = 0; x < 4; ++x) m.acgt[x] = s.acgt[x];
+            m.non_acgt = s.non_acgt;
+            m.index = at;
+        } catch (const std::exception &e) {
+            std::lock_guard<std::mutex> lk(finish_mu);
+            if (finish_error.empty()) finish_error = e.what();
+        }
+    };
+    // read sets under a count filter go their own way; assemblies (and read sets without one) take the bin-minimum kernel
+    std::vector<size_t> plain, filtered;
+    for (size_t i = 0; i < n; ++i) (seqs[i].reads && min_count >= 2 ? filtered : plain).push_back(i);
+
+    // 2. hash + bin minima on the device, in batches of at most ~4 G bases
     constexpr uint64_t BATCH_CODES = 4ull << 30;
-    for (size_t b0 = 0; b0 < n;) {
+    for (size_t b0 = 0; b0 < plain.size();) {
         size_t b1 = b0;
         uint64_t codes_in_batch = 0;
-        while (b1 < n && (b1 == b0 || codes_in_batch + seqs[b1].codes.size() <= BATCH_CODES)) {
-            codes_in_batch += seqs[b1].codes.size();
+        while (b1 < plain.size() && (b1 == b0 || codes_in_batch + seqs[plain[b1]].codes.size() <= BATCH_CODES)) {
+            codes_in_batch += seqs[plain[b1]].codes.size();
             ++b1;
         }
         const size_t nb = b1 - b0;
@@ -94,36 +294,14 @@ MultiSketch sketch_files_gpu(Device &dev, const std::string &output_prefix, cons
         // bytes to gather here and to send over PCIe
         std::vector<uint64_t> code_begin(nb + 1, 0), word_begin(nb + 1, 0), offset_begin(nb + 1, 0), offsets;
         for (size_t i = 0; i < nb; ++i) {
-            const Sequence &s = seqs[b0 + i];
+            const Sequence &s = seqs[plain[b0 + i]];
             code_begin[i + 1] = code_begin[i] + s.codes.size();
             word_begin[i + 1] = word_begin[i] + (s.codes.size() + 15) / 16;
             offsets.insert(offsets.end(), s.offsets.begin(), s.offsets.end());
             offset_begin[i + 1] = offsets.size();
         }
         std::unique_ptr<uint32_t[]> packed(new uint32_t[std::max<uint64_t>(word_begin[nb], 1)]);   // not zero-filled
-        parallel_for(nb, threads, [&](size_t i) {
-            const std::vector<uint8_t> &c = seqs[b0 + i].codes;
-            uint32_t *out = packed.get() + word_begin[i];
-            const size_t whole = c.size() / 16;
-            for (size_t w = 0; w < whole; ++w) {
-                uint64_t lo, hi;
-                memcpy(&lo, c.data() + 16 * w, 8);
-                memcpy(&hi, c.data() + 16 * w + 8, 8);
-                auto squeeze = [](uint64_t v) -> uint32_t {   // 8 bytes of 2 significant bits -> 16 bits
-                    v &= 0x0303030303030303ull;
-                    v = (v | (v >> 6)) & 0x000F000F000F000Full;
-                    v = (v | (v >> 12)) & 0x000000FF000000FFull;
-                    v = (v | (v >> 24)) & 0xFFFFull;
-                    return (uint32_t)v;
-                };
-                out[w] = squeeze(lo) | (squeeze(hi) << 16);
-            }
-            if (c.size() % 16) {
-                uint32_t word = 0;
-                for (size_t x = 16 * whole; x < c.size(); ++x) word |= (uint32_t)(c[x] & 3u) << (2u * (uint32_t)(x - 16 * whole));
-                out[whole] = word;
-            }
-        });
+        parallel_for(nb, threads, [&](size_t i) { pack_codes(seqs[plain[b0 + i]].codes, packed.get() + word_begin[i]); });
         std::vector<uint64_t> signs(nb * nk * num_bins);
         const double t0 = since();
         t_pack += t0 - (t_parse + t_pack + t_gpu + t_finish);
@@ -132,42 +310,38 @@ MultiSketch sketch_files_gpu(Device &dev, const std::string &output_prefix, cons
         if (rc_ != SKL_OK) throw std::runtime_error(skl_last_error());
         t_gpu += since() - t0;
         // 3. densify + transpose (host threads)
-        std::string finish_error;
-        std::mutex finish_mu;
-        parallel_for(nb, threads, [&](size_t i) {
-          try {
-            const Sequence &s = seqs[b0 + i];
-            bool densified = false;
-            for (size_t ki = 0; ki < nk; ++ki) {
-                const uint64_t *src = signs.data() + (i * nk + ki) * num_bins;
-                std::vector<uint64_t> sg(src, src + num_bins);
-                if (std::all_of(sg.begin(), sg.end(), [](uint64_t v) { return v == UINT64_MAX; })) {
-                    throw std::runtime_error("K-mer larger than smallest valid sequence");   // as the CPU path
-                }
-                densified |= densify_bin(sg);
-                fill_usigs(bins.data() + (b0 + i) * sample_words + ki * ss64 * BBITS, sg);
-            }
-            SketchMeta &m = meta[b0 + i];
-            m.name = inputs[b0 + i].first;
-            m.rc = rc;
-            m.reads = false;
-            uint64_t total = 0;
-            for (uint64_t c : s.acgt) total += c;
-            m.seq_length = total;
-            m.densified = densified;
-            for (int x = 0; x < 4; ++x) m.acgt[x] = s.acgt[x];
-            m.non_acgt = s.non_acgt;
-            m.index = b0 + i;
-          } catch (const std::exception &e) {
-            std::lock_guard<std::mutex> lk(finish_mu);
-            if (finish_error.empty()) finish_error = e.what();
-          }
-        });
+        parallel_for(nb, threads, [&](size_t i) { finish(plain[b0 + i], signs.data() + i * nk * num_bins, nullptr); });
         if (!finish_error.empty()) throw std::runtime_error(finish_error);
-        for (size_t i = b0; i < b1; ++i) Sequence().codes.swap(seqs[i].codes);   // release
+        for (size_t i = b0; i < b1; ++i) Sequence().codes.swap(seqs[plain[i]].codes);   // release
         b0 = b1;
         t_finish = since() - t_parse - t_pack - t_gpu;
     }
+
+    // 2'. read sets with a count filter: survivors on the device, the filter replayed on the host.  A batch holds at most
+    // max(64, nk) streams (one 24 MiB filter each) and ~1 G bases.
+    ReadsTiming rt;
+    const double t_reads0 = since();
+    for (size_t b0 = 0; b0 < filtered.size();) {
+        size_t b1 = b0;
+        uint64_t codes_in_batch = 0;
+        while (b1 < filtered.size() &&
+               (b1 == b0 || ((b1 - b0 + 1) * nk <= std::max<size_t>(64, nk) && codes_in_batch + seqs[filtered[b1]].codes.size() <= (1ull << 30)))) {
+            codes_in_batch += seqs[filtered[b1]].codes.size();
+            ++b1;
+        }
+        const std::vector<size_t> idx(filtered.begin() + b0, filtered.begin() + b1);
+        std::vector<uint64_t> signs;
+        std::vector<char> any_window;
+        reads_signs_gpu(dev, seqs, idx, kmers, num_bins, rc, min_count, threads, signs, any_window, rt);
+        parallel_for(idx.size(), threads, [&](size_t i) {
+            finish(idx[i], signs.data() + i * nk * num_bins, any_window.data() + i * nk);
+        });
+        if (!finish_error.empty()) throw std::runtime_error(finish_error);
+        for (size_t i : idx) Sequence().codes.swap(seqs[i].codes);   // release
+        b0 = b1;
+    }
+    const double t_reads = since() - t_reads0;
+
     const double t_before_write = since();
     MultiSketch::write_sketch_data(output_prefix, bins.data(), bins.size());
     MultiSketch m(std::move(meta), ss64 * 64, kmers);
@@ -176,6 +350,12 @@ MultiSketch sketch_files_gpu(Device &dev, const std::string &output_prefix, cons
     if (timing) {
         std::fprintf(stderr, "TIMING sketch --gpu: parse=%.3fs pack=%.3fs upload+kernel+download=%.3fs densify+transpose=%.3fs write=%.3fs\n",
                      t_parse, t_pack, t_gpu, t_finish, since() - t_before_write);
+        if (!filtered.empty()) {
+            std::fprintf(stderr, "TIMING reads: total=%.3fs survivors_gpu=%.3fs replay_wait=%.3fs chunks=%llu window_starts=%llu "
+                                 "survivors=%llu\n",
+                         t_reads, rt.gpu, rt.replay_wait, (unsigned long long)rt.chunks, (unsigned long long)rt.window_starts,
+                         (unsigned long long)rt.survivors);
+        }
     }
     return m;
 }

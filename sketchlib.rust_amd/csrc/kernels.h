@@ -363,6 +363,31 @@ int sketch_span();
 int sketch_span_lds();
 int sketch_wg_lds();   // threads (= spans) per workgroup of the LDS-staged kernel: a sample's span count is padded to a multiple
 
+// Survivors of the read sketcher's count filter (read_survivors.hip, skl_reads_survivors): every valid window
+// of every (sample, k) stream in a range of window starts whose sign is below its bin's threshold.
+struct ReadSurvivorArgs {
+    const uint32_t *packed;        // 2-bit codes as SketchArgs::packed
+    const uint64_t *word_begin;    // [n_samples]
+    const uint64_t *code_begin;    // [n_samples + 1]
+    const uint64_t *offsets;       // breaks, each sample in its own coordinates, every one <= its code count
+    const uint64_t *offset_begin;  // [n_samples + 1]
+    const uint64_t *win_begin, *win_end;   // [n_samples] window starts [win_begin, win_end) of this launch
+    const uint64_t *span_begin;    // [n_samples + 1] prefix sum of this launch's spans, each sample's padded to whole waves
+    uint64_t n_spans;              // a multiple of 64
+    uint32_t n_samples, nk;
+    const uint32_t *kmers;         // [nk]
+    const uint64_t *top_f, *top_r; // [nk][4] srol^(k-1) of the forward / reverse seeds
+    uint64_t num_bins, bin_size;
+    double inv_bin_size;
+    int32_t rc;
+    const uint64_t *thresholds;    // [n_samples * nk][num_bins]
+    uint64_t capacity;             // records per stream
+    uint64_t *survivors;           // [n_samples * nk][capacity][2]: (window start, sign)
+    unsigned long long *counts;    // [n_samples * nk] survivors found (may exceed capacity), pre-zeroed
+};
+hipError_t launch_read_survivors(const ReadSurvivorArgs &args, hipStream_t stream);
+int read_survivor_span();   // window starts per thread
+
 // Candidate lists on the device (cand_gen.hip): any shared bin between index sketches.
 struct CandGenArgs {
     const uint16_t *skq;      // [n][sketch_size] index sketches, row = sample id
