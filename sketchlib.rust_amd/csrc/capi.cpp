@@ -19,6 +19,7 @@
 #include <cstring>
 #include <map>
 #include <mutex>
+#include <optional>
 #include <set>
 #include <string>
 #include <vector>
@@ -473,7 +474,7 @@ static hipError_t dispatch_pair_kernel(skl_ctx *ctx, const PairArgs &args_in, in
     {
         const uint64_t k_walked = mode == MODE_JACCARD ? 1u : args.k_count;
         if (ctx->knobs.tile32_min >= 0 && pairs * k_walked >= (uint64_t)ctx->knobs.tile32_min) shape = 325;
-        if (args.mid_band) shape = 325;   // dense_band's mid-band rule: 32-row tiles with the last round cut in 2
+        if (args.mid_band) shape = 325;   // the mid-band rule (dense_plan.hpp): 32-row tiles with the last round cut in 2
     }
 #ifdef SKL_AB
     const Knobs &kn = ctx->knobs;
@@ -492,14 +493,10 @@ static hipError_t dispatch_pair_kernel(skl_ctx *ctx, const PairArgs &args_in, in
     const bool sliced_launch = mode == MODE_JACCARD || (mode == MODE_COUNTS && (small || args.k_sliced || big_sketch));
     const uint32_t wg_per_cu = ((shape == 3255 && !sliced_launch) || (shape == 3254 && sliced_launch)) ? 3u : 4u;
     args.round_size = ctx->knobs.round_priority ? wg_per_cu * (uint32_t)ctx->n_cu / n_xcd : 0u;
-    ctx->last_count_planes = std::max(1u, args.k_slices);
-    ctx->last_tail = false;
     if (args.tail_slices > 1u) {
         // tail-sliced one-workgroup-per-unit launch: two planes whatever kernel ends up running (a
         // kernel without the slices leaves plane 1 as it found it: zero)
         args.tail_resident = wg_per_cu * (uint32_t)ctx->n_cu / n_xcd;
-        ctx->last_count_planes = 2;
-        ctx->last_tail = true;
     }
     if (try_kslice) {
         // single-k Jaccard: the sliced and the all-k form are the same work, the sliced one
@@ -935,50 +932,6 @@ int fill_args(const skl_sketches *rows, const skl_sketches *cols, const skl_dist
     return SKL_OK;
 }
 
-// Launch-size rule shared with dispatch_pair_kernel: core/acc launches below this many pairs
-// run k-sliced (counts + epilogue kernel), larger ones as one fused kernel.
-constexpr long long SLICED_MAX_PAIRS = 32ll << 20;   // n ~ 8000 all-vs-all: equal there (scripts/ab_sweep.py)
-constexpr size_t COUNTS_SCRATCH_MAX = 4ull << 30;    // bytes of bin-match counts one unfused core/accessory launch may park in HBM
-static bool coreacc_runs_sliced(const skl_ctx *ctx, const skl_sketches *s, uint64_t pairs)
-{
-    const int forced = forced_kernel(ctx);
-    if (forced != 0 && forced != 4) return false;   // another kernel forced: never slice
-    if (s->ss64 > (size_t)KSLICE_MAX_U16_CHUNKS) return true;   // beyond 65 535 bins the fused form's u16 fields do not hold a count: always counts + epilogue
-    const long long limit = ctx->knobs.sliced_max_pairs >= 0 ? ctx->knobs.sliced_max_pairs : SLICED_MAX_PAIRS;
-    return pairs < (uint64_t)limit;
-}
-
-static uint64_t cond_index(uint64_t i, uint64_t j, uint64_t n)
-{
-    return n * i - ((i * (i + 1)) >> 1) + j - 1 - i;  // distance_matrix.rs:11-14
-}
-
-// Number of pairs in rows [r0, r1) of the condensed triangle of n samples.
-static uint64_t self_rows_pairs(uint64_t r0, uint64_t r1, uint64_t n)
-{
-    if (n < 2) return 0;
-    r1 = std::min<uint64_t>(r1, n - 1);
-    if (r1 <= r0) return 0;
-    auto upto = [n](uint64_t r) { return r * n - r * (r + 1) / 2; };  // pairs with i < r
-    return upto(r1) - upto(r0);
-}
-
-
-// k-sliced core/accessory launches: into how many chunk slices to cut each k-mer length (the kernel
-// then runs one workgroup per (tile, k, slice) and the epilogue sums the partial counts).  Default: 1.
-// Measured on MI355X (profiles/r02_k_slices_experiment.txt): at BASELINE's 1 000 genomes -- 1 400
-// whole-k workgroups on 1 024 resident slots, 1.37 rounds that cost 2 -- 2 slices keep every SIMD at 4
-// waves for 100 of 163 us instead of 60 of 157 us, but each workgroup pays its fixed 7 + 2 us (first
-// row DMA under load, reduction and stores) on half the work, and the launch ends at the same time
-// (0.1601 vs 0.1600 ms per step); 4 slices are 3 % slower, and from n = 1 400 up slices only cost.
-// SKL_K_SLICES forces a value (tests keep the sliced form bit-exact; A/B runs).
-static uint32_t choose_k_slices(const skl_ctx *ctx, size_t ss64)
-{
-    const uint32_t S = ctx->knobs.k_slices > 0 ? std::min(8u, (uint32_t)ctx->knobs.k_slices) : 1u;
-    uint32_t chunks = 0;
-    return slice_plan((uint32_t)ss64, S, &chunks);   // (slices that hold something: a short sketch gets fewer)
-}
-
 // EARLY BREAK.  core_acc_dist leaves its loop over the k-mer lengths at the first one whose ln J lies below the tolerance
 // (jaccard.rs:89-91: J = 0, i.e. no more shared bins than chance -- expected_samebits, :26-31) and a fit over fewer than three
 // lengths is (1, 1) (:117): a pair that fails the test at one of its first lengths is decided by them alone, and between
@@ -996,7 +949,7 @@ static uint32_t choose_k_slices(const skl_ctx *ctx, size_t ss64)
 // EB_COST, measured (profiles/r06_early_break_forced_lengths.md: whole calls with 2 / 3 lengths forced, T(3) - T(2) = one length's
 // kernel time - EB_COST x the difference of the alive shares): 15-22.  Beyond 65 535 bins a completion is a run of thousands of
 // dependent trips of one wave and comes to ~60: there the early break is taken only where hardly a pair stays in the running.
-// Pair spaces large enough for the blocked epilogue order (below) complete a pair for ~12-15: cfg 3 with 2 / 3 lengths 642 / 733
+// Pair spaces large enough for the blocked epilogue order (dense_plan.hpp) complete a pair for ~12-15: cfg 3 with 2 / 3 lengths 642 / 733
 // ms, n = 16 000 17.2 / 19.3.
 constexpr double EB_COST = 20.0, EB_COST_BLOCKED = 12.0, EB_COST_BIG = 60.0;
 static double eb_cost_of(const skl_sketches *rows, const skl_sketches *cols, int self_mode)
@@ -1004,17 +957,6 @@ static double eb_cost_of(const skl_sketches *rows, const skl_sketches *cols, int
     if (rows->ss64 > (size_t)KSLICE_MAX_U16_CHUNKS) return EB_COST_BIG;
     const uint64_t pairs = self_mode ? (uint64_t)rows->n * (rows->n - 1) / 2 : (uint64_t)rows->n * cols->n;
     return pairs >= (48ull << 20) ? EB_COST_BLOCKED : EB_COST;
-}
-// BLOCKED EPILOGUE ORDER (epilogue.hip): the early break's epilogue walks the pairs in blocks of 1 024 rows x 256 columns, each
-// block on one XCD, whose L2 then holds the block's 256 column slices while its rows pass -- instead of the launch's flat order
-// (a row after the other, all its columns), in which a slice's next reader comes a whole row later and every completion is a
-// gather from the Infinity Cache or, once the slices of one length outgrow it (cfg 3: 717 MB), from HBM.  Pays where many
-// pairs stay in the running and the launch is large: at 4.9 % alive n = 12 000 / 16 000 / 24 000 / 60 000 / 100 000:
-// 10.3 -> 9.9, 18.3 -> 17.2, 41.0 -> 38.0, 266 -> 234, 827 -> 642 ms; at 1.4 % alive (2 048 bins) +1 %: not taken.
-bool eb_blocked_order(const skl_ctx *ctx, const skl_sketches *rows, const EbPlan *plan, uint64_t pairs)
-{
-    if (ctx->knobs.eb_blocked >= 0) return ctx->knobs.eb_blocked != 0;   // (A/B build: forced)
-    return plan != nullptr && plan->alive_share >= 0.03 && pairs >= (48ull << 20) && rows->ss64 <= (size_t)KSLICE_MAX_U16_CHUNKS;
 }
 
 constexpr uint32_t EB_BLOCKS_MAX = 64;      // blocks per side
@@ -1249,389 +1191,301 @@ extern "C" int skl_ctx_early_break_blocks(skl_ctx *ctx, uint32_t *blk_rows, uint
     return SKL_OK;
 }
 
-// Core of every dense call: rows [r0, r1) of the pair space into `dst` (device).
-// elem_bytes is the output record size per pair.
+static_assert(PLAN_MODE_COUNTS == MODE_COUNTS && PLAN_MODE_JACCARD == MODE_JACCARD && PLAN_MODE_COREACC == MODE_COREACC &&
+              PLAN_MAX_U16_CHUNKS == (uint32_t)KSLICE_MAX_U16_CHUNKS, "dense_plan.hpp restates these constants of kernels.h");
+
+// Which counts buffer a band's launch uses, and whether its epilogue runs on the second stream beside the next band's counts kernel.
+struct BandSlot {
+    int buf = 0;
+    bool overlapped = false;
+};
+
+// rows [r0, r1) of the call into `out`
+static void set_rows(PairArgs *g, const DenseCall &c, uint64_t r0, uint64_t r1, void *out)
+{
+    g->row_begin = (uint32_t)r0;
+    g->row_end = (uint32_t)r1;
+    g->self_mode = c.self_mode ? 1 : 0;
+    g->out_base = c.out_base(r0);
+    g->out = out;
+}
+
+// PLANE 1 of the counts scratch, which the tail slices ADD into: all zero on entry, re-zeroed by the epilogue.  The context
+// remembers the one (pointer, bytes) it knows to be zero.  Before the pair launch: zero `plane1` unless it is that one (null: this
+// launch writes the scratch in another layout), and mark it dirty -- it holds partial counts from the pair launch on ...
+static int plane1_before_launch(skl_ctx *ctx, void *plane1, size_t bytes)
+{
+    if (plane1 && (ctx->clean_plane1 != plane1 || ctx->clean_plane1_bytes != bytes)) HIP_TRY(hipMemsetAsync(plane1, 0, bytes, ctx->stream));
+    ctx->clean_plane1 = nullptr;
+    return SKL_OK;
+}
+// ... and is "clean" again only once the epilogue that re-zeroes it is enqueued.  Any early return in between leaves it marked dirty.
+static void plane1_after_epilogue(skl_ctx *ctx, void *plane1, size_t bytes)
+{
+    ctx->clean_plane1 = plane1;
+    ctx->clean_plane1_bytes = bytes;
+}
+
+// The epilogue fields both counts forms set: where launch `g` left its counts, which pairs they are, where the output goes.
+static void fill_epilogue(EpilogueArgs *e, const skl_sketches *rows, const skl_sketches *cols, const skl_dist_params *p, const PairArgs &g,
+                          const CountsLaunch &L, void *dst)
+{
+    memset(e, 0, sizeof *e);
+    e->counts = (uint32_t *)g.out;
+    e->pair_stride = g.cnt_pair_stride;
+    e->k_stride = g.cnt_k_stride;
+    e->n_pairs = L.pairs;
+    e->nk = L.lengths;
+    e->ss64 = (uint32_t)rows->ss64;
+    e->n_slices = L.two_planes ? 2u : L.k_slices;
+    e->rezero_plane1 = L.tail ? 1u : 0u;
+    e->nA_rows = (uint32_t)rows->n;
+    e->nB_cols = (uint32_t)cols->n;
+    e->row_begin = g.row_begin;
+    e->self_mode = g.self_mode;
+    e->n_total = (uint32_t)cols->n;
+    e->out_base = g.out_base;
+    e->has_comp = g.has_comp;
+    e->log_variant = g.log_variant;
+    e->compA = rows->d_comp;
+    e->compB = cols->d_comp;
+    e->cutoff = p->completeness_cutoff;
+    e->out = (float *)dst;
+}
+
+// Core/accessory, unfused: counts -> scratch -> epilogue kernel.
+static int run_counts_epilogue(skl_ctx *ctx, const skl_sketches *rows, const skl_sketches *cols, const skl_dist_params *p, const DenseCall &c,
+                               const EbPlan *plan, const CountsLaunch &L, uint64_t r0, uint64_t r1, BandSlot slot, void *dst_dev)
+{
+    // (a stream of its own: the banded host output copies band i back on aux_stream while band i + 1 is computed, and must not
+    // queue behind that band's epilogues)
+    if (slot.overlapped && !ctx->epi_stream) HIP_TRY(hipStreamCreateWithFlags(&ctx->epi_stream, hipStreamNonBlocking));
+    hipStream_t epi_stream = slot.overlapped ? ctx->epi_stream : ctx->stream;
+    PairArgs g;
+    SKL_TRY(fill_args(rows, cols, p, MODE_COUNTS, 0, &g));
+    if (L.early) {
+        g.k_count = L.lengths;
+        g.cnt_pair_stride = L.lengths;
+    }
+    if (L.mixed) {
+        g.xcd_interleave = 1;
+        g.block_ke = plan->d_block_ke;
+        g.blk_shift_r = plan->shift_r;
+        g.blk_shift_c = plan->shift_c;
+        g.blk_cols = plan->blk_cols;
+    }
+    void *counts = nullptr;
+    SKL_TRY(ctx_scratch(ctx, L.plane_bytes * L.planes, &counts, slot.overlapped && slot.buf ? 15 : 1));
+    g.cnt_u16 = L.cnt_u16 ? 1u : 0u;
+    if (L.sliced) {   // k-major scratch: coalesced stores from the (tile, k[, chunk slice]) workgroups
+        g.cnt_pair_stride = 1;
+        g.cnt_k_stride = L.pairs;
+        g.k_sliced = 1;
+        g.k_slices = L.k_slices;
+        g.tail_slices = L.tail_slices;
+        g.slice_chunks = L.slice_chunks;
+        g.mid_band = L.mid_band ? 1u : 0u;
+    }
+    set_rows(&g, c, r0, r1, counts);
+    SKL_TRY(ensure_ytab(rows));   // (before the pair launch: nothing may fail between it and the epilogue)
+    // FUSED EPILOGUE (round 5): a plain k-sliced launch -- one workgroup per (tile, k-mer length), no chunk slices -- finishes
+    // its pairs itself: the workgroup that completes a tile's k-mer lengths reads the tile's counts back and stores (core, acc)
+    // (pair_kslice.hip, FUSE).  The second launch (10 us at cfg 2, 6 of them the cost of any dependent launch) is gone.
+    bool fused = false;
+#ifdef SKL_AB
+    // (A/B build only, SKL_FUSE_EPILOGUE=1: measured SLOWER than the second launch at cfg 2 -- 0.154 against 0.145 ms per step:
+    // the arrival pattern itself is free, but with the k-major dispatch order every tile completes in the launch's last round
+    // and one workgroup then does a whole tile's regressions alone while the chip empties; profiles/r05_fused_epilogue.md)
+    if (L.fuse_epilogue && rows->nk <= (size_t)MAX_FUSED_K && kslice_supported(g, MODE_COUNTS, true)) {
+        // arrival counters, one per tile of the launch (16-row tiles at most), counted modulo nk: zero once per (buffer, nk)
+        const size_t tiles_max = ((r1 - r0 + 15) / 16 + 1) * ((cols->n + 127) / 128 + 1) + 64;
+        void *fc = nullptr;
+        const size_t had = ctx->scratch_bytes[11];
+        SKL_TRY(ctx_scratch(ctx, tiles_max * sizeof(uint32_t), &fc, 11));
+        if (ctx->scratch_bytes[11] != had || ctx->fuse_counter_k != rows->nk) {
+            HIP_TRY(hipMemsetAsync(fc, 0, ctx->scratch_bytes[11], ctx->stream));
+            ctx->fuse_counter_k = rows->nk;
+        }
+        g.fuse_counter = (uint32_t *)fc;
+        g.fuse_variant = (uint32_t)env_int("SKL_FUSE_VARIANT", 0);
+        g.fuse_out = (float *)dst_dev;
+        g.ytab = rows->d_ytab;
+        for (size_t t = 0; t < rows->nk; ++t) g.kf[t] = (double)rows->kmers[t];
+        g.cutoff = p->completeness_cutoff;
+        fused = true;
+    }
+#endif
+    void *const plane1 = L.two_planes ? (char *)counts + L.plane_bytes : nullptr;
+    SKL_TRY(plane1_before_launch(ctx, plane1, L.plane_bytes));
+    SKL_TRY(timed_pair_launch(ctx, g, MODE_COUNTS));
+    if (fused) {
+        ctx->last_kernel += " + fused core/accessory epilogue (last workgroup of a tile)";
+        return SKL_OK;
+    }
+    EpilogueArgs e;
+    fill_epilogue(&e, rows, cols, p, g, L, dst_dev);
+    e.nk_total = (uint32_t)rows->nk;
+    if (L.early) {
+        e.rows_ref = rows->d_rows;
+        e.cols_ref = cols->d_rows;
+        e.alive_count = ctx->eb_counter;
+        ctx->eb_pairs += L.pairs;
+        if (L.mixed) {
+            e.block_ke = plan->d_block_ke;
+            e.blk_shift_r = plan->shift_r;
+            e.blk_shift_c = plan->shift_c;
+            e.blk_cols = plan->blk_cols;
+            ctx->last_kernel += " + early break: block by block (" + std::to_string(plan->blk_rows) + " x " + std::to_string(plan->blk_cols) + " blocks of sample ids), the pairs still in the running completed by the epilogue";
+        } else {
+            ctx->last_kernel += " + early break: " + std::to_string(L.lengths) + " of " + std::to_string(rows->nk) + " k-mer lengths counted, the pairs still in the running completed by the epilogue";
+        }
+    }
+    e.min_alive = rows->min_alive;
+    e.cnt_u16 = g.cnt_u16;
+    e.row_end = (uint32_t)r1;
+    e.xcd_shift = ctx_xcd_shift(ctx);
+    e.blocked = L.blocked ? 1u : 0u;
+    e.blk_row_shift = (uint32_t)ctx->knobs.eb_blk_row_shift;
+    if (e.blocked) ctx->last_kernel += " (epilogue in blocks of 1 024 x 256 pairs per XCD)";
+    e.ahead = L.ahead ? 1u : 0u;
+    e.lean = L.lean ? 1u : 0u;
+    e.comp_lean = L.comp_lean ? 1u : 0u;
+    e.lds_rows = L.lds_rows ? 1u : 0u;
+    e.ytab = rows->d_ytab;
+    e.tolerance = g.tolerance;
+    e.kf = rows->d_kf;
+    if (slot.overlapped) {   // this band's epilogue on the second stream, behind its counts kernel
+        HIP_TRY(hipEventRecord(ctx->eb_events[slot.buf], ctx->stream));
+        HIP_TRY(hipStreamWaitEvent(epi_stream, ctx->eb_events[slot.buf], 0));
+    }
+#ifdef SKL_AB
+    if (L.epilogue_r5) {
+        if (!L.early) e.nk_total = 0;
+        HIP_TRY(launch_coreacc_epilogue(e, epi_stream));   // round 5's epilogue: alive pairs completed where they are found (A/B timing)
+    } else
+#endif
+    {
+        if (coreacc_epilogue_is_lean(e)) ctx->last_kernel += e.cnt_u16 ? " [lean epilogue]" : " [lean epilogue, sliced counts]";
+        HIP_TRY(launch_coreacc_epilogue_r6(e, epi_stream));
+    }
+    if (slot.overlapped) HIP_TRY(hipEventRecord(ctx->eb_events[2 + slot.buf], epi_stream));
+    if (plane1) plane1_after_epilogue(ctx, plane1, L.plane_bytes);
+    return SKL_OK;
+}
+
+// Single k, smaller than the chip: bin-match counts in tail slices per tile + an epilogue launch that turns the summed counts
+// into the f32 output (dense_plan.hpp tail_slicing).
+static int run_single_k_tail(skl_ctx *ctx, const skl_sketches *rows, const skl_sketches *cols, const skl_dist_params *p, const DenseCall &c,
+                             const CountsLaunch &L, int jout, uint64_t r0, uint64_t r1, void *dst_dev)
+{
+    PairArgs g;
+    SKL_TRY(fill_args(rows, cols, p, MODE_JACCARD, jout, &g));
+    void *counts = nullptr;
+    SKL_TRY(ctx_scratch(ctx, L.plane_bytes * L.planes, &counts, 1));
+    g.cnt_pair_stride = 1;
+    g.cnt_k_stride = L.pairs;
+    g.k_sliced = 1;
+    g.k_slices = 1;
+    g.tail_slices = L.tail_slices;
+    g.slice_chunks = L.slice_chunks;
+    set_rows(&g, c, r0, r1, counts);
+    void *const plane1 = (char *)counts + L.plane_bytes;
+    SKL_TRY(plane1_before_launch(ctx, plane1, L.plane_bytes));
+    SKL_TRY(timed_pair_launch(ctx, g, MODE_COUNTS));
+    EpilogueArgs e;
+    fill_epilogue(&e, rows, cols, p, g, L, dst_dev);
+    e.jaccard_out = 1;
+    e.jout = jout;
+    e.kf0 = g.kf[0];
+    e.dtab = g.dtab;
+    HIP_TRY(launch_coreacc_epilogue(e, ctx->stream));
+    plane1_after_epilogue(ctx, plane1, L.plane_bytes);
+    return SKL_OK;
+}
+
+// One launch of the mode's own kernel: fused all-k core/accessory, single k, bin-match counts.
+static int run_direct(skl_ctx *ctx, const skl_sketches *rows, const skl_sketches *cols, const skl_dist_params *p, const DenseCall &c, int jout,
+                      uint64_t r0, uint64_t r1, void *dst_dev)
+{
+    PairArgs g;
+    SKL_TRY(fill_args(rows, cols, p, c.mode, jout, &g));
+    set_rows(&g, c, r0, r1, dst_dev);
+    return timed_pair_launch(ctx, g, c.mode);
+}
+
+static const char *dense_range_name(int mode)
+{
+    return mode == MODE_COREACC ? "skl:dense_band core/accessory" : mode == MODE_JACCARD ? "skl:dense_band single k" : "skl:dense_band bin-match counts";
+}
+
+// Core of every dense call: rows [r0, r1) of the pair space into `dst` (device).  HOW it is launched -- the form, the
+// counts' width, slices and planes, the epilogue's order, the row bands -- is decided in dense_plan.hpp; here the decision's
+// input is gathered and its answer executed, band by band.
 int dense_band(skl_ctx *ctx, const skl_sketches *rows, const skl_sketches *cols,
                       const skl_dist_params *p, int mode, int jout, int self_mode, uint64_t r0,
                       uint64_t r1, void *dst_dev)
 {
-    const uint64_t n_cols = cols->n;
-    const uint64_t base = self_mode ? cond_index(r0, r0 + 1, n_cols) : r0 * n_cols;
-    const uint64_t pairs = self_mode ? self_rows_pairs(r0, r1, n_cols) : (r1 - r0) * n_cols;
-    if (pairs == 0) return SKL_OK;
-    const RoctxRange range_(mode == MODE_COREACC ? "skl:dense_band core/accessory" : mode == MODE_JACCARD ? "skl:dense_band single k" : "skl:dense_band bin-match counts");
-
-    const bool coreacc = mode == MODE_COREACC;
-    // Small core/acc launches run as (tile, k) workgroups producing counts + the epilogue
-    // kernel (pair_kslice.hip): 5x the workgroups of the fused kernel and two columns per lane.
+    DenseCall c;
+    c.mode = mode;
+    c.self_mode = self_mode != 0;
+    c.n_cols = cols->n;
+    c.r0 = r0;
+    c.r1 = r1;
+    if (c.pairs(r0, r1) == 0) return SKL_OK;
+    const RoctxRange range_(dense_range_name(mode));
+    c.nk = (uint32_t)rows->nk;
+    c.ss64 = (uint32_t)rows->ss64;
+    c.has_comp = rows->d_comp && cols->d_comp;
+    c.comp_unit = rows->comp_unit && cols->comp_unit;
+    c.n_cu = ctx->n_cu;
+    c.forced_kernel = forced_kernel(ctx);
+    c.fused_coreacc_ok = fused_coreacc_ok(rows);
+    c.knobs = ctx->knobs;
     const EbPlan *plan = nullptr;
-    if (coreacc && (forced_kernel(ctx) == 0 || forced_kernel(ctx) == 4)) {
+    if (mode == MODE_COREACC && (c.forced_kernel == 0 || c.forced_kernel == 4)) {
         SKL_TRY(early_break_plan(ctx, rows, cols, self_mode, p ? p->completeness_cutoff : 0.0, &plan));
         ctx->eb_last_plan = plan;
     }
-    const bool eb_mixed = plan != nullptr && plan->mixed;               // the early break decided block by block
-    const int eb_lengths = plan != nullptr && !eb_mixed ? plan->lengths : 0;
-    const bool early = eb_lengths > 0 || eb_mixed;
-    // (with the early break every launch takes the counts + epilogue form, whatever its size: three of the k-mer lengths,
-    // 12 bytes of counts per pair through HBM -- nothing beside the two lengths not walked)
-    const bool sliced = coreacc && (coreacc_runs_sliced(ctx, rows, pairs) || early);
-    if (coreacc && (sliced || !fused_coreacc_ok(rows))) {
-        // unfused: counts -> scratch2 -> epilogue kernel
-        // (the counts scratch is bounded: a band whose counts would not fit COUNTS_SCRATCH_MAX is computed in two halves
-        // of equal pair count, each into its slice of the destination -- only sketches beyond 65 535 bins or more than 6
-        // k-mer lengths come here with that many pairs)
-        const size_t nkw = eb_lengths > 0 ? (size_t)eb_lengths : rows->nk;   // k-mer lengths the pair kernel counts (block by block: planes)
-        // U16 COUNTS (round 6): sketches of up to 1 023 chunks count at most 65 472 bins per length, so a launch without
-        // chunk slices (no plane to add into) parks its counts as u16: half the scratch traffic of the stream
-        const bool tiny = pairs * nkw < 2ull * 4ull * (uint64_t)ctx->n_cu * 2048ull;   // (launches that may be tail-sliced keep u32: slices ADD into a plane)
-        const bool cnt_u16 = sliced && rows->ss64 <= (size_t)KSLICE_MAX_U16_CHUNKS && !tiny && ctx->knobs.k_slices <= 1 && ctx->knobs.counts_u16 &&
-                             !ctx->knobs.fuse_epilogue && !ctx->knobs.epilogue_r5;   // (the A/B build's older epilogues read u32)
-        const size_t cnt_bytes = cnt_u16 ? sizeof(uint16_t) : sizeof(uint32_t);
-        // BAND PIPELINE (round 6).  The counts scratch is bounded, and a call whose counts do not fit is computed in row bands of
-        // equal pair count.  From 64 Mi pairs on the bands are also what hides the epilogue: band i's epilogue (+ completion
-        // of the pairs still in the running) is memory-bound, band i + 1's counts kernel is bound by the vector ALUs, so they
-        // run side by side -- counts kernels on the context's stream, epilogues on its second stream, two counts buffers.
-        // (the side-by-side run costs the counts kernel about what it hides of the epilogue -- an epilogue wave displaces a wave of the
-        // counts kernel, which fills the register file by itself -- and pays only where the epilogue is heavy: from ~3 % of the
-        // pairs still in the running.  n = 16 000 at 4.9 %: 18.5 against 19.4 ms; cfg 3 at 1.1 %: 782 against 748 ms.)
-        // Since the blocked epilogue order (eb_blocked_order) covers that regime better -- n = 16 000: 17.2 ms blocked, 18.3-18.8
-        // piped; cfg 3 at two lengths: 642 blocked, 775 piped -- the pipeline was off unless asked for (A/B build,
-        // SKL_EB_PIPELINE=1; tests/test_gpu_early_break_r6.py keeps it exact).
-        const bool blocked = early && eb_blocked_order(ctx, rows, plan, pairs);
-        // ROUND 6, LATE: with the lean epilogue (58 VGPRs, 8 waves per SIMD, a third of the instructions) the side-by-side run pays
-        // where it did not: 300 000 x 10 000 at 1.4 % still in the running 161.6 -> 154.0 ms, n = 30 000 at 2 048 bins 23.9 -> 23.2
-        // (profiles/r06_epilogue_lean.md) -- on by itself wherever that kernel runs in the flat order.
-        if (early) SKL_TRY(ensure_ytab(rows));   // (min_alive)
-        const bool lean_like = !eb_mixed && (!(rows->d_comp && cols->d_comp) || (rows->comp_unit && cols->comp_unit)) && rows->min_alive != 0xFFFFFFFFu && nkw >= 2 && nkw <= 4;
-        // (together with the blocked order it pays for the largest calls only: cfg 3 586 -> 575 ms, n = 40 000 95.4 -> 94.7, but
-        // n = 16 000 in 4 bands 15.5 -> 18.0: from 2^30 pairs)
-        bool piping = false;
-        if (early) {
-            const int pk = ctx->knobs.eb_pipeline;
-            if (pk == 1) piping = !blocked && (eb_mixed || (plan != nullptr && plan->alive_share >= 0.03) || ctx->knobs.early_break >= 2);
-            else if (pk == 2) piping = lean_like;
-            else if (pk == -1) piping = lean_like && (!blocked || pairs >= (1ull << 30));
-        }
-        if (!ctx->eb_in_pipeline && r1 - r0 > 1 &&
-            (pairs * nkw * cnt_bytes > COUNTS_SCRATCH_MAX || (piping && pairs >= (uint64_t)ctx->knobs.eb_pipeline_min))) {
-            const uint64_t fit = std::max<uint64_t>(1, COUNTS_SCRATCH_MAX / (nkw * cnt_bytes));
-            const uint64_t want = piping ? std::max<uint64_t>((uint64_t)ctx->knobs.eb_pipeline_min / 2, pairs / 8) : fit;
-            const uint64_t n_bands = (pairs + std::min(fit, want) - 1) / std::min(fit, want);
-            std::vector<uint64_t> cuts(1, r0);
-            for (uint64_t b = 1; b < n_bands; ++b) {
-                const uint64_t target = pairs * b / n_bands;   // pairs before the cut
-                uint64_t cut;
-                if (self_mode) {   // the first row whose predecessors hold at least `target` pairs
-                    uint64_t lo = cuts.back() + 1, hi = r1 - 1;
-                    while (lo < hi) {
-                        const uint64_t m = (lo + hi) / 2;
-                        if (self_rows_pairs(r0, m, n_cols) < target) lo = m + 1; else hi = m;
-                    }
-                    cut = lo;
-                } else {
-                    cut = r0 + (target + n_cols - 1) / n_cols;
-                }
-                cut = std::min<uint64_t>(std::max<uint64_t>(cut, cuts.back() + 1), r1 - 1);
-                if (cut > cuts.back()) cuts.push_back(cut);
-            }
-            cuts.push_back(r1);
-            const bool overlap = piping && cuts.size() > 2;
-            if (overlap && !ctx->eb_events[0]) {
-                for (auto &ev : ctx->eb_events) HIP_TRY(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-            }
-            ctx->eb_in_pipeline = true;
-            int rc = SKL_OK;
-            for (size_t b = 0; b + 1 < cuts.size() && rc == SKL_OK; ++b) {
-                const int buf = (int)(b & 1);
-                ctx->eb_pipe_buf = overlap ? buf : 0;
-                ctx->eb_pipe_overlap = overlap;
-                // (the epilogue that read this counts buffer two bands ago must be done before the counts kernel rewrites it)
-                if (overlap && b >= 2) {
-                    const hipError_t e = hipStreamWaitEvent(ctx->stream, ctx->eb_events[2 + buf], 0);
-                    if (e != hipSuccess) rc = fail(SKL_ERR_HIP, "hipStreamWaitEvent: %s", hipGetErrorString(e));
-                }
-                const uint64_t base_b = self_mode ? cond_index(cuts[b], cuts[b] + 1, n_cols) : cuts[b] * n_cols;
-                if (rc == SKL_OK) rc = dense_band(ctx, rows, cols, p, mode, jout, self_mode, cuts[b], cuts[b + 1], (char *)dst_dev + (base_b - base) * 2 * sizeof(float));
-            }
-            ctx->eb_in_pipeline = false;
-            ctx->eb_pipe_overlap = false;
-            ctx->eb_pipe_buf = 0;
-            if (overlap) {   // the output belongs to the context's stream again
-                for (int buf = 0; buf < 2; ++buf) {
-                    const hipError_t e = hipStreamWaitEvent(ctx->stream, ctx->eb_events[2 + buf], 0);
-                    if (e != hipSuccess && rc == SKL_OK) rc = fail(SKL_ERR_HIP, "hipStreamWaitEvent: %s", hipGetErrorString(e));
-                }
-                if (rc == SKL_OK) ctx->last_kernel += "; " + std::to_string(cuts.size() - 1) + " row bands, each band's epilogue beside the next band's counts kernel";
-            }
-            return rc;
-        }
-        const bool piped = ctx->eb_in_pipeline && ctx->eb_pipe_overlap;
-        // (a stream of its own: the banded host output copies band i back on aux_stream while band i + 1 is computed, and must not
-        // queue behind that band's epilogues)
-        if (piped && !ctx->epi_stream) HIP_TRY(hipStreamCreateWithFlags(&ctx->epi_stream, hipStreamNonBlocking));
-        hipStream_t epi_stream = piped ? ctx->epi_stream : ctx->stream;
-        PairArgs g;
-        SKL_TRY(fill_args(rows, cols, p, MODE_COUNTS, 0, &g));
-        if (early) {
-            g.k_count = (uint32_t)nkw;
-            g.cnt_pair_stride = nkw;
-        }
-        if (eb_mixed) {
-            g.xcd_interleave = 1;
-            g.block_ke = plan->d_block_ke;
-            g.blk_shift_r = plan->shift_r;
-            g.blk_shift_c = plan->shift_c;
-            g.blk_cols = plan->blk_cols;
-        }
-        void *counts = nullptr;
-        const uint32_t k_slices = sliced ? choose_k_slices(ctx, rows->ss64) : 1u;
-        // A launch with fewer (tile, k) units than resident workgroup slots cannot fill the chip with one
-        // workgroup per unit: most SIMDs hold 0-2 waves and the launch takes the time of ONE unit at a
-        // lone wave's issue rate whatever its size (0.055-0.064 ms from 100 to 500 genomes).  Such launches are
-        // cut into tail_slices chunk slices per unit -- and so is the last, partial round of any launch
-        // SKL_TAIL_MAX_PCT lets through (default 90: launches of up to 0.9 estimated rounds, where the
-        // whole launch is that partial round; the partial round of a longer launch gains nothing,
-        // profiles/r02_ab_tail_slices.jsonl).  Slice 0 of a unit stores, the others add into a second
-        // plane that is zero on entry and re-zeroed by the epilogue.
-        const uint64_t est_units = pairs * nkw / 2048;
-        const uint64_t slots = 4ull * (uint64_t)ctx->n_cu;
-        // (launches of less than 1/16 round -- ~200 genomes -- are cut twice as fine when the sketch allows it)
-        // (round 4: any sketch size is cut -- slices of whole stages, the last one shorter, slice_plan() -- e.g. the 157
-        // chunks of `-s 10000`; and launches over sketches beyond 65 535 bins slice their last round however many rounds
-        // they have: a unit of 1 563+ chunks dwarfs the fixed cost of a workgroup)
-        const bool big_sketch = rows->ss64 > (size_t)KSLICE_MAX_U16_CHUNKS;
-        const uint32_t tail_wanted = ctx->knobs.tail_slices == 4 && est_units * 16 <= slots && rows->ss64 >= 64 ? 8u : (uint32_t)ctx->knobs.tail_slices;
-        uint32_t tail_chunks = 0;
-        const uint32_t tail_slices = slice_plan((uint32_t)rows->ss64, tail_wanted, &tail_chunks);
-        bool tail = sliced && k_slices == 1u && tail_slices > 1u && forced_kernel(ctx) == 0 &&
-                    ((big_sketch && est_units <= 16 * slots) || est_units * 100 <= (uint64_t)std::max(0ll, ctx->knobs.tail_max_pct) * slots);
-        // MID BAND (round 3): from half the 32-row threshold up to it (4-8 Mi pair x k evaluations: 1 300-1 790 genomes at
-        // 5 k-mer lengths) the launch is a handful of rounds of workgroups whichever tile it takes, and its last, partial
-        // round decides: 32 x 128 tiles with THAT round cut into 2 chunk slices are 0.7-4.6 % ahead of 16 x 128 tiles
-        // there (profiles/r03_ab_mid_sizes.jsonl, r03_ab_mid_band.jsonl); plain 32-row tiles are not (+-4 %).  Above the
-        // band plain 32-row tiles, below it 16-row tiles (cfg 2: 0.156 against 0.162 ms).
-        const uint64_t evals = pairs * nkw;
-        const long long t32 = ctx->knobs.tile32_min;
-        const bool mid_band = ctx->knobs.mid_band && !tail && sliced && k_slices == 1u && t32 > 0 && tail_slices > 1u &&
-                              forced_kernel(ctx) == 0 && rows->ss64 >= 16 && evals * 2 >= (uint64_t)t32 && evals < (uint64_t)t32;
-        uint32_t tail_slices_eff = tail_slices, tail_chunks_eff = tail_chunks;
-        if (mid_band) {
-            tail = true;
-            tail_slices_eff = slice_plan((uint32_t)rows->ss64, 2u, &tail_chunks_eff);
-        }
-        const bool two_planes = tail;
-        const bool u16_now = cnt_u16 && !tail && k_slices == 1u;
-        const size_t plane_bytes = pairs * nkw * (u16_now ? sizeof(uint16_t) : sizeof(uint32_t));
-        SKL_TRY(ctx_scratch(ctx, plane_bytes * std::max(two_planes ? 2u : 1u, k_slices), &counts, piped && ctx->eb_pipe_buf ? 15 : 1));
-        g.cnt_u16 = u16_now ? 1u : 0u;
-        if (sliced) {   // k-major scratch: coalesced stores from the (tile, k[, chunk slice]) workgroups
-            g.cnt_pair_stride = 1;
-            g.cnt_k_stride = pairs;
-            g.k_sliced = 1;
-            g.k_slices = k_slices;
-            g.tail_slices = tail ? tail_slices_eff : 0u;
-            if (tail) g.slice_chunks = tail_chunks_eff;
-            else if (k_slices > 1u) (void)slice_plan((uint32_t)rows->ss64, std::min(8u, (uint32_t)ctx->knobs.k_slices), &g.slice_chunks);
-            g.mid_band = mid_band ? 1u : 0u;
-        }
-        if (two_planes) {
-            void *plane1 = (char *)counts + plane_bytes;
-            if (ctx->clean_plane1 != plane1 || ctx->clean_plane1_bytes != plane_bytes) {
-                HIP_TRY(hipMemsetAsync(plane1, 0, plane_bytes, ctx->stream));
-                ctx->clean_plane1 = plane1;
-                ctx->clean_plane1_bytes = plane_bytes;
-            }
-        } else {
-            ctx->clean_plane1 = nullptr;   // this launch writes the scratch in another layout
-        }
-        g.row_begin = (uint32_t)r0;
-        g.row_end = (uint32_t)r1;
-        g.self_mode = self_mode;
-        g.out_base = base;
-        g.out = counts;
-        SKL_TRY(ensure_ytab(rows));   // (before the pair launch: nothing may fail between it and the epilogue)
-        // FUSED EPILOGUE (round 5): a plain k-sliced launch -- one workgroup per (tile, k-mer length), no chunk slices -- finishes
-        // its pairs itself: the workgroup that completes a tile's k-mer lengths reads the tile's counts back and stores (core, acc)
-        // (pair_kslice.hip, FUSE).  The second launch (10 us at cfg 2, 6 of them the cost of any dependent launch) is gone.
-        bool fused = false;
-#ifdef SKL_AB
-        // (A/B build only, SKL_FUSE_EPILOGUE=1: measured SLOWER than the second launch at cfg 2 -- 0.154 against 0.145 ms per step:
-        // the arrival pattern itself is free, but with the k-major dispatch order every tile completes in the launch's last round
-        // and one workgroup then does a whole tile's regressions alone while the chip empties; profiles/r05_fused_epilogue.md)
-        if (sliced && !early && k_slices == 1u && !two_planes && ctx->knobs.fuse_epilogue && forced_kernel(ctx) == 0 &&
-            rows->nk <= (size_t)MAX_FUSED_K && kslice_supported(g, MODE_COUNTS, true) && rows->ss64 <= (size_t)KSLICE_MAX_U16_CHUNKS) {
-            // arrival counters, one per tile of the launch (16-row tiles at most), counted modulo nk: zero once per (buffer, nk)
-            const size_t tiles_max = ((r1 - r0 + 15) / 16 + 1) * ((cols->n + 127) / 128 + 1) + 64;
-            void *fc = nullptr;
-            const size_t had = ctx->scratch_bytes[11];
-            SKL_TRY(ctx_scratch(ctx, tiles_max * sizeof(uint32_t), &fc, 11));
-            if (ctx->scratch_bytes[11] != had || ctx->fuse_counter_k != rows->nk) {
-                HIP_TRY(hipMemsetAsync(fc, 0, ctx->scratch_bytes[11], ctx->stream));
-                ctx->fuse_counter_k = rows->nk;
-            }
-            g.fuse_counter = (uint32_t *)fc;
-            g.fuse_variant = (uint32_t)env_int("SKL_FUSE_VARIANT", 0);
-            g.fuse_out = (float *)dst_dev;
-            g.ytab = rows->d_ytab;
-            for (size_t t = 0; t < rows->nk; ++t) g.kf[t] = (double)rows->kmers[t];
-            g.cutoff = p->completeness_cutoff;
-            fused = true;
-        }
-#endif
-        // Plane 1 holds partial counts from the pair launch until the epilogue has re-zeroed it: it is
-        // "clean" again only once that epilogue is enqueued.  Any early return in between leaves it marked dirty.
-        const void *const plane1_clean = ctx->clean_plane1;
-        ctx->clean_plane1 = nullptr;
-        SKL_TRY(timed_pair_launch(ctx, g, MODE_COUNTS));
-        if (fused) {
-            ctx->last_kernel += " + fused core/accessory epilogue (last workgroup of a tile)";
-            return SKL_OK;
-        }
-        EpilogueArgs e;
-        memset(&e, 0, sizeof e);
-        e.counts = (uint32_t *)counts;
-        e.pair_stride = g.cnt_pair_stride;
-        e.k_stride = g.cnt_k_stride;
-        e.n_pairs = pairs;
-        e.nk = (uint32_t)nkw;
-        e.nk_total = (uint32_t)rows->nk;
-        if (early) {
-            e.rows_ref = rows->d_rows;
-            e.cols_ref = cols->d_rows;
-            e.alive_count = ctx->eb_counter;
-            ctx->eb_pairs += pairs;
-            if (eb_mixed) {
-                e.block_ke = plan->d_block_ke;
-                e.blk_shift_r = plan->shift_r;
-                e.blk_shift_c = plan->shift_c;
-                e.blk_cols = plan->blk_cols;
-                ctx->last_kernel += " + early break: block by block (" + std::to_string(plan->blk_rows) + " x " + std::to_string(plan->blk_cols) + " blocks of sample ids), the pairs still in the running completed by the epilogue";
-            } else {
-                ctx->last_kernel += " + early break: " + std::to_string(nkw) + " of " + std::to_string(rows->nk) + " k-mer lengths counted, the pairs still in the running completed by the epilogue";
-            }
-        }
-        e.min_alive = rows->min_alive;
-        e.cnt_u16 = g.cnt_u16;
-        e.row_end = (uint32_t)r1;
-        e.xcd_shift = ctx_xcd_shift(ctx);
-        e.blocked = early && eb_blocked_order(ctx, rows, plan, pairs) ? 1u : 0u;
-        e.blk_row_shift = (uint32_t)ctx->knobs.eb_blk_row_shift;
-        if (e.blocked) ctx->last_kernel += " (epilogue in blocks of 1 024 x 256 pairs per XCD)";
-        // (the workgroup's row slices in LDS pay from ~8 completions per workgroup of 256 pairs on: n = 16 000 at 4 096 bins, 4.9 %
-        // still in the running: 18.0 against 18.7 ms; at 2 048 bins, 1.4 %: 30.8 against 27.3 -- profiles/r06_epilogue_forms.md)
-        e.ahead = ctx->knobs.eb_ahead ? 1u : 0u;
-        e.lean = ctx->knobs.eb_lean ? 1u : 0u;
-        e.comp_lean = rows->d_comp && cols->d_comp && rows->comp_unit && cols->comp_unit ? 1u : 0u;
-        e.lds_rows = ctx->knobs.eb_lds_rows && plan != nullptr && plan->alive_share >= 0.03 ? 1u : 0u;
-        e.ss64 = (uint32_t)rows->ss64;
-        e.n_slices = sliced ? ctx->last_count_planes : 1u;
-        e.rezero_plane1 = sliced && ctx->last_tail ? 1u : 0u;
-        e.nA_rows = (uint32_t)rows->n;
-        e.nB_cols = (uint32_t)cols->n;
-        e.row_begin = (uint32_t)r0;
-        e.self_mode = self_mode;
-        e.n_total = (uint32_t)cols->n;
-        e.out_base = base;
-        e.has_comp = g.has_comp;
-        e.log_variant = g.log_variant;
-        e.ytab = rows->d_ytab;
-        e.compA = rows->d_comp;
-        e.compB = cols->d_comp;
-        e.cutoff = p->completeness_cutoff;
-        e.tolerance = g.tolerance;
-        e.kf = rows->d_kf;
-        e.out = (float *)dst_dev;
-        if (piped) {   // this band's epilogue on the second stream, behind its counts kernel
-            HIP_TRY(hipEventRecord(ctx->eb_events[ctx->eb_pipe_buf], ctx->stream));
-            HIP_TRY(hipStreamWaitEvent(epi_stream, ctx->eb_events[ctx->eb_pipe_buf], 0));
-        }
-#ifdef SKL_AB
-        if (ctx->knobs.epilogue_r5 && !eb_mixed && !(early && (e.has_comp || rows->ss64 > (size_t)KSLICE_MAX_U16_CHUNKS))) {
-            if (!early) e.nk_total = 0;
-            HIP_TRY(launch_coreacc_epilogue(e, epi_stream));   // round 5's epilogue: alive pairs completed where they are found (A/B timing)
-        } else
-#endif
-        {
-            if (coreacc_epilogue_is_lean(e)) ctx->last_kernel += e.cnt_u16 ? " [lean epilogue]" : " [lean epilogue, sliced counts]";
-            HIP_TRY(launch_coreacc_epilogue_r6(e, epi_stream));
-        }
-        if (piped) HIP_TRY(hipEventRecord(ctx->eb_events[2 + ctx->eb_pipe_buf], epi_stream));
-        // (an empty launch, or one another kernel took, leaves plane 1 not known to be zero)
-        if (two_planes && ctx->last_tail) ctx->clean_plane1 = plane1_clean;
-        return SKL_OK;
+    if (plan) {
+        c.eb_plan = true;
+        c.eb_lengths = plan->lengths;
+        c.eb_mixed = plan->mixed;
+        c.eb_alive_share = plan->alive_share;
+        if (plan->mixed || plan->lengths > 0) SKL_TRY(ensure_ytab(rows));   // (min_alive, which the rules read, is set with the table)
     }
-    PairArgs g;
-    SKL_TRY(fill_args(rows, cols, p, mode, jout, &g));
-    g.row_begin = (uint32_t)r0;
-    g.row_end = (uint32_t)r1;
-    g.self_mode = self_mode;
-    g.out_base = base;
-    g.out = dst_dev;
-    if (mode == MODE_JACCARD) {
-        // A single-k launch smaller than the chip has the same problem as a small core/accessory one
-        // (one workgroup per tile on a quarter of the SIMDs, each wave at its own issue interval: 0.058
-        // ms from 200 to 1 000 genomes) and takes the same cure: bin-match counts in tail_slices chunk
-        // slices per tile + an epilogue launch that turns the summed counts into the f32 output.
-        const uint64_t est_units = pairs / 2048;
-        const uint64_t slots = 4ull * (uint64_t)ctx->n_cu;
-        const uint32_t tail_wanted = ctx->knobs.tail_slices == 4 && est_units * 16 <= slots && rows->ss64 >= 64 ? 8u : (uint32_t)ctx->knobs.tail_slices;
-        uint32_t tail_chunks = 0;
-        const uint32_t tail_slices = slice_plan((uint32_t)rows->ss64, tail_wanted, &tail_chunks);
-        const bool tail = tail_slices > 1u && forced_kernel(ctx) == 0 &&
-                          ((rows->ss64 > (size_t)KSLICE_MAX_U16_CHUNKS && est_units <= 16 * slots) ||
-                           est_units * 100 <= (uint64_t)std::max(0ll, ctx->knobs.tail_max_pct) * slots);
-        if (tail) {
-            void *counts = nullptr;
-            const size_t plane_bytes = pairs * sizeof(uint32_t);
-            SKL_TRY(ctx_scratch(ctx, plane_bytes * 2, &counts, 1));
-            void *plane1 = (char *)counts + plane_bytes;
-            if (ctx->clean_plane1 != plane1 || ctx->clean_plane1_bytes != plane_bytes) {
-                HIP_TRY(hipMemsetAsync(plane1, 0, plane_bytes, ctx->stream));
-                ctx->clean_plane1 = plane1;
-                ctx->clean_plane1_bytes = plane_bytes;
-            }
-            g.cnt_pair_stride = 1;
-            g.cnt_k_stride = pairs;
-            g.k_sliced = 1;
-            g.k_slices = 1;
-            g.tail_slices = tail_slices;
-            g.slice_chunks = tail_chunks;
-            g.out = counts;
-            const void *const plane1_clean = ctx->clean_plane1;   // as above: dirty until the epilogue is enqueued
-            ctx->clean_plane1 = nullptr;
-            SKL_TRY(timed_pair_launch(ctx, g, MODE_COUNTS));
-            EpilogueArgs e;
-            memset(&e, 0, sizeof e);
-            e.counts = (uint32_t *)counts;
-            e.pair_stride = 1;
-            e.k_stride = pairs;
-            e.n_pairs = pairs;
-            e.nk = 1;
-            e.ss64 = (uint32_t)rows->ss64;
-            e.n_slices = 2;
-            e.rezero_plane1 = 1;
-            e.nA_rows = (uint32_t)rows->n;
-            e.nB_cols = (uint32_t)cols->n;
-            e.row_begin = (uint32_t)r0;
-            e.self_mode = self_mode;
-            e.n_total = (uint32_t)cols->n;
-            e.out_base = base;
-            e.has_comp = g.has_comp;
-            e.log_variant = g.log_variant;
-            e.compA = rows->d_comp;
-            e.compB = cols->d_comp;
-            e.cutoff = p->completeness_cutoff;
-            e.jaccard_out = 1;
-            e.jout = jout;
-            e.kf0 = g.kf[0];
-            e.dtab = g.dtab;
-            e.out = (float *)dst_dev;
-            HIP_TRY(launch_coreacc_epilogue(e, ctx->stream));
-            if (ctx->last_tail) ctx->clean_plane1 = plane1_clean;
-            return SKL_OK;
-        }
+    c.min_alive = rows->min_alive;
+
+    const RowBands bands = plan_row_bands(c);
+    const size_t n_bands = bands.cuts.size() - 1;
+    if (bands.overlap && !ctx->eb_events[0]) {
+        for (auto &ev : ctx->eb_events) HIP_TRY(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
     }
-    return timed_pair_launch(ctx, g, mode);
+    int rc = SKL_OK;
+    for (size_t b = 0; b < n_bands && rc == SKL_OK; ++b) {
+        std::optional<RoctxRange> band_range_;   // (a banded call: one range per band inside the call's)
+        if (n_bands > 1) band_range_.emplace(dense_range_name(mode));
+        const BandSlot slot = {bands.overlap ? (int)(b & 1) : 0, bands.overlap};
+        // (the epilogue that read this counts buffer two bands ago must be done before the counts kernel rewrites it)
+        if (bands.overlap && b >= 2) {
+            const hipError_t e = hipStreamWaitEvent(ctx->stream, ctx->eb_events[2 + slot.buf], 0);
+            if (e != hipSuccess) rc = fail(SKL_ERR_HIP, "hipStreamWaitEvent: %s", hipGetErrorString(e));
+        }
+        if (rc != SKL_OK) break;
+        const uint64_t b0 = bands.cuts[b], b1 = bands.cuts[b + 1];
+        void *dst = (char *)dst_dev + (c.out_base(b0) - c.out_base(r0)) * 2 * sizeof(float);   // (only core/accessory calls are cut: (core, acc) records)
+        const CountsLaunch L = plan_counts_launch(c, b0, b1);
+        if (L.form == FORM_COUNTS_EPILOGUE) rc = run_counts_epilogue(ctx, rows, cols, p, c, plan, L, b0, b1, slot, dst);
+        else if (L.form == FORM_SINGLE_K_TAIL) rc = run_single_k_tail(ctx, rows, cols, p, c, L, jout, b0, b1, dst);
+        else rc = run_direct(ctx, rows, cols, p, c, jout, b0, b1, dst);
+    }
+    if (bands.overlap) {   // the output belongs to the context's stream again
+        for (int buf = 0; buf < 2; ++buf) {
+            const hipError_t e = hipStreamWaitEvent(ctx->stream, ctx->eb_events[2 + buf], 0);
+            if (e != hipSuccess && rc == SKL_OK) rc = fail(SKL_ERR_HIP, "hipStreamWaitEvent: %s", hipGetErrorString(e));
+        }
+        if (rc == SKL_OK) ctx->last_kernel += "; " + std::to_string(n_bands) + " row bands, each band's epilogue beside the next band's counts kernel";
+    }
+    return rc;
 }
 
 static size_t record_bytes(const skl_sketches *s, int mode)

@@ -9,6 +9,8 @@
 #include <algorithm>
 #include <vector>
 
+#include "dense_plan.hpp"   // slice_plan()
+
 namespace skl {
 
 constexpr int BBITS = 14;          // src/sketch/mod.rs:34
@@ -185,19 +187,6 @@ hipError_t launch_pair_kernel_ksplit(const PairArgs &args, int mode, int rows_pe
 hipError_t launch_pair_kernel_kslice(const PairArgs &args, int mode, int shape, bool k_sliced, int ablate,
                                      TileScratch &scratch, hipStream_t stream);
 bool kslice_supported(const PairArgs &args, int mode, bool k_sliced);
-// A sketch of ss64 chunks cut into at most `wanted` chunk slices of whole stages: *chunks per slice (a multiple of 8, the
-// last slice shorter) -> number of slices that hold something (1: the sketch is too short to cut)
-inline uint32_t slice_plan(uint32_t ss64, uint32_t wanted, uint32_t *chunks)
-{
-    if (wanted < 2u || ss64 < 16u) {
-        *chunks = 0;
-        return 1u;
-    }
-    const uint32_t per = ((ss64 + wanted - 1u) / wanted + 7u) / 8u * 8u;
-    *chunks = per;
-    return (ss64 + per - 1u) / per;
-}
-
 // reference layout -> lane-interleaved layout (B operand); n_pad = 64*ceil(n/64)
 hipError_t launch_relayout(const uint64_t *ref_layout, uint4 *lane_layout, uint32_t n,
                            uint32_t nk, uint32_t ss64, hipStream_t stream);
