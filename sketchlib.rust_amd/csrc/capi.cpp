@@ -88,7 +88,7 @@ int ctx_bind(skl_ctx *ctx)
     return SKL_OK;
 }
 
-int ctx_scratch(skl_ctx *ctx, size_t bytes, void **out, int which)
+int ctx_scratch(skl_ctx *ctx, size_t bytes, void **out, ScratchSlot which)
 {
     void *&buf = ctx->scratch[which];
     size_t &cap = ctx->scratch_bytes[which];
@@ -101,7 +101,7 @@ int ctx_scratch(skl_ctx *ctx, size_t bytes, void **out, int which)
         }
         HIP_TRY(hipMalloc(&buf, bytes));
         cap = bytes;
-        if (which == 1) ctx->clean_plane1 = nullptr;   // a new counts scratch: nothing is known to be zero in it
+        if (which == SCRATCH_COUNTS) ctx->clean_plane1 = nullptr;   // a new counts scratch: nothing is known to be zero in it
     }
     *out = buf;
     return SKL_OK;
@@ -1275,7 +1275,7 @@ static int run_counts_epilogue(skl_ctx *ctx, const skl_sketches *rows, const skl
         g.blk_cols = plan->blk_cols;
     }
     void *counts = nullptr;
-    SKL_TRY(ctx_scratch(ctx, L.plane_bytes * L.planes, &counts, slot.overlapped && slot.buf ? 15 : 1));
+    SKL_TRY(ctx_scratch(ctx, L.plane_bytes * L.planes, &counts, slot.overlapped && slot.buf ? SCRATCH_COUNTS_2 : SCRATCH_COUNTS));
     g.cnt_u16 = L.cnt_u16 ? 1u : 0u;
     if (L.sliced) {   // k-major scratch: coalesced stores from the (tile, k[, chunk slice]) workgroups
         g.cnt_pair_stride = 1;
@@ -1300,10 +1300,10 @@ static int run_counts_epilogue(skl_ctx *ctx, const skl_sketches *rows, const skl
         // arrival counters, one per tile of the launch (16-row tiles at most), counted modulo nk: zero once per (buffer, nk)
         const size_t tiles_max = ((r1 - r0 + 15) / 16 + 1) * ((cols->n + 127) / 128 + 1) + 64;
         void *fc = nullptr;
-        const size_t had = ctx->scratch_bytes[11];
-        SKL_TRY(ctx_scratch(ctx, tiles_max * sizeof(uint32_t), &fc, 11));
-        if (ctx->scratch_bytes[11] != had || ctx->fuse_counter_k != rows->nk) {
-            HIP_TRY(hipMemsetAsync(fc, 0, ctx->scratch_bytes[11], ctx->stream));
+        const size_t had = ctx->scratch_bytes[SCRATCH_FUSE_COUNTERS];
+        SKL_TRY(ctx_scratch(ctx, tiles_max * sizeof(uint32_t), &fc, SCRATCH_FUSE_COUNTERS));
+        if (ctx->scratch_bytes[SCRATCH_FUSE_COUNTERS] != had || ctx->fuse_counter_k != rows->nk) {
+            HIP_TRY(hipMemsetAsync(fc, 0, ctx->scratch_bytes[SCRATCH_FUSE_COUNTERS], ctx->stream));
             ctx->fuse_counter_k = rows->nk;
         }
         g.fuse_counter = (uint32_t *)fc;
@@ -1381,7 +1381,7 @@ static int run_single_k_tail(skl_ctx *ctx, const skl_sketches *rows, const skl_s
     PairArgs g;
     SKL_TRY(fill_args(rows, cols, p, MODE_JACCARD, jout, &g));
     void *counts = nullptr;
-    SKL_TRY(ctx_scratch(ctx, L.plane_bytes * L.planes, &counts, 1));
+    SKL_TRY(ctx_scratch(ctx, L.plane_bytes * L.planes, &counts, SCRATCH_COUNTS));
     g.cnt_pair_stride = 1;
     g.cnt_k_stride = L.pairs;
     g.k_sliced = 1;
@@ -1520,8 +1520,8 @@ static int dense_rows(skl_ctx *ctx, const skl_sketches *rows, const skl_sketches
     void *dev[2] = {nullptr, nullptr};
     const uint64_t all_pairs = self_mode ? self_rows_pairs(r0, r1, n_cols) : (r1 - r0) * n_cols;
     const size_t band_alloc = (size_t)std::min<uint64_t>(BAND_BYTES, all_pairs * rec);
-    SKL_TRY(ctx_scratch(ctx, band_alloc, &dev[0], 0));
-    SKL_TRY(ctx_scratch(ctx, all_pairs * rec > BAND_BYTES ? band_alloc : 16, &dev[1], 3));
+    SKL_TRY(ctx_scratch(ctx, band_alloc, &dev[0], SCRATCH_KEY_BAND));
+    SKL_TRY(ctx_scratch(ctx, all_pairs * rec > BAND_BYTES ? band_alloc : 16, &dev[1], SCRATCH_KEY_BAND_2));
     // A copy into pageable host memory does not return before it is done (the runtime stages it), so the copy of band i is
     // ISSUED after band i + 1's kernels are in the queue: the host blocks in the copy while the device computes.
     struct PendingCopy {
@@ -1555,7 +1555,7 @@ static int dense_rows(skl_ctx *ctx, const skl_sketches *rows, const skl_sketches
                 pending.bytes = 0;
             }
             HIP_TRY(hipStreamSynchronize(ctx->aux_stream));
-            SKL_TRY(ctx_scratch(ctx, pairs * rec, &dev[buf], buf == 0 ? 0 : 3));
+            SKL_TRY(ctx_scratch(ctx, pairs * rec, &dev[buf], buf == 0 ? SCRATCH_KEY_BAND : SCRATCH_KEY_BAND_2));
             band = dev[buf];
         }
         // the copy that read this buffer two bands ago must be done before it is overwritten

@@ -131,10 +131,10 @@ static int sketch_signs_impl(skl_ctx *ctx, const uint8_t *codes, const uint32_t 
     const size_t sign_words = n_samples * nk * num_bins;
     // device buffers of the context: packed codes | signs | the small arrays
     void *d_packed = nullptr, *d_signs = nullptr, *d_small = nullptr;
-    SKL_TRY(ctx_scratch(ctx, std::max<uint64_t>(total_words, 4) * sizeof(uint32_t), &d_packed, 12));
-    SKL_TRY(ctx_scratch(ctx, sign_words * sizeof(uint64_t), &d_signs, 13));
+    SKL_TRY(ctx_scratch(ctx, std::max<uint64_t>(total_words, 4) * sizeof(uint32_t), &d_packed, SCRATCH_SKETCH_BASES));
+    SKL_TRY(ctx_scratch(ctx, sign_words * sizeof(uint64_t), &d_signs, SCRATCH_SKETCH_SIGNS));
     const size_t small_words = 4 * (n_samples + 1) + n_offs + 9 * nk + 8;   // u64 each (the k-mer lengths: two per word)
-    SKL_TRY(ctx_scratch(ctx, small_words * sizeof(uint64_t), &d_small, 14));
+    SKL_TRY(ctx_scratch(ctx, small_words * sizeof(uint64_t), &d_small, SCRATCH_SKETCH_SMALL));
     std::vector<uint64_t> small;
     small.reserve(small_words);
     auto put = [&](const uint64_t *v, size_t count) {
@@ -260,8 +260,8 @@ static int sketch_signs_impl(skl_ctx *ctx, const uint8_t *codes, const uint32_t 
     // The sketching buffers belong to the context so that a run of sketch calls does not allocate per call -- but beyond 1 GiB
     // they would sit in the way of what follows (the kNN drivers size their bands by the free memory): released, with the
     // pinned ring.  (Both streams are idle here.)
-    if (ctx->scratch_bytes[12] + ctx->scratch_bytes[13] > (1ull << 30)) {
-        for (int slot : {12, 13}) {
+    if (ctx->scratch_bytes[SCRATCH_SKETCH_BASES] + ctx->scratch_bytes[SCRATCH_SKETCH_SIGNS] > (1ull << 30)) {
+        for (int slot : {SCRATCH_SKETCH_BASES, SCRATCH_SKETCH_SIGNS}) {
             if (ctx->scratch[slot]) HIP_TRY(hipFree(ctx->scratch[slot]));
             ctx->scratch[slot] = nullptr;
             ctx->scratch_bytes[slot] = 0;

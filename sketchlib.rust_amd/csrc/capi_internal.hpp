@@ -1,7 +1,8 @@
 // capi_internal.hpp -- shared between the translation units that implement
 // include/sketchlib_dist.h (capi.cpp: contexts, slabs, dense calls; capi_knn.cpp: the kNN
 // drivers; capi_aux.cpp: candidate lists and sketching).  Not part of the public boundary.
-// How a dense call is launched is decided in dense_plan.hpp (pure, no HIP), reached through kernels.h.
+// How a dense call is launched is decided in dense_plan.hpp (pure, no HIP), reached through kernels.h; how the kNN drivers cut
+// and feed their bands in knn_plan.hpp (pure, no HIP).
 #pragma once
 
 #include "../../include/sketchlib_dist.h"
@@ -15,6 +16,7 @@
 #include <vector>
 
 #include "kernels.h"
+#include "knn_plan.hpp"
 #include "knobs.hpp"
 #include "roctx_ranges.hpp"
 
@@ -59,18 +61,38 @@ struct EbPlan {
     uint8_t *d_block_ke = nullptr;
 };
 
+// The context's grow-only scratch buffers (ctx_scratch).
+enum ScratchSlot : int {
+    SCRATCH_KEY_BAND = 0,          // key band of the kNN drivers; band of a host-destined dense call
+    SCRATCH_COUNTS = 1,            // bin-match counts
+    SCRATCH_KNN_STAGING = 2,       // kNN results on their way to the host
+    SCRATCH_KEY_BAND_2 = 3,        // the second key band (bands that overlap)
+    SCRATCH_TURNED_BAND = 4,       // turned key band (symmetric kNN) ...
+    SCRATCH_TURNED_BAND_2 = 5,     // ... and the second one
+    SCRATCH_KNN_FLAGS = 6,         // its row flags (2 x n u32)
+    SCRATCH_KNN_ROW_BITS = 7,      // its block bits
+    SCRATCH_PRUNE_BOUNDS = 8,      // tile-pruning bounds (n u32)
+    SCRATCH_KNN_TURNED_BITS = 9,   // bits of the turned bands
+    SCRATCH_PRUNE_COUNTERS = 10,   // pruning counters
+    SCRATCH_FUSE_COUNTERS = 11,    // arrival counters of the fused epilogue
+    SCRATCH_SKETCH_BASES = 12,     // GPU sketching: packed bases,
+    SCRATCH_SKETCH_SIGNS = 13,     // signs,
+    SCRATCH_SKETCH_SMALL = 14,     // small arrays
+    SCRATCH_COUNTS_2 = 15,         // second counts band (early break of the core/accessory kNN; odd bands of an overlapped dense call)
+    SCRATCH_SLOTS = 16
+};
+
 struct skl_ctx {
     int device = 0;
     int n_cu = 256;                     // compute units of the device (MI355X: 256)
     hipStream_t own_stream = nullptr;
     hipStream_t stream = nullptr;
     // grow-only scratch
-    void *scratch[16] = {};   // 0/3: key bands, 1: counts, 2: kNN staging, 4/5: turned key bands (symmetric kNN), 6: its row flags (2 x n u32), 7: its block bits,
-                              // 8: tile-pruning bounds (n u32), 9: bits of the turned bands, 10: pruning counters, 11: arrival counters of the fused epilogue, 12-14: GPU sketching (packed bases, signs, small arrays), 15: second counts band (early break of the core/accessory kNN; odd bands of an overlapped dense call)
-    size_t scratch_bytes[16] = {};
+    void *scratch[SCRATCH_SLOTS] = {};
+    size_t scratch_bytes[SCRATCH_SLOTS] = {};
     uint32_t *pinned = nullptr;         // pinned host ring of the sketching upload (two batches of packed bases; grow-only)
     uint64_t pinned_words = 0;
-    size_t fuse_counter_k = 0;          // k-mer lengths the arrival counters of slot 11 count modulo (fused epilogue)
+    size_t fuse_counter_k = 0;          // k-mer lengths the arrival counters of SCRATCH_FUSE_COUNTERS count modulo (fused epilogue)
     hipStream_t aux_stream = nullptr;   // top-k of band i runs here while band i+1 is computed
     hipStream_t epi_stream = nullptr;   // overlapped row bands of a large early-break call (dense_plan.hpp plan_row_bands): band i's epilogue beside band i+1's counts kernel
     // band pipelines (kNN: pair kernel -> top-k; dense to host: pair kernel -> D2H copy):
@@ -102,7 +124,7 @@ struct skl_ctx {
     hipEvent_t eb_events[4] = {nullptr, nullptr, nullptr, nullptr};   // counts of buffer b done / epilogue of buffer b done
     std::vector<EbPlan *> eb_plans;        // early-break decisions of the last few slab pairs (newest last)
     const EbPlan *eb_last_plan = nullptr;  // the plan of the last dense core/accessory call (skl_ctx_early_break_blocks)
-    bool knn_prune_pending = false;        // the device counters (scratch slot 10) hold counts not yet read back
+    bool knn_prune_pending = false;        // the device counters (SCRATCH_PRUNE_COUNTERS) hold counts not yet read back
     uint64_t knn_tiles = 0, knn_tiles_pruned = 0;   // tile pruning of the last self kNN call (skl_ctx_knn_prune_stats)
     int knn_ties = SKL_KNN_TIES_REFERENCE;   // what self_dists_knn returns (mod.rs:133-224); skl_ctx_set_knn_ties(CANONICAL) opts out
     Knobs knobs;                        // environment switches as of skl_ctx_create
@@ -135,7 +157,7 @@ struct DevBuf {
     ~DevBuf() { if (p) (void)hipFree(p); }
 };
 
-constexpr size_t BAND_BYTES = 512ull << 20;  // scratch bound for host-destined / banded output
+using skl::BAND_BYTES;   // (knn_plan.hpp: the kNN band heights read it too)
 
 SKL_INTERNAL int ctx_bind(skl_ctx *ctx);
 // which glibc_log.hpp form reproduces this host's libm log(): probed once per process against
@@ -143,7 +165,7 @@ SKL_INTERNAL int ctx_bind(skl_ctx *ctx);
 // warning printed once)
 SKL_INTERNAL int host_log_variant();
 // grow-only scratch slot `which` of the context, at least `bytes` large
-SKL_INTERNAL int ctx_scratch(skl_ctx *ctx, size_t bytes, void **out, int which = 0);
+SKL_INTERNAL int ctx_scratch(skl_ctx *ctx, size_t bytes, void **out, ScratchSlot which);
 SKL_INTERNAL uint32_t ctx_xcd_shift(const skl_ctx *ctx);   // log2 of the XCDs the tile order deals workgroups to
 SKL_INTERNAL int forced_kernel(const skl_ctx *ctx);   // A/B build: SKL_KERNEL; product library: always 0
 // the pair kernel bracketed by HIP events on the context's stream (skl_ctx_kernel_ms)

@@ -1,7 +1,7 @@
 // capi_knn.cpp -- the sparse (k nearest neighbours) entry points of include/sketchlib_dist.h:
 // row-by-row bands, the one-evaluation self kNN, its multi-GPU split and the merge of partial
 // states.  Kernels: pair_kslice.hip (pair distances, turned second store), kernels.hip
-// (topk_merge_kernel, merge_states_kernel).
+// (topk_merge_kernel, merge_states_kernel).  Band heights, panels, the band driver's geometry and merges: knn_plan.hpp (pure).
 #include "capi_internal.hpp"
 
 #include <algorithm>
@@ -38,25 +38,23 @@ struct KnnState {
 };
 }  // namespace
 
-// Rows per band of the symmetric drivers: about 8 bands per participant (7/16 of the pair
-// evaluations saved), each band at least 32 M pairs, four band buffers within `budget` bytes.
-// TILE-PRUNING COUNTERS (diagnostic): 1 024 slots of 4 words on the device (scratch slot 10), added to by the pair kernels of
+// TILE-PRUNING COUNTERS (diagnostic): 1 024 slots of 4 words on the device (scratch slot SCRATCH_PRUNE_COUNTERS), added to by the pair kernels of
 // every band of a call, read back LAZILY by skl_ctx_knn_prune_stats -- never on the launch path: the drivers that feed bands one
 // call at a time (column windows, column panels) must not stall the host once per call.
 static int prune_stats_reset(skl_ctx *ctx)
 {
     ctx->knn_tiles = ctx->knn_tiles_sparse = ctx->knn_tiles_pruned = ctx->knn_tiles_probe_pruned = ctx->knn_pruned_stages = ctx->knn_tile_stages = 0;
-    if (ctx->scratch[10] != nullptr) HIP_TRY(hipMemsetAsync(ctx->scratch[10], 0, 4096 * sizeof(uint32_t), ctx->stream));
+    if (ctx->scratch[SCRATCH_PRUNE_COUNTERS] != nullptr) HIP_TRY(hipMemsetAsync(ctx->scratch[SCRATCH_PRUNE_COUNTERS], 0, 4096 * sizeof(uint32_t), ctx->stream));
     return SKL_OK;
 }
 
 static int prune_stats_collect(skl_ctx *ctx)
 {
-    if (ctx->scratch[10] == nullptr || !ctx->knn_prune_pending) return SKL_OK;
+    if (ctx->scratch[SCRATCH_PRUNE_COUNTERS] == nullptr || !ctx->knn_prune_pending) return SKL_OK;
     std::vector<uint32_t> counted(4096, 0u);
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     if (ctx->aux_stream) HIP_TRY(hipStreamSynchronize(ctx->aux_stream));
-    HIP_TRY(hipMemcpy(counted.data(), ctx->scratch[10], counted.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(counted.data(), ctx->scratch[SCRATCH_PRUNE_COUNTERS], counted.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
     ctx->knn_tiles_pruned = ctx->knn_tiles_probe_pruned = ctx->knn_pruned_stages = ctx->knn_tiles_sparse = 0;
     for (size_t x = 0; x < 1024; ++x) {
         ctx->knn_tiles_pruned += (uint64_t)counted[4 * x] + counted[4 * x + 1];
@@ -65,22 +63,6 @@ static int prune_stats_collect(skl_ctx *ctx)
         ctx->knn_tiles_sparse += counted[4 * x + 3];
     }
     return SKL_OK;
-}
-
-// Bytes per pair and band buffer the symmetric drivers' budget counts: the record, and for core/accessory keys the share of
-// the early break's two counts buffers (up to 4 lengths x 2 bytes each against four band buffers: + 4 bytes per buffer).
-static size_t coreacc_rec_with_counts(const skl_sketches *s, const skl_dist_params *p)
-{
-    if (p->dist_type != SKL_DIST_COREACC) return sizeof(float);
-    return 2 * sizeof(float) + (s->nk >= 3 && s->nk <= 8 && fused_coreacc_ok(s) ? 4 : 0);
-}
-
-static size_t symmetric_band_rows(size_t n, size_t rec, size_t budget, size_t participants)
-{
-    auto up16 = [](size_t x) { return (x + 15) / 16 * 16; };
-    const size_t budget_rows = std::max<size_t>(16, budget / 4 / (n * rec) / 16 * 16);
-    const size_t parts = std::max<size_t>(1, participants);
-    return std::min(budget_rows, std::max(up16((n + 8 * parts - 1) / (8 * parts)), up16((32ull << 20) / n + 1)));
 }
 
 static int knn_state_init(KnnState &st, size_t rows, size_t knn, bool coreacc, hipStream_t stream, bool ref_heap = false)
@@ -104,365 +86,381 @@ static int knn_state_init(KnnState &st, size_t rows, size_t knn, bool coreacc, h
     return SKL_OK;
 }
 
-// Symmetric self kNN (whole matrix in one call): band [b0, b1) is compared with the columns
-// from b0 on only.  The pair kernel stores every record twice -- row-major for the rows of the
-// band, and turned (pair_kslice.hip, out_t) as candidates of the rows below the band -- and
-// both copies are merged into a running per-row top-k (topk_merge_kernel), so each (i, j) is
-// evaluated once instead of twice (the reference evaluates both, mod.rs:148-171; distances are
-// symmetric).  Same neighbours, same order as the row-by-row form.
+static_assert(PLAN_TOPK_LDS_MAX == TOPK_LDS_MAX && PLAN_REFHEAP_LDS_MAX == REFHEAP_LDS_MAX, "knn_plan.hpp restates these constants of kernels.h");
+
 static bool knn_symmetric_ok(const skl_sketches *s, const skl_dist_params *p)
 {
-    // (beyond 65 535 bins: single-k only -- the k-sliced form walks the k-mer length in segments, the fused
-    // core/accessory form has no such walk)
-    if (p->dist_type == SKL_DIST_COREACC && !fused_coreacc_ok(s)) return false;
-    const int forced = forced_kernel(s->ctx);
-    if (forced != 0 && forced != 4) return false;          // the turned store lives in pair_kslice.hip
-    return true;
+    return skl::knn_symmetric_ok(p->dist_type == SKL_DIST_COREACC, fused_coreacc_ok(s), forced_kernel(s->ctx));
 }
 
-// The bands `bands` (ascending indices; band b = rows [b*band_rows, (b+1)*band_rows)) merged into
-// the running states `st` of all n rows.
-// COLUMN WINDOW (win_lo, win_hi; default: all columns): only the pairs whose COLUMN sample lies in [win_lo, win_hi) are
-// evaluated -- band rows against columns [max(b0, win_lo), win_hi), turned copies to the rows [max(b1, win_lo), win_hi) -- which
-// is one participant's share of the reference-order pipeline over several devices (skl_self_dists_knn_window).
-// CROSS FORM (`cols` given): the rows of `s` against the columns [win_lo, win_hi) of another slab (or of the same one, row
-// ranges of the self kNN: self_rows), no symmetry, nothing turned -- one COLUMN PANEL of the row-by-row kNN.  The drivers
-// call it panel after panel, ascending, so a row meets its candidates in ascending id, its list tightens from panel to panel,
-// and from the second panel on the pair kernel prunes against the rows' bounds (the columns have no lists: bound 0).
-struct KnnCross {
-    const skl_sketches *cols = nullptr;   // null: the symmetric form
-    bool self_rows = false;               // rows and columns are the same sample set: a row is not its own candidate
-    size_t row_lo = 0, row_hi = ~(size_t)0;   // rows of the call (bands are clipped to them)
-    // (symmetric form, one band per call -- skl_self_dists_knn_window: every list the band's TURNED copy reaches already holds
-    // knn candidates, as from a whole-matrix call's second band on: the early break of the core/accessory keys may start with
-    // the call's first band.  The band's own rows are not covered -- under accept logs they may start empty: knn_window_impl)
-    bool lists_hold_knn = false;
+static int knn_ani_undo(const skl_dist_params *p) { return (p->dist_type != SKL_DIST_COREACC && p->ani) ? 1 : 0; }
+
+// The states of rows [r0, r1) -> the public output form (into_sorted_vec of the heaps / the sorted running lists as they are).
+static int knn_finalize(const KnnState &st, size_t r0, size_t r1, size_t knn, const skl_dist_params *p, uint64_t *d_idx, float *d_d0,
+                        float *d_d1, hipStream_t stream)
+{
+    const size_t o = r0 * knn;
+    if (st.h_key != nullptr) {
+        HIP_TRY(launch_refheap_finalize(st.h_key + o, st.h_id + o, st.h_d1 ? st.h_d1 + o : nullptr, st.h_len + r0, (uint32_t)(r1 - r0), (uint32_t)knn,
+                                        knn_ani_undo(p), d_idx, d_d0, d_d1, stream));
+    } else {
+        HIP_TRY(launch_topk_finalize(st.key + o, st.idx + o, st.d1 ? st.d1 + o : nullptr, (r1 - r0) * knn, knn_ani_undo(p), d_idx, d_d0, d_d1, stream));
+    }
+    return SKL_OK;
+}
+
+// ---------------------------------------------------------------------------
+// The band driver: knn_plan.hpp decides the geometry, the buffers' sizes, what a band is eligible for and its two merges;
+// here the decision is executed.
+// ---------------------------------------------------------------------------
+
+// What the plan reads about one call of the band driver: rows of `s` against columns of `cs` (the same slab but for a cross
+// panel), all columns and all rows -- a column window or a cross panel narrows win_* / row_* afterwards.
+static KnnCall knn_call(const skl_ctx *ctx, const skl_sketches *s, const skl_sketches *cs, const skl_dist_params *p, KnnForm form,
+                        size_t knn, size_t band_rows, size_t n_bands, bool overlap, const KnnState &st)
+{
+    KnnCall c;
+    c.form = form;
+    c.n_rows = s->n;
+    c.n_cols = cs->n;
+    c.band_rows = band_rows;
+    c.knn = knn;
+    c.win_hi = cs->n;
+    c.row_hi = s->n;
+    c.coreacc = p->dist_type == SKL_DIST_COREACC;
+    c.ref = st.h_key != nullptr;
+    c.overlap = overlap;
+    c.nk = s->nk;
+    c.ss64 = s->ss64;
+    c.has_comp = s->d_comp != nullptr;
+    c.fused_coreacc_ok = fused_coreacc_ok(s);
+    c.forced_kernel = forced_kernel(ctx);
+    c.n_bands = n_bands;
+    c.knobs = ctx->knobs;
+    return c;
+}
+
+// The scratch of a call: [2] = one per band buffer (the same one twice when bands do not overlap).
+struct KnnBuffers {
+    void *kband[2] = {nullptr, nullptr}, *tband[2] = {nullptr, nullptr};
+    uint32_t *flags[2] = {nullptr, nullptr}, *row_bits[2] = {nullptr, nullptr}, *tbits[2] = {nullptr, nullptr};
+    uint32_t *prune_q = nullptr, *prune_stats = nullptr;
+    void *eb_counts[2] = {nullptr, nullptr};
 };
 
-static int knn_symmetric_bands(skl_ctx *ctx, const skl_sketches *s, const skl_dist_params *p, size_t knn,
-                               size_t band_rows, const std::vector<uint32_t> &bands, bool overlap, KnnState &st,
-                               size_t win_lo = 0, size_t win_hi = ~(size_t)0, const KnnCross &cross = KnnCross())
+static int knn_band_buffers(skl_ctx *ctx, const KnnCall &c, const KnnCallPlan &P, KnnBuffers &m)
 {
-    const bool is_cross = cross.cols != nullptr;
-    const skl_sketches *cs = is_cross ? cross.cols : s;
-    const size_t n = cs->n;            // columns (= samples in the symmetric form)
-    const size_t n_rows = s->n;
-    win_hi = std::min(win_hi, n);
-    const bool coreacc = p->dist_type == SKL_DIST_COREACC;
-    const bool ref = st.h_key != nullptr;   // the reference's tie order: heaps replayed (a row's candidates arrive in ascending id
-                                            // over the bands -- turned from the bands above its own, then its own band's columns)
-    const int mode = coreacc ? MODE_COREACC : MODE_JACCARD;
-    const int jout = coreacc ? 0 : (p->ani ? JOUT_ANI_KEY : JOUT_DIST);
-    const size_t rec = coreacc ? 2 * sizeof(float) : sizeof(float);
-    const size_t t_stride = (band_rows + 31) / 32 * 32;   // whole tiles of either height (16 or 32 rows: dispatch_pair_kernel)
-    void *kband[2] = {nullptr, nullptr}, *tband[2] = {nullptr, nullptr};
-    const size_t k_cols = is_cross ? win_hi - win_lo / 64 * 64 : n;   // columns of a band's records (cross form: the panel's)
-    SKL_TRY(ctx_scratch(ctx, band_rows * k_cols * rec, &kband[0], 0));
-    if (!is_cross) SKL_TRY(ctx_scratch(ctx, n * t_stride * rec, &tband[0], 4));
-    kband[1] = kband[0];
-    tband[1] = tband[0];
-    if (overlap) {
-        SKL_TRY(ctx_scratch(ctx, band_rows * k_cols * rec, &kband[1], 3));
-        if (!is_cross) SKL_TRY(ctx_scratch(ctx, n * t_stride * rec, &tband[1], 5));
+    SKL_TRY(ctx_scratch(ctx, P.key_band_bytes, &m.kband[0], SCRATCH_KEY_BAND));
+    if (P.turned) SKL_TRY(ctx_scratch(ctx, P.turned_band_bytes, &m.tband[0], SCRATCH_TURNED_BAND));
+    m.kband[1] = m.kband[0];
+    m.tband[1] = m.tband[0];
+    if (c.overlap) {
+        SKL_TRY(ctx_scratch(ctx, P.key_band_bytes, &m.kband[1], SCRATCH_KEY_BAND_2));
+        if (P.turned) SKL_TRY(ctx_scratch(ctx, P.turned_band_bytes, &m.tband[1], SCRATCH_TURNED_BAND_2));
     }
-    // Row flags of the transposed band (one array per band buffer): the pair kernel marks the rows that
-    // received a record below their knn-th best so far with the band's number, and the merge of the
-    // transposed band (n - b1 workgroups reading band_rows records each: 2/3 of the merge time at cfg 5)
-    // returns at once for the others.  The threshold the pair kernel compares with is read from the
-    // running state while merges of earlier bands may still be updating it on the other stream: a
-    // stale value is a higher one (a row's knn-th best only ever improves), so it flags too many rows,
-    // never too few; ties never count (a band's sample ids are above every id a lower row holds).
-    void *flag_mem = nullptr;
-    SKL_TRY(ctx_scratch(ctx, 2 * n * sizeof(uint32_t), &flag_mem, 6));
-    uint32_t *flags[2] = {(uint32_t *)flag_mem, (uint32_t *)flag_mem + (overlap ? n : 0)};
-    HIP_TRY(hipMemsetAsync(flag_mem, 0, 2 * n * sizeof(uint32_t), ctx->stream));
-    // ... and for the band's own rows one bit per 64-column block (the merge of the band reads only the
-    // marked stretches of a row): band_rows x ceil(columns / 2048) words per band buffer, behind the flags
-    const size_t bit_words = ((is_cross ? k_cols : n) / 64 + 1 + 31) / 32;   // (bit = 64-column block of the band's view)
-    void *bits_mem = nullptr;
-    SKL_TRY(ctx_scratch(ctx, 2 * band_rows * bit_words * sizeof(uint32_t), &bits_mem, 7));
-    uint32_t *row_bits[2] = {(uint32_t *)bits_mem, (uint32_t *)bits_mem + (overlap ? band_rows * bit_words : 0)};
-    // ... and for the turned band one bit per (column, 32-row stretch of the band), so that BOTH merges read marked stretches
-    // only and a tile without a mark need not exist: TILE PRUNING (pair_kslice_walk.inc).  Single-k keys are monotone in the
-    // mismatch count, so before each band a small kernel turns every sample's current knn-th best into the mismatch count
-    // beyond which a pair cannot enter its list, and the pair kernel leaves a tile once every pair of it is beyond both its
-    // samples' bounds on the chunks walked so far.  The bounds come from the same (possibly stale, i.e. too high) thresholds
-    // as the flags: a pair pruned now would be rejected by both lists whenever it arrived, so the lists -- ids AND order, in
-    // either tie rule -- are those of the unpruned run.  Not with a completeness correction (the key then depends on the pair).
-    const size_t tbit_words = is_cross ? 0 : (t_stride / 32 + 31) / 32;   // (cross form: nothing turned; the array is only a non-null mark)
-    const bool prune = ctx->knobs.knn_prune && ctx->knobs.knn_row_flags && !coreacc && !(s->d_comp != nullptr) &&
-                       s->ss64 <= (size_t)KSLICE_MAX_U16_CHUNKS;
-    uint32_t *tbits[2] = {nullptr, nullptr}, *prune_q = nullptr, *prune_stats = nullptr;
-    if (ctx->knobs.knn_row_flags) {
+    void *flag_mem = nullptr, *bits_mem = nullptr;
+    SKL_TRY(ctx_scratch(ctx, P.flags_bytes, &flag_mem, SCRATCH_KNN_FLAGS));
+    m.flags[0] = (uint32_t *)flag_mem;
+    m.flags[1] = m.flags[0] + P.flags_half;
+    HIP_TRY(hipMemsetAsync(flag_mem, 0, P.flags_bytes, ctx->stream));
+    SKL_TRY(ctx_scratch(ctx, P.row_bits_bytes, &bits_mem, SCRATCH_KNN_ROW_BITS));
+    m.row_bits[0] = (uint32_t *)bits_mem;
+    m.row_bits[1] = m.row_bits[0] + P.row_bits_half;
+    if (P.turned_bits_bytes) {
         void *tb = nullptr;
-        SKL_TRY(ctx_scratch(ctx, std::max<size_t>(2 * n * tbit_words, 64) * sizeof(uint32_t), &tb, 9));
-        tbits[0] = (uint32_t *)tb;
-        tbits[1] = (uint32_t *)tb + (overlap ? n * tbit_words : 0);
+        SKL_TRY(ctx_scratch(ctx, P.turned_bits_bytes, &tb, SCRATCH_KNN_TURNED_BITS));
+        m.tbits[0] = (uint32_t *)tb;
+        m.tbits[1] = m.tbits[0] + P.turned_bits_half;
     }
-    if (prune) {
+    if (P.prune) {
         void *pq = nullptr, *ps = nullptr;
-        SKL_TRY(ctx_scratch(ctx, (n_rows + 64 + (is_cross ? n + 64 : 0)) * sizeof(uint32_t), &pq, 8));
-        const bool fresh = ctx->scratch[10] == nullptr;
-        SKL_TRY(ctx_scratch(ctx, 4096 * sizeof(uint32_t), &ps, 10));
-        prune_q = (uint32_t *)pq;
-        prune_stats = (uint32_t *)ps;
-        if (fresh) HIP_TRY(hipMemsetAsync(prune_stats, 0, 4096 * sizeof(uint32_t), ctx->stream));   // (afterwards: prune_stats_reset, at the start of a call)
+        SKL_TRY(ctx_scratch(ctx, P.prune_bounds_bytes, &pq, SCRATCH_PRUNE_BOUNDS));
+        const bool fresh = ctx->scratch[SCRATCH_PRUNE_COUNTERS] == nullptr;
+        SKL_TRY(ctx_scratch(ctx, 4096 * sizeof(uint32_t), &ps, SCRATCH_PRUNE_COUNTERS));
+        m.prune_q = (uint32_t *)pq;
+        m.prune_stats = (uint32_t *)ps;
+        if (fresh) HIP_TRY(hipMemsetAsync(m.prune_stats, 0, 4096 * sizeof(uint32_t), ctx->stream));   // (afterwards: prune_stats_reset, at the start of a call)
         ctx->knn_prune_pending = true;
-        if (is_cross) HIP_TRY(hipMemsetAsync(prune_q + n_rows + 64, 0, (n + 64) * sizeof(uint32_t), ctx->stream));   // the columns have no lists: bound 0
+        if (c.cross()) HIP_TRY(hipMemsetAsync(m.prune_q + P.prune_cols_at, 0, (c.n_cols + 64) * sizeof(uint32_t), ctx->stream));   // the columns have no lists: bound 0
     }
-    hipStream_t topk_stream = overlap ? ctx->aux_stream : ctx->stream;
-    if (overlap) {   // the states were cleared on the context's stream, the merges run on the other one
+    return SKL_OK;
+}
+
+// The early break's decision for the call and its counts buffers: *eb_lengths k-mer lengths counted (0: no early break).
+// The counts kernel stays on the context's stream; the band's epilogue goes with the merges (the other stream when bands
+// overlap): it is bound by memory and by the latency of the one-by-one completions, the counts kernel by the VALUs.
+static int knn_early_break_buffers(skl_ctx *ctx, const skl_sketches *s, const skl_sketches *cs, const KnnCall &c, const KnnCallPlan &P,
+                                   KnnBuffers &m, int *eb_lengths)
+{
+    *eb_lengths = 0;
+    if (!P.eb_may_ask) return SKL_OK;
+    SKL_TRY(early_break_lengths(ctx, s, cs, 1, eb_lengths));
+    if (*eb_lengths <= 0) return SKL_OK;
+    // (the band heights count these buffers in -- coreacc_rec_with_counts() -- but a band height the CALLER chose, or a
+    // device short of memory, must not fail the call: without the counts the bands take the fused kernel as before)
+    const size_t bytes = knn_eb_counts_bytes(c, *eb_lengths);
+    int rc = ctx_scratch(ctx, bytes, &m.eb_counts[0], SCRATCH_COUNTS);
+    ctx->clean_plane1 = nullptr;   // (the counts scratch holds another layout now)
+    m.eb_counts[1] = m.eb_counts[0];
+    if (rc == SKL_OK && c.overlap) rc = ctx_scratch(ctx, bytes, &m.eb_counts[1], SCRATCH_COUNTS_2);
+    if (rc == SKL_ERR_OOM) {
+        (void)hipGetLastError();   // (cleared: the call goes on)
+        *eb_lengths = 0;
+        return SKL_OK;
+    }
+    return rc;
+}
+
+// uint4 words of the lane slab before the 64-column block that starts at column col0
+static size_t knn_lane_offset(const skl_sketches *s, size_t col0) { return (col0 / 64) * (s->nk * s->ss64 * 7 * 64); }
+
+// The pair launch of band B into buffer `buf`: the view, the marks it leaves for the merges (cleared here) and, with tile
+// pruning, every sample's bound as of now.
+static int knn_pair_args(skl_ctx *ctx, const skl_sketches *s, const skl_sketches *cs, const skl_dist_params *p, const KnnCall &c,
+                         const KnnCallPlan &P, const KnnBand &B, const KnnBuffers &m, int buf, const KnnState &st, PairArgs *out)
+{
+    PairArgs &g = *out;
+    const size_t knn = c.knn;
+    SKL_TRY(fill_args(s, cs, p, c.coreacc ? MODE_COREACC : MODE_JACCARD, c.coreacc ? 0 : (p->ani ? JOUT_ANI_KEY : JOUT_DIST), &g));
+    g.B += knn_lane_offset(s, B.col0);
+    g.nB = B.nB;
+    if (g.compB) g.compB += B.col0;
+    g.row_begin = (uint32_t)B.b0;
+    g.row_end = (uint32_t)B.b1;
+    g.self_mode = 0;
+    g.out_base = (uint64_t)B.b0 * g.nB;
+    g.out = m.kband[buf];
+    g.out_t = B.has_turned ? (float *)m.tband[buf] : nullptr;
+    g.t_col_begin = (uint32_t)(B.t_first - B.col0);
+    g.t_stride = (uint32_t)P.t_stride;
+    if (ctx->knobs.knn_row_flags) {
+        HIP_TRY(hipMemsetAsync(m.row_bits[buf], 0, c.band_rows * P.bit_words * sizeof(uint32_t), ctx->stream));
+        g.r_bits = m.row_bits[buf];
+        g.r_bits_stride = (uint32_t)P.bit_words;
+        g.r_thr = c.ref ? st.thr + B.b0 : st.key + B.b0 * knn + (knn - 1);        // knn-th best of sample b0 + r
+        g.r_thr_stride = c.ref ? 1u : (uint32_t)knn;
+    }
+    if (g.out_t && ctx->knobs.knn_row_flags) {
+        g.t_flag = m.flags[buf] + B.col0;                   // indexed by the view's column number, like t_col_begin
+        g.t_flag_value = B.flag_value;
+        g.t_thr = c.ref ? st.thr + B.col0 : st.key + B.col0 * knn + (knn - 1);      // knn-th best of sample col0 + c
+        g.t_thr_stride = c.ref ? 1u : (uint32_t)knn;
+        HIP_TRY(hipMemsetAsync(m.tbits[buf] + B.t_first * P.tbit_words, 0, (c.win_hi - B.t_first) * P.tbit_words * sizeof(uint32_t), ctx->stream));
+        g.t_bits = m.tbits[buf] + B.col0 * P.tbit_words;
+        g.t_bits_stride = (uint32_t)P.tbit_words;
+    }
+    if (P.prune) {
+        // every sample's bound as of now (the merges of earlier bands may still be lowering thresholds: stale = too high = safe)
+        HIP_TRY(launch_prune_thresholds(c.ref ? st.thr : st.key + (knn - 1), c.ref ? 1u : (uint32_t)knn, (uint32_t)c.n_rows, g.dtab,
+                                        (uint32_t)(64 * s->ss64), m.prune_q, ctx->stream));
+        g.prune_q_rows = m.prune_q;
+        g.prune_q_cols = m.prune_q + P.prune_cols_at + B.col0;
+        g.prune_stats = m.prune_stats;
+        g.prune_flags = ctx->knobs.knn_sparse ? 0u : 1u;
+
+        if (!g.t_bits) {   // (the last band has no turned copy; the kernel takes "both bit sets given" as the sign that the merges mask)
+            g.t_bits = m.tbits[buf] + B.col0 * P.tbit_words;
+            g.t_bits_stride = (uint32_t)P.tbit_words;
+        }
+        ctx->knn_tiles += B.tiles;
+    }
+    return SKL_OK;
+}
+
+// EARLY-BREAK band: the counts launch `cnt` over the view of the band's pair launch `g` (first eb_lengths k-mer lengths, u16
+// records, k-major) and the epilogue `e` that turns them into g's records, marks and turned copy.
+static int knn_early_break_args(skl_ctx *ctx, const skl_sketches *s, const skl_sketches *cs, const skl_dist_params *p, const PairArgs &g,
+                                const KnnBand &B, int eb_lengths, void *counts, PairArgs *cnt, EpilogueKnnArgs *epi)
+{
+    const size_t pairs_view = (B.b1 - B.b0) * (size_t)g.nB;
+    PairArgs &c = *cnt;
+    SKL_TRY(fill_args(s, cs, p, MODE_COUNTS, 0, &c));
+    c.B += knn_lane_offset(s, B.col0);
+    c.nB = g.nB;
+    c.row_begin = g.row_begin;
+    c.row_end = g.row_end;
+    c.self_mode = 0;
+    c.out_base = g.out_base;
+    c.k_count = (uint32_t)eb_lengths;
+    c.cnt_pair_stride = 1;
+    c.cnt_k_stride = pairs_view;
+    c.k_sliced = 1;
+    c.k_slices = 1;
+    c.cnt_u16 = 1;
+    c.out = counts;
+    EpilogueKnnArgs &e = *epi;
+    memset(&e, 0, sizeof e);
+    e.counts = (const uint32_t *)counts;
+    e.n_pairs = pairs_view;
+    e.rows = (uint32_t)(B.b1 - B.b0);
+    e.nB = g.nB;
+    e.nk = (uint32_t)eb_lengths;
+    e.nk_total = (uint32_t)s->nk;
+    e.ss64 = (uint32_t)s->ss64;
+    e.row_sample0 = (uint32_t)B.b0;
+    e.col_sample0 = (uint32_t)B.col0;
+    e.ytab = s->d_ytab;
+    e.kf = s->d_kf;
+    e.tolerance = g.tolerance;
+    e.rows_ref = s->d_rows;
+    e.cols_ref = cs->d_rows;
+    e.out = (float *)g.out;
+    e.r_thr = g.r_thr;
+    e.r_thr_stride = g.r_thr_stride;
+    e.r_bits = g.r_bits;
+    e.r_bits_stride = g.r_bits_stride;
+    e.out_t = g.out_t;
+    e.t_col_begin = g.t_col_begin;
+    e.t_stride = g.t_stride;
+    e.t_thr = g.t_thr;
+    e.t_thr_stride = g.t_thr_stride;
+    e.t_flag = g.t_flag;
+    e.t_flag_value = g.t_flag_value;
+    e.t_bits = g.t_bits;
+    e.t_bits_stride = g.t_bits_stride;
+    e.alive_count = ctx->eb_counter;
+    e.min_alive = s->min_alive;
+    e.xcd_blocked = (uint32_t)ctx->knobs.knn_epi_blocked;
+    e.cnt_u16 = 1;
+    e.plain_marks_nothing = B.plain_marks_nothing ? 1u : 0u;
+    return SKL_OK;
+}
+
+// Where a planned merge reads: the band buffer, the rows' flags and the marks of its records.
+struct KnnMergeSource {
+    const float *keys = nullptr;
+    const uint32_t *flag = nullptr, *seg_bits = nullptr;
+    uint32_t seg_bits_stride = 0;
+};
+static KnnMergeSource knn_merge_source(const skl_ctx *ctx, const KnnCallPlan &P, const KnnMerge &mg, const KnnBuffers &m, int buf)
+{
+    KnnMergeSource src;
+    const bool marks = ctx->knobs.knn_row_flags;
+    const size_t first = mg.state_row_base;   // (turned: row r of the launch = sample t_first + r)
+    src.keys = (const float *)(mg.turned ? m.tband[buf] : m.kband[buf]);
+    src.flag = mg.row_flags && marks ? m.flags[buf] + first : nullptr;
+    src.seg_bits = !marks ? nullptr : (mg.turned ? m.tbits[buf] + first * P.tbit_words : m.row_bits[buf]);
+    src.seg_bits_stride = (uint32_t)(mg.turned ? P.tbit_words : P.bit_words);
+    return src;
+}
+
+// canonical ties: the sorted running lists
+static int knn_merge_topk(const skl_ctx *ctx, const KnnCall &c, const KnnBand &B, const KnnMerge &mg, const KnnMergeSource &src,
+                          const KnnState &st, hipStream_t stream)
+{
+    TopkMergeArgs m;
+    memset(&m, 0, sizeof m);
+    m.knn = (uint32_t)c.knn;
+    m.stride2 = c.coreacc ? 2 : 1;
+    m.run_key = st.key;
+    m.run_idx = st.idx;
+    m.run_d1 = st.d1;
+    m.streaming = ctx->knobs.topk_stream;
+    m.keys = src.keys;
+    m.key_stride = mg.stride * m.stride2;
+    m.rows = mg.rows;
+    m.cols = mg.cols;
+    m.id_base = mg.id_base;
+    m.skip_below = mg.skip_below;
+    m.state_row_base = mg.state_row_base;
+    m.self_id_base = mg.self_id_base;
+    m.flag = src.flag;
+    m.flag_value = mg.row_flags ? B.flag_value : 0u;
+    m.seg_bits = src.seg_bits;
+    m.seg_bits_stride = src.seg_bits_stride;
+    m.seg_shift = mg.seg_shift;
+    HIP_TRY(launch_topk_merge(m, stream));
+    return SKL_OK;
+}
+
+// reference ties: the heaps replayed
+static int knn_merge_refheap(const skl_ctx *ctx, const KnnCall &c, const KnnBand &B, const KnnMerge &mg, const KnnMergeSource &src,
+                             const KnnState &st, hipStream_t stream)
+{
+    RefHeapMergeArgs m;
+    memset(&m, 0, sizeof m);
+    m.knn = (uint32_t)c.knn;
+    m.stride2 = c.coreacc ? 2 : 1;
+    m.h_key = st.h_key;
+    m.h_id = st.h_id;
+    m.h_d1 = st.h_d1;
+    m.h_len = st.h_len;
+    m.thr = st.thr;
+    m.log_rec = st.log_rec;
+    m.log_id = st.log_id;
+    m.log_len = st.log_len;
+    m.log_cap = st.log_cap;
+    m.force_workgroup_form = ctx->knobs.refheap_wave ? 0u : 1u;
+    m.keys = src.keys;
+    m.key_stride = mg.stride * m.stride2;
+    m.rows = mg.rows;
+    m.cols = mg.cols;
+    m.id_base = mg.id_base;
+    m.skip_below = mg.skip_below;
+    m.state_row_base = mg.state_row_base;
+    m.self_id_base = mg.self_id_base;
+    m.flag = src.flag;
+    m.flag_value = B.flag_value;
+    m.seg_bits = src.seg_bits;
+    m.seg_bits_stride = src.seg_bits_stride;
+    m.seg_shift = mg.seg_shift;
+    HIP_TRY(launch_refheap_merge(m, stream));
+    return SKL_OK;
+}
+
+// The bands `bands` of call `c` (ascending indices) merged into the running states `st`: rows of `s` against columns of `cs`.
+static int knn_run_bands(skl_ctx *ctx, const skl_sketches *s, const skl_sketches *cs, const skl_dist_params *p, const KnnCall &c,
+                         const std::vector<uint32_t> &bands, KnnState &st)
+{
+    const KnnCallPlan P = plan_knn_call(c);
+    const int mode = c.coreacc ? MODE_COREACC : MODE_JACCARD;
+    KnnBuffers m;
+    SKL_TRY(knn_band_buffers(ctx, c, P, m));
+    hipStream_t topk_stream = c.overlap ? ctx->aux_stream : ctx->stream;
+    if (c.overlap) {   // the states were cleared on the context's stream, the merges run on the other one
         HIP_TRY(hipEventRecord(ctx->knn_pair_done[0], ctx->stream));
         HIP_TRY(hipStreamWaitEvent(topk_stream, ctx->knn_pair_done[0], 0));
     }
-
-    // EARLY BREAK (core/accessory keys; capi.cpp early_break_lengths): from the call's second band on -- every list then holds
-    // knn candidates, so a pair that left the reference's loop early, (1, 1), marks nothing -- the band is COUNTED at its first
-    // eb_lengths k-mer lengths (k-sliced counts launch) and coreacc_epilogue_knn_kernel writes the records, the marks and the
-    // turned copy (pre-filled with (1, 1)), completing the pairs still in the running.  Same records as the fused kernel's.
-    // The counts kernel stays on the context's stream; the band's epilogue goes with the merges (the other stream when bands
-    // overlap): it is bound by memory and by the latency of the one-by-one completions, the counts kernel by the VALUs.
     int eb_lengths = 0;
-    void *eb_counts[2] = {nullptr, nullptr};
-    if (coreacc && !is_cross && fused_coreacc_ok(s) && forced_kernel(ctx) == 0 && ctx->knobs.knn_row_flags &&
-        (bands.size() > 1 || cross.lists_hold_knn)) {
-        SKL_TRY(early_break_lengths(ctx, s, cs, 1, &eb_lengths));
-        if (eb_lengths > 0) {
-            // (the band heights count these buffers in -- coreacc_rec_with_counts() -- but a band height the CALLER chose, or a
-            // device short of memory, must not fail the call: without the counts the bands take the fused kernel as before)
-            const size_t bytes = band_rows * n * (size_t)eb_lengths * sizeof(uint16_t);   // (the largest view a band can have; u16 records: fused_coreacc_ok means at most 65 472 bins)
-            int rc = ctx_scratch(ctx, bytes, &eb_counts[0], 1);
-            ctx->clean_plane1 = nullptr;   // (the counts scratch holds another layout now)
-            eb_counts[1] = eb_counts[0];
-            if (rc == SKL_OK && overlap) rc = ctx_scratch(ctx, bytes, &eb_counts[1], 15);
-            if (rc == SKL_ERR_OOM) {
-                (void)hipGetLastError();   // (cleared: the call goes on)
-                eb_lengths = 0;
-            } else if (rc != SKL_OK) {
-                return rc;
-            }
-        }
-    }
-    const size_t jb_words = s->nk * s->ss64 * 7 * 64;   // uint4 per 64-column block of the lane slab
+    SKL_TRY(knn_early_break_buffers(ctx, s, cs, c, P, m, &eb_lengths));
     size_t it = 0;
     for (const uint32_t band : bands) {
-        const size_t b0 = std::max((size_t)band * band_rows, cross.row_lo);
-        const size_t b1 = std::min(std::min(n_rows, (size_t)band * band_rows + band_rows), cross.row_hi);
-        if (b1 <= b0) continue;
-        const size_t c_first = is_cross ? win_lo : std::max(b0, win_lo);   // first candidate column of the band's own rows
-        const size_t t_first = is_cross ? win_hi : std::max(b1, win_lo);   // first row that receives the band turned (cross form: none)
-        if (c_first >= win_hi) continue;               // the window lies left of this band: nothing of it here
+        const KnnBand B = plan_knn_band(c, P, band, it, eb_lengths);
+        if (B.skip) continue;
         const RoctxRange range_("skl:knn_band pair kernel + merges (every pair once)");
-        const int buf = overlap ? (int)(it & 1) : 0;
-        if (overlap && it >= 2) HIP_TRY(hipStreamWaitEvent(ctx->stream, ctx->knn_topk_done[buf], 0));
-        // the band against the column view that starts at the 64-column block holding its first candidate column
-        const size_t col0 = c_first / 64 * 64;
+        const int buf = c.overlap ? (int)(it & 1) : 0;
+        if (c.overlap && it >= 2) HIP_TRY(hipStreamWaitEvent(ctx->stream, ctx->knn_topk_done[buf], 0));
         PairArgs g;
-        SKL_TRY(fill_args(s, cs, p, mode, jout, &g));
-        g.B += (col0 / 64) * jb_words;
-        g.nB = (uint32_t)(win_hi - col0);
-        if (g.compB) g.compB += col0;
-        g.row_begin = (uint32_t)b0;
-        g.row_end = (uint32_t)b1;
-        g.self_mode = 0;
-        g.out_base = (uint64_t)b0 * g.nB;
-        g.out = kband[buf];
-        g.out_t = t_first < win_hi ? (float *)tband[buf] : nullptr;
-        g.t_col_begin = (uint32_t)(t_first - col0);
-        g.t_stride = (uint32_t)t_stride;
-        const uint32_t flag_value = (uint32_t)(it + 1);      // never 0, distinct per band of this call
-        if (ctx->knobs.knn_row_flags) {
-            HIP_TRY(hipMemsetAsync(row_bits[buf], 0, band_rows * bit_words * sizeof(uint32_t), ctx->stream));
-            g.r_bits = row_bits[buf];
-            g.r_bits_stride = (uint32_t)bit_words;
-            g.r_thr = ref ? st.thr + b0 : st.key + b0 * knn + (knn - 1);        // knn-th best of sample b0 + r
-            g.r_thr_stride = ref ? 1u : (uint32_t)knn;
-        }
-        if (g.out_t && ctx->knobs.knn_row_flags) {
-            g.t_flag = flags[buf] + col0;                   // indexed by the view's column number, like t_col_begin
-            g.t_flag_value = flag_value;
-            g.t_thr = ref ? st.thr + col0 : st.key + col0 * knn + (knn - 1);      // knn-th best of sample col0 + c
-            g.t_thr_stride = ref ? 1u : (uint32_t)knn;
-            HIP_TRY(hipMemsetAsync(tbits[buf] + t_first * tbit_words, 0, (win_hi - t_first) * tbit_words * sizeof(uint32_t), ctx->stream));
-            g.t_bits = tbits[buf] + col0 * tbit_words;
-            g.t_bits_stride = (uint32_t)tbit_words;
-        }
-        if (prune) {
-            // every sample's bound as of now (the merges of earlier bands may still be lowering thresholds: stale = too high = safe)
-            HIP_TRY(launch_prune_thresholds(ref ? st.thr : st.key + (knn - 1), ref ? 1u : (uint32_t)knn, (uint32_t)n_rows, g.dtab,
-                                            (uint32_t)(64 * s->ss64), prune_q, ctx->stream));
-            g.prune_q_rows = prune_q;
-            g.prune_q_cols = (is_cross ? prune_q + n_rows + 64 : prune_q) + col0;
-            g.prune_stats = prune_stats;
-            g.prune_flags = ctx->knobs.knn_sparse ? 0u : 1u;
-
-            if (!g.t_bits) {   // (the last band has no turned copy; the kernel takes "both bit sets given" as the sign that the merges mask)
-                g.t_bits = tbits[buf] + col0 * tbit_words;
-                g.t_bits_stride = (uint32_t)tbit_words;
-            }
-            ctx->knn_tiles += (uint64_t)((b1 - b0 + 31) / 32) * ((g.nB + 127) / 128);
-        }
-        const bool eb_band = eb_lengths > 0 && (it >= 1 || cross.lists_hold_knn);
+        SKL_TRY(knn_pair_args(ctx, s, cs, p, c, P, B, m, buf, st, &g));
         EpilogueKnnArgs e;
-        if (eb_band) {
-            const size_t pairs_view = (b1 - b0) * (size_t)g.nB;
-            void *counts = eb_counts[buf];
-            PairArgs c;
-            SKL_TRY(fill_args(s, cs, p, MODE_COUNTS, 0, &c));
-            c.B += (col0 / 64) * jb_words;
-            c.nB = g.nB;
-            c.row_begin = g.row_begin;
-            c.row_end = g.row_end;
-            c.self_mode = 0;
-            c.out_base = g.out_base;
-            c.k_count = (uint32_t)eb_lengths;
-            c.cnt_pair_stride = 1;
-            c.cnt_k_stride = pairs_view;
-            c.k_sliced = 1;
-            c.k_slices = 1;
-            c.cnt_u16 = 1;
-            c.out = counts;
-            SKL_TRY(timed_pair_launch(ctx, c, MODE_COUNTS));
-            memset(&e, 0, sizeof e);
-            e.counts = (const uint32_t *)counts;
-            e.n_pairs = pairs_view;
-            e.rows = (uint32_t)(b1 - b0);
-            e.nB = g.nB;
-            e.nk = (uint32_t)eb_lengths;
-            e.nk_total = (uint32_t)s->nk;
-            e.ss64 = (uint32_t)s->ss64;
-            e.row_sample0 = (uint32_t)b0;
-            e.col_sample0 = (uint32_t)col0;
-            e.ytab = s->d_ytab;
-            e.kf = s->d_kf;
-            e.tolerance = g.tolerance;
-            e.rows_ref = s->d_rows;
-            e.cols_ref = cs->d_rows;
-            e.out = (float *)kband[buf];
-            e.r_thr = g.r_thr;
-            e.r_thr_stride = g.r_thr_stride;
-            e.r_bits = g.r_bits;
-            e.r_bits_stride = g.r_bits_stride;
-            e.out_t = g.out_t;
-            e.t_col_begin = g.t_col_begin;
-            e.t_stride = g.t_stride;
-            e.t_thr = g.t_thr;
-            e.t_thr_stride = g.t_thr_stride;
-            e.t_flag = g.t_flag;
-            e.t_flag_value = g.t_flag_value;
-            e.t_bits = g.t_bits;
-            e.t_bits_stride = g.t_bits_stride;
-            e.alive_count = ctx->eb_counter;
-            e.min_alive = s->min_alive;
-            e.xcd_blocked = (uint32_t)ctx->knobs.knn_epi_blocked;
-            e.cnt_u16 = 1;
-            // (bands ascend: the `it` bands before this one each gave band_rows candidates to every row the turned copy reaches,
-            // and their merges run before this launch on the same stream)
-            e.plain_marks_nothing = (cross.lists_hold_knn || it * band_rows >= knn) ? 1u : 0u;
-            ctx->eb_pairs += pairs_view;
+        if (B.eb_band) {
+            PairArgs cnt;
+            SKL_TRY(knn_early_break_args(ctx, s, cs, p, g, B, eb_lengths, m.eb_counts[buf], &cnt, &e));
+            SKL_TRY(timed_pair_launch(ctx, cnt, MODE_COUNTS));
+            ctx->eb_pairs += e.n_pairs;
             ctx->last_kernel += " + early break: " + std::to_string(eb_lengths) + " of " + std::to_string(s->nk) + " k-mer lengths counted, the pairs still in the running completed by the band's epilogue";
         } else {
             SKL_TRY(timed_pair_launch(ctx, g, mode));
         }
-        if (overlap) {
+        if (c.overlap) {
             HIP_TRY(hipEventRecord(ctx->knn_pair_done[buf], ctx->stream));
             HIP_TRY(hipStreamWaitEvent(topk_stream, ctx->knn_pair_done[buf], 0));
         }
-        if (eb_band) {   // counts -> records, marks, turned copy: with the merges, behind the counts kernel
+        if (B.eb_band) {   // counts -> records, marks, turned copy: with the merges, behind the counts kernel
             if (g.out_t != nullptr) {   // (1, 1): every pair that left the loop before its third length
-                HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)tband[buf], 0x3F800000, (win_hi - t_first) * t_stride * 2, topk_stream));
+                HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)m.tband[buf], 0x3F800000, (c.win_hi - B.t_first) * P.t_stride * 2, topk_stream));
             }
             HIP_TRY(launch_coreacc_epilogue_knn(e, topk_stream));
         }
-        if (ref) {
-            RefHeapMergeArgs m;
-            memset(&m, 0, sizeof m);
-            m.knn = (uint32_t)knn;
-            m.stride2 = coreacc ? 2 : 1;
-            m.h_key = st.h_key;
-            m.h_id = st.h_id;
-            m.h_d1 = st.h_d1;
-            m.h_len = st.h_len;
-            m.thr = st.thr;
-            m.log_rec = st.log_rec;
-            m.log_id = st.log_id;
-            m.log_len = st.log_len;
-            m.log_cap = st.log_cap;
-            m.force_workgroup_form = ctx->knobs.refheap_wave ? 0u : 1u;
-            // rows below the band FIRST: for them the band's samples are the next candidates in ascending id, and their
-            // own band comes later; then the band's own rows (columns [b0, n) minus themselves: everything below b0 reached
-            // them turned, from the bands above).  Either way a row is fed ascending ids over the sequence of launches.
-            m.keys = (const float *)tband[buf];
-            m.key_stride = (uint64_t)t_stride * m.stride2;
-            m.rows = g.out_t ? (uint32_t)(win_hi - t_first) : 0u;
-            m.cols = (uint32_t)(b1 - b0);
-            m.id_base = (uint32_t)b0;
-            m.skip_below = 0;
-            m.self_id_base = m.state_row_base = (uint32_t)t_first;
-            m.flag = ctx->knobs.knn_row_flags ? flags[buf] + t_first : nullptr;
-            m.flag_value = flag_value;
-            m.seg_bits = ctx->knobs.knn_row_flags ? tbits[buf] + t_first * tbit_words : nullptr;   // (row r of this launch = sample t_first + r)
-            m.seg_bits_stride = (uint32_t)tbit_words;
-            m.seg_shift = 5;
-            HIP_TRY(launch_refheap_merge(m, topk_stream));
-            m.flag = nullptr;
-            m.seg_shift = 6;
-            m.keys = (const float *)kband[buf];
-            m.key_stride = (uint64_t)g.nB * m.stride2;
-            m.rows = (uint32_t)(b1 - b0);
-            m.cols = g.nB;
-            m.id_base = (uint32_t)col0;
-            m.skip_below = (uint32_t)c_first;
-            m.state_row_base = (uint32_t)b0;
-            m.self_id_base = (is_cross && !cross.self_rows) ? 0xFFFFFFFFu : (uint32_t)b0;
-            m.seg_bits = ctx->knobs.knn_row_flags ? row_bits[buf] : nullptr;
-            m.seg_bits_stride = (uint32_t)bit_words;
-            HIP_TRY(launch_refheap_merge(m, topk_stream));
-            if (overlap) HIP_TRY(hipEventRecord(ctx->knn_topk_done[buf], topk_stream));
-            ++it;
-            continue;
+        for (const KnnMerge &mg : B.merge) {
+            const KnnMergeSource src = knn_merge_source(ctx, P, mg, m, buf);
+            SKL_TRY(c.ref ? knn_merge_refheap(ctx, c, B, mg, src, st, topk_stream) : knn_merge_topk(ctx, c, B, mg, src, st, topk_stream));
         }
-        TopkMergeArgs m;
-        memset(&m, 0, sizeof m);
-        m.knn = (uint32_t)knn;
-        m.stride2 = coreacc ? 2 : 1;
-        m.run_key = st.key;
-        m.run_idx = st.idx;
-        m.run_d1 = st.d1;
-        m.streaming = ctx->knobs.topk_stream;
-        // rows of the band: columns [b0, n) minus themselves (the view's first b0 - col0 columns
-        // reached them turned, from earlier bands)
-        m.keys = (const float *)kband[buf];
-        m.key_stride = (uint64_t)g.nB * m.stride2;
-        m.rows = (uint32_t)(b1 - b0);
-        m.cols = g.nB;
-        m.id_base = (uint32_t)col0;
-        m.skip_below = (uint32_t)c_first;
-        m.state_row_base = (uint32_t)b0;
-        m.self_id_base = (is_cross && !cross.self_rows) ? 0xFFFFFFFFu : (uint32_t)b0;
-        m.seg_bits = ctx->knobs.knn_row_flags ? row_bits[buf] : nullptr;
-        m.seg_bits_stride = (uint32_t)bit_words;
-        HIP_TRY(launch_topk_merge(m, topk_stream));
-        m.seg_bits = nullptr;
-        // rows below the band: the band's samples as their candidates
-        m.keys = (const float *)tband[buf];
-        m.key_stride = (uint64_t)t_stride * m.stride2;
-        m.rows = g.out_t ? (uint32_t)(win_hi - t_first) : 0u;
-        m.cols = (uint32_t)(b1 - b0);
-        m.id_base = (uint32_t)b0;
-        m.skip_below = 0;
-        m.self_id_base = m.state_row_base = (uint32_t)t_first;
-        m.flag = ctx->knobs.knn_row_flags ? flags[buf] + t_first : nullptr;
-        m.flag_value = flag_value;
-        m.seg_bits = ctx->knobs.knn_row_flags ? tbits[buf] + t_first * tbit_words : nullptr;   // (row r of this launch = sample t_first + r)
-        m.seg_bits_stride = (uint32_t)tbit_words;
-        m.seg_shift = 5;
-        HIP_TRY(launch_topk_merge(m, topk_stream));
-        if (overlap) HIP_TRY(hipEventRecord(ctx->knn_topk_done[buf], topk_stream));
+        if (c.overlap) HIP_TRY(hipEventRecord(ctx->knn_topk_done[buf], topk_stream));
         ++it;
     }
-    if (prune) ctx->knn_tile_stages = (s->ss64 + 3) / 4;   // stages of a whole 32 x 128 tile: 4 waves, one chunk each per stage
-    if (overlap && it) {   // the states (and the band buffers) belong to the context's stream again
+    if (P.prune) ctx->knn_tile_stages = (s->ss64 + 3) / 4;   // stages of a whole 32 x 128 tile: 4 waves, one chunk each per stage
+    if (c.overlap && it) {   // the states (and the band buffers) belong to the context's stream again
         HIP_TRY(hipEventRecord(ctx->knn_topk_done[0], topk_stream));
         HIP_TRY(hipStreamWaitEvent(ctx->stream, ctx->knn_topk_done[0], 0));
     }
@@ -473,20 +471,13 @@ static int knn_self_symmetric(skl_ctx *ctx, const skl_sketches *s, const skl_dis
                               size_t band_rows, bool overlap, uint64_t *d_idx, float *d_d0, float *d_d1)
 {
     const size_t n = s->n;
-    const bool coreacc = p->dist_type == SKL_DIST_COREACC;
     const bool ref = ctx->knn_ties == SKL_KNN_TIES_REFERENCE;
     KnnState st;
-    SKL_TRY(knn_state_init(st, n, knn, coreacc, ctx->stream, ref));
+    SKL_TRY(knn_state_init(st, n, knn, p->dist_type == SKL_DIST_COREACC, ctx->stream, ref));
     std::vector<uint32_t> bands((n + band_rows - 1) / band_rows);
     for (size_t b = 0; b < bands.size(); ++b) bands[b] = (uint32_t)b;
-    SKL_TRY(knn_symmetric_bands(ctx, s, p, knn, band_rows, bands, overlap, st));
-    if (ref) {
-        HIP_TRY(launch_refheap_finalize(st.h_key, st.h_id, st.h_d1, st.h_len, (uint32_t)n, (uint32_t)knn, (!coreacc && p->ani) ? 1 : 0,
-                                        d_idx, d_d0, d_d1, ctx->stream));
-    } else {
-        HIP_TRY(launch_topk_finalize(st.key, st.idx, st.d1, n * knn, (!coreacc && p->ani) ? 1 : 0, d_idx, d_d0, d_d1,
-                                     ctx->stream));
-    }
+    SKL_TRY(knn_run_bands(ctx, s, s, p, knn_call(ctx, s, s, p, KNN_SYMMETRIC, knn, band_rows, bands.size(), overlap, st), bands, st));
+    SKL_TRY(knn_finalize(st, 0, n, knn, p, d_idx, d_d0, d_d1, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));   // the running states are freed on return
     return SKL_OK;
 }
@@ -496,18 +487,20 @@ static int knn_self_symmetric(skl_ctx *ctx, const skl_sketches *s, const skl_dis
 // of band i + 1 (VALU bound) fills the other one.  The top-k is the streaming one of the
 // symmetric driver (topk_merge_kernel), fed a whole row at once.
 static int knn_rows_banded(skl_ctx *ctx, const skl_sketches *rows, const skl_sketches *cands,
-                           const skl_dist_params *p, size_t knn, int self_mode, size_t r0, size_t r1,
-                           size_t band_rows, bool overlap, uint64_t *d_idx, float *d_d0, float *d_d1)
+                           const skl_dist_params *p, const KnnRowsCall &rc, size_t band_rows, bool overlap,
+                           uint64_t *d_idx, float *d_d0, float *d_d1)
 {
-    const bool coreacc = p->dist_type == SKL_DIST_COREACC;
+    const size_t knn = rc.knn, r0 = rc.r0, r1 = rc.r1;
+    const int self_mode = rc.self_mode ? 1 : 0;
+    const bool coreacc = rc.coreacc;
     const int mode = coreacc ? MODE_COREACC : MODE_JACCARD;
     const int jout = coreacc ? 0 : (p->ani ? JOUT_ANI_KEY : JOUT_DIST);
     const size_t rec = coreacc ? 2 * sizeof(float) : sizeof(float);
     const size_t n_cand = cands->n;
     void *band[2] = {nullptr, nullptr};
-    SKL_TRY(ctx_scratch(ctx, band_rows * n_cand * rec, &band[0], 0));
+    SKL_TRY(ctx_scratch(ctx, band_rows * n_cand * rec, &band[0], SCRATCH_KEY_BAND));
     band[1] = band[0];
-    if (overlap) SKL_TRY(ctx_scratch(ctx, band_rows * n_cand * rec, &band[1], 3));
+    if (overlap) SKL_TRY(ctx_scratch(ctx, band_rows * n_cand * rec, &band[1], SCRATCH_KEY_BAND_2));
     hipStream_t topk_stream = overlap ? ctx->aux_stream : ctx->stream;
     // Three ways from a band of records to neighbour lists:
     //   * the streaming running top-k (topk_merge_kernel) + finalize: canonical ties, knn <= TOPK_LDS_MAX;
@@ -516,48 +509,26 @@ static int knn_rows_banded(skl_ctx *ctx, const skl_sketches *rows, const skl_ske
     const bool ref_ties = ctx->knn_ties == SKL_KNN_TIES_REFERENCE;
     const bool big = knn > (size_t)TOPK_LDS_MAX;
     const bool streaming_state = !ref_ties && !big;
-    // COLUMN PANELS (round 5): a row-by-row kNN over many candidates -- cross kNN against a large reference set, a row range of
-    // the self kNN -- is fed its candidates in ascending panels of columns instead of all at once: the rows' lists tighten
-    // from panel to panel, and from the second panel on the pair kernel leaves the tiles whose pairs are beyond their ROW's
-    // bound (tile pruning, as in the symmetric driver; the columns have no lists here).  Same lists in either tie rule: a
-    // row still meets its candidates in ascending id.  Single-k keys without a completeness correction, lists that fit the
-    // LDS forms, at least 4 panels of 32 Ki columns and launches large enough for the prunable 32 x 128 tiles.
-    {
-        // (A/B build: SKL_KNN_PANEL forces a panel width -- and lifts the size conditions -- so that tests reach this path on
-        // inputs small enough for the oracle)
-        const size_t forced_panel = (size_t)std::max(0ll, ctx->knobs.knn_panel) / 128 * 128;
-        const size_t panel = forced_panel ? forced_panel : std::max<size_t>(32768, (n_cand / 8 + 127) / 128 * 128);
-        const bool eligible = ctx->knobs.knn_prune && ctx->knobs.knn_row_flags && !coreacc && !(rows->d_comp && cands->d_comp) &&
-                              rows->ss64 <= (size_t)KSLICE_MAX_U16_CHUNKS && !big && knn <= (size_t)REFHEAP_LDS_MAX && forced_kernel(ctx) == 0 &&
-                              (forced_panel ? n_cand > panel : (n_cand >= 4 * panel && (r1 - r0) * panel >= (size_t)(16u << 20)));
-        if (eligible) {
-            // bands of rows whose records of one panel fit a quarter of the budget the caller sized `band_rows` for
-            size_t rows_per = std::max<size_t>(32, std::min<size_t>(r1 - r0, band_rows * n_cand / panel) / 32 * 32);
-            if (ctx->knobs.knn_band_rows) rows_per = std::max<size_t>(1, (size_t)ctx->knobs.knn_band_rows);   // (test knob)
-            rows_per = std::min(rows_per, (size_t)1 << 20);
-            KnnState pst;
-            SKL_TRY(knn_state_init(pst, rows->n, knn, false, ctx->stream, ref_ties));
-            std::vector<uint32_t> bands;
-            for (size_t b = r0 / rows_per; b * rows_per < r1; ++b) bands.push_back((uint32_t)b);
-            KnnCross cross;
-            cross.cols = cands;
-            cross.self_rows = self_mode != 0;
-            cross.row_lo = r0;
-            cross.row_hi = r1;
-            SKL_TRY(prune_stats_reset(ctx));
-            for (size_t c0 = 0; c0 < n_cand; c0 += panel) {
-                SKL_TRY(knn_symmetric_bands(ctx, rows, p, knn, rows_per, bands, overlap && bands.size() > 1, pst, c0, std::min(n_cand, c0 + panel), cross));
-            }
-            const int ani_undo = p->ani ? 1 : 0;
-            if (ref_ties) {
-                HIP_TRY(launch_refheap_finalize(pst.h_key + r0 * knn, pst.h_id + r0 * knn, nullptr, pst.h_len + r0, (uint32_t)(r1 - r0), (uint32_t)knn,
-                                                ani_undo, d_idx, d_d0, d_d1, ctx->stream));
-            } else {
-                HIP_TRY(launch_topk_finalize(pst.key + r0 * knn, pst.idx + r0 * knn, nullptr, (r1 - r0) * knn, ani_undo, d_idx, d_d0, d_d1, ctx->stream));
-            }
-            HIP_TRY(hipStreamSynchronize(ctx->stream));   // the running states are freed on return
-            return SKL_OK;
+    // COLUMN PANELS (knn_plan.hpp plan_knn_panels): the candidates in ascending panels of columns, each a call of the band driver
+    const KnnPanels panels = plan_knn_panels(rc, band_rows);
+    if (panels.eligible) {
+        KnnState pst;
+        SKL_TRY(knn_state_init(pst, rows->n, knn, false, ctx->stream, ref_ties));
+        std::vector<uint32_t> bands;
+        for (size_t b = r0 / panels.rows_per; b * panels.rows_per < r1; ++b) bands.push_back((uint32_t)b);
+        KnnCall call = knn_call(ctx, rows, cands, p, KNN_CROSS_PANEL, knn, panels.rows_per, bands.size(), overlap && bands.size() > 1, pst);
+        call.self_rows = self_mode != 0;
+        call.row_lo = r0;
+        call.row_hi = r1;
+        SKL_TRY(prune_stats_reset(ctx));
+        for (size_t c0 = 0; c0 < n_cand; c0 += panels.panel) {
+            call.win_lo = c0;
+            call.win_hi = std::min(n_cand, c0 + panels.panel);
+            SKL_TRY(knn_run_bands(ctx, rows, cands, p, call, bands, pst));
         }
+        SKL_TRY(knn_finalize(pst, r0, r1, knn, p, d_idx, d_d0, d_d1, ctx->stream));
+        HIP_TRY(hipStreamSynchronize(ctx->stream));   // the running states are freed on return
+        return SKL_OK;
     }
     KnnState st;
     DevBuf big_scratch;
@@ -586,7 +557,7 @@ static int knn_rows_banded(skl_ctx *ctx, const skl_sketches *rows, const skl_ske
             HIP_TRY(hipStreamWaitEvent(topk_stream, ctx->knn_pair_done[buf], 0));
         }
         const size_t o = (b0 - r0) * knn;   // first output item of the band
-        const int ani_undo = (!coreacc && p->ani) ? 1 : 0;
+        const int ani_undo = knn_ani_undo(p);
         if (streaming_state) {
             TopkMergeArgs m;
             memset(&m, 0, sizeof m);
@@ -641,10 +612,7 @@ static int knn_rows_banded(skl_ctx *ctx, const skl_sketches *rows, const skl_ske
         }
         if (overlap) HIP_TRY(hipEventRecord(ctx->knn_topk_done[buf], topk_stream));
     }
-    if (streaming_state) {
-        HIP_TRY(launch_topk_finalize(st.key, st.idx, st.d1, (r1 - r0) * knn, (!coreacc && p->ani) ? 1 : 0, d_idx, d_d0,
-                                     d_d1, topk_stream));
-    }
+    if (streaming_state) SKL_TRY(knn_finalize(st, 0, r1 - r0, knn, p, d_idx, d_d0, d_d1, topk_stream));
     if (overlap) {   // results (and the band buffers) belong to the context's stream again
         HIP_TRY(hipEventRecord(ctx->knn_topk_done[0], topk_stream));
         HIP_TRY(hipStreamWaitEvent(ctx->stream, ctx->knn_topk_done[0], 0));
@@ -668,48 +636,24 @@ static int knn_rows(skl_ctx *ctx, const skl_sketches *rows, const skl_sketches *
         return fail(SKL_ERR_INVALID_ARG, "knn=%zu must be in [1, %zu]", knn, max_knn);
     }
     if (r1 == r0) return SKL_OK;
-    // (no upper bound on knn beyond the candidates there are, as in the reference, lib.rs:379-382 / mod.rs:325: up to
-    // TOPK_LDS_MAX neighbours the lists live in LDS; more go through global memory, row by row)
-    const bool ref_ties = ctx->knn_ties == SKL_KNN_TIES_REFERENCE;
-    const bool big_knn = knn > (size_t)TOPK_LDS_MAX;
-
-    const size_t rec = coreacc ? 2 * sizeof(float) : sizeof(float);
-    // the key band lives only on the device: take up to a quarter of the free HBM (<= 8 GiB)
-    // so that the row-wise top-k kernel has thousands of rows (= workgroups) per launch
+    // band heights, every pair once or row by row, overlap: knn_plan.hpp plan_knn_rows
+    KnnRowsCall rc;
+    rc.n_cand = n_cand;
+    rc.r0 = r0;
+    rc.r1 = r1;
+    rc.knn = knn;
+    rc.self_mode = self_mode != 0;
+    rc.coreacc = coreacc;
+    rc.ref_ties = ctx->knn_ties == SKL_KNN_TIES_REFERENCE;
+    rc.nk = rows->nk;
+    rc.ss64 = rows->ss64;
+    rc.both_comp = rows->d_comp && cands->d_comp;
+    rc.fused_coreacc_ok = fused_coreacc_ok(rows);
+    rc.forced_kernel = forced_kernel(ctx);
     size_t free_b = 0, total_b = 0;
-    size_t band_bytes = BAND_BYTES;
-    if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) {
-        band_bytes = std::max(band_bytes, std::min<size_t>(free_b / 4, 8ull << 30));
-    }
-    size_t band_rows = std::max<size_t>(1, band_bytes / 2 / (n_cand * rec));   // two key bands
-    const size_t forced_band_rows = (size_t)ctx->knobs.knn_band_rows;  // test knob: force several bands
-    if (forced_band_rows) band_rows = forced_band_rows;
-    band_rows = std::min(band_rows, r1 - r0);
-    // The whole self matrix: evaluate each pair once (knn_self_symmetric) when that leaves bands
-    // worth launching -- about 8 of them (7/16 of the pair evaluations saved), each at least 32 M
-    // pairs, within four band buffers of up to half the free HBM (<= 32 GiB; core/accessory keys: <= 96 GiB) together.
-    // (the reference's tie order depends on the ORDER candidates arrive in, ascending j for every row: the symmetric driver
-    // delivers exactly that order, band by band, to a heap that lives in global memory between the bands; lists too long for
-    // the LDS-resident running state go row by row)
-    bool symmetric = self_mode && r0 == 0 && r1 == n_cand && knn_symmetric_ok(rows, p) && !big_knn &&
-                     ctx->knobs.knn_symmetric;   // (SKL_KNN_SYMMETRIC=0: A/B against the row-by-row form)
-    if (symmetric) {
-        size_t budget = band_bytes;
-        // (core/accessory keys -- no tile pruning, whose thresholds want short bands -- take taller bands: the bands' epilogue
-        // finds a column group's slices in L2 for more rows, and there are fewer launches and heap replays: cfg 5 in
-        // core/accessory mode, 704 / 1 408 / 2 048 / 2 816 / 4 096 rows: 25.1 / 24.7 / 24.6 / 24.6 / 24.6 s)
-        const size_t budget_cap = p->dist_type == SKL_DIST_COREACC ? 96ull << 30 : 32ull << 30;
-        if (free_b) budget = std::max(budget, std::min<size_t>(free_b / 2, budget_cap));
-        const size_t want = forced_band_rows ? forced_band_rows : symmetric_band_rows(n_cand, coreacc_rec_with_counts(rows, p), budget, 1);
-        if (want >= n_cand) symmetric = false;
-        else band_rows = want;
-    }
-    if (!symmetric && (big_knn || ref_ties)) {
-        // per-row working arrays in global memory (knn beyond the LDS forms): keep them within 1 GiB
-        const size_t per_row = big_knn ? std::max<size_t>((size_t)topk_items_pitch(knn) * sizeof(uint64_t), 3 * (knn + 1) * sizeof(float)) : 0;
-        if (per_row) band_rows = std::max<size_t>(1, std::min<size_t>(band_rows, (size_t)(1ull << 30) / per_row));
-    }
-    const bool overlap = ctx->knobs.knn_overlap && band_rows < r1 - r0;
+    if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) rc.free_bytes = free_b;
+    rc.knobs = ctx->knobs;
+    const KnnRowsPlan plan = plan_knn_rows(rc);
 
     // device staging for host-destined results
     uint64_t *d_idx = out_idx;
@@ -717,16 +661,16 @@ static int knn_rows(skl_ctx *ctx, const skl_sketches *rows, const skl_sketches *
     const size_t items = (r1 - r0) * knn;
     if (!out_on_device) {
         void *stage = nullptr;
-        SKL_TRY(ctx_scratch(ctx, items * (sizeof(uint64_t) + 2 * sizeof(float)), &stage, 2));
+        SKL_TRY(ctx_scratch(ctx, items * (sizeof(uint64_t) + 2 * sizeof(float)), &stage, SCRATCH_KNN_STAGING));
         d_idx = (uint64_t *)stage;
         d_d0 = (float *)(d_idx + items);
         d_d1 = d_d0 + items;
     }
     SKL_TRY(prune_stats_reset(ctx));
-    if (symmetric) {
-        SKL_TRY(knn_self_symmetric(ctx, rows, p, knn, band_rows, overlap, d_idx, d_d0, d_d1));
+    if (plan.symmetric) {
+        SKL_TRY(knn_self_symmetric(ctx, rows, p, knn, plan.band_rows, plan.overlap, d_idx, d_d0, d_d1));
     } else {
-        SKL_TRY(knn_rows_banded(ctx, rows, cands, p, knn, self_mode, r0, r1, band_rows, overlap, d_idx, d_d0, d_d1));
+        SKL_TRY(knn_rows_banded(ctx, rows, cands, p, rc, plan.band_rows, plan.overlap, d_idx, d_d0, d_d1));
     }
     if (!out_on_device) {
         HIP_TRY(hipMemcpyAsync(out_idx, d_idx, items * sizeof(uint64_t), hipMemcpyDeviceToHost,
@@ -784,11 +728,8 @@ extern "C" int skl_self_dists_knn(skl_ctx *ctx, const skl_sketches *s, const skl
 extern "C" size_t skl_knn_band_rows(const skl_sketches *s, const skl_dist_params *p, size_t n_participants)
 {
     if (!s || !p || s->n == 0) return 0;
-    const size_t rec = coreacc_rec_with_counts(s, p);
-    const long long forced = s->ctx->knobs.knn_band_rows;   // test knob (the same for every participant)
-    if (forced > 0) return std::min<size_t>(s->n, (size_t)forced);
-    // a fixed budget (no free-memory query): every participant must arrive at the same number
-    return std::min(s->n, symmetric_band_rows(s->n, rec, 32ull << 30, n_participants));
+    const size_t rec = coreacc_rec_with_counts(p->dist_type == SKL_DIST_COREACC, s->nk, fused_coreacc_ok(s));
+    return knn_shared_band_rows(s->n, rec, s->ctx->knobs, n_participants);
 }
 
 extern "C" int skl_self_dists_knn_partial(skl_ctx *ctx, const skl_sketches *s, const skl_dist_params *p, size_t knn,
@@ -823,7 +764,7 @@ extern "C" int skl_self_dists_knn_partial(skl_ctx *ctx, const skl_sketches *s, c
     SKL_TRY(knn_state_init(st, n, knn, coreacc, ctx->stream));
     SKL_TRY(prune_stats_reset(ctx));
     const bool overlap = ctx->knobs.knn_overlap && list.size() > 1;
-    SKL_TRY(knn_symmetric_bands(ctx, s, p, knn, band_rows, list, overlap, st));
+    SKL_TRY(knn_run_bands(ctx, s, s, p, knn_call(ctx, s, s, p, KNN_SYMMETRIC, knn, band_rows, list.size(), overlap, st), list, st));
     const hipMemcpyKind kind = out_on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
     const size_t items = n * knn;
     HIP_TRY(hipMemcpyAsync(state_key, st.key, items * sizeof(uint32_t), kind, ctx->stream));
@@ -882,15 +823,17 @@ static int knn_window_impl(skl_ctx *ctx, const skl_sketches *s, const skl_dist_p
     const std::vector<uint32_t> one{(uint32_t)band};
     // (the counters run on over the bands of a window: skl_ctx_knn_prune_stats reports everything since the last kNN
     // call of another kind -- no read-back, no reset here: this call must not stall the hand-over of the heaps)
-    KnnCross form;   // (the symmetric form)
+    KnnCall call = knn_call(ctx, s, s, p, KNN_WINDOW, knn, band_rows, one.size(), false, st);
+    call.win_lo = col_lo;
+    call.win_hi = col_hi;
     // Every list the band's TURNED copy reaches -- the window's rows [max(b1, col_lo), col_hi) -- holds knn candidates: bands
     // 0 .. band - 1 of this call's sequence gave each of them band_rows >= knn, on this participant, so this holds for heaps that
     // started empty on the window (the _logged form) as well.  It says nothing of the band's OWN rows: below col_lo they start
     // empty under logs.  It need not: it only feeds plain_marks_nothing, which epilogue.hip applies to the turned side, while
     // the own rows' records are stored and marked by the row-side test against the row's own threshold (thr_row: "not full"
     // lets a (1, 1) in), so a row with fewer than knn candidates still takes its plain pairs.
-    form.lists_hold_knn = band >= 1 && band_rows >= knn;
-    return knn_symmetric_bands(ctx, s, p, knn, band_rows, one, false, st, col_lo, col_hi, form);
+    call.lists_hold_knn = band >= 1 && band_rows >= knn;
+    return knn_run_bands(ctx, s, s, p, call, one, st);
 }
 
 // Empty heaps (h_len = 0, thr = "not full") for rows [row_begin, row_end) of caller-owned state arrays.
