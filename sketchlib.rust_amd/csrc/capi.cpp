@@ -18,6 +18,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <map>
+#include <memory>
 #include <mutex>
 #include <optional>
 #include <set>
@@ -422,15 +423,7 @@ Knobs read_knobs()
 int ab_forced_log_variant() { return (int)std::max(-2ll, std::min(1ll, env_int("SKL_FORCE_LOG_VARIANT", -2))); }   // -2: not forced
 #endif
 
-// XCDs the device presents as one: an MI355X XCD has 32 CUs, so an unpartitioned (SPX) part shows 256 CUs = 8 XCDs, a CPX
-// partition 32 CUs = 1.  The tile order deals workgroups to XCDs by blockIdx mod that number; SKL_XCDS forces it (tests).
-uint32_t ctx_xcd_shift(const skl_ctx *ctx)
-{
-    int x = ctx->knobs.xcds > 0 ? ctx->knobs.xcds : ctx->n_cu / 32;
-    uint32_t shift = 0;
-    while (shift < 3u && (2 << shift) <= x) ++shift;
-    return shift;
-}
+uint32_t ctx_xcd_shift(const skl_ctx *ctx) { return plan_xcd_shift(ctx->n_cu, ctx->knobs.xcds); }
 
 int forced_kernel(const skl_ctx *ctx)
 {
@@ -444,79 +437,42 @@ int forced_kernel(const skl_ctx *ctx)
 #endif
 }
 
-// One tile computation.  Product library: the chunk-split kernel (pair_kslice.hip: 16 x 128 tiles,
-// chunks split over the 4 waves, rows by LDS DMA; one workgroup per (tile, k) for small launches
-// and for single-k Jaccard, all k + fused regression otherwise) and, for the shapes it does not
-// take, pair_ksplit.hip.  The A/B build adds the round-2/3 forms of the two tile shapes behind
-// SKL_KSLICE_SHAPE and SKL_KERNEL=ksplit.
+// One launch of the pair kernel: which tile shape and form it takes is plan_pair_shape()'s answer (dense_plan.hpp); whether the
+// chunk-split kernel takes the launch is the kernel's own knowledge (kslice_supported, pair_kslice.hip).
 static hipError_t dispatch_pair_kernel(skl_ctx *ctx, const PairArgs &args_in, int mode, hipStream_t stream)
 {
     PairArgs args = args_in;
     args.group_span = (uint32_t)ctx->knobs.group_span;
     args.xcd_shift = ctx_xcd_shift(ctx);
     args.inline_prefix_ok = ctx->knobs.inline_prefix ? 1u : 0u;
-    const uint32_t n_xcd = 1u << args.xcd_shift;
-    static const char *mode_names[] = {"COUNTS", "JACCARD", "COREACC"};
-    const std::string m = mode_names[mode];
-    std::string *name = &ctx->last_kernel;
-    TileScratch &tiles = ctx->tile_scratch;
-    const uint64_t rows = args.row_end - args.row_begin;
-    const uint64_t pairs = args.self_mode ? rows * args.nB / 2 : rows * (uint64_t)args.nB;
-    const bool small = pairs < (8ull << 20);
-    // 165 = 16 x 128 tiles in the 128-register form (4 waves per SIMD): +3.5 % at n = 16 000 over the
-    // 141-register form 162 (3 waves), equal at n = 1 000 (profiles/r02_ab_tight.jsonl)
-    // 325 = 32 x 128 tiles (130-168 registers, 3 waves per SIMD) for launches of at least
-    // tile32_min pair x k-mer-length evaluations (~4 096 units of 32 x 128): every column register is
-    // used against 32 rows instead of 16, which halves the lane-slab traffic per pair -- HBM bytes per
-    // launch at n = 16 000 fall from 59.5 GB to 32.0 GB and the kernel gains 1.5-6 %
-    // (profiles/r02_tile32_*.md); smaller launches lose to the coarser tail (n = 1 000: +32 %).
-    int shape = 165, ksplit_rows = 8;   // 8 >= 4 rows from n = 1000 up once XCDs are balanced
-    {
-        const uint64_t k_walked = mode == MODE_JACCARD ? 1u : args.k_count;
-        if (ctx->knobs.tile32_min >= 0 && pairs * k_walked >= (uint64_t)ctx->knobs.tile32_min) shape = 325;
-        if (args.mid_band) shape = 325;   // the mid-band rule (dense_plan.hpp): 32-row tiles with the last round cut in 2
-    }
+    PairLaunch a;
+    a.mode = mode;
+    a.self_mode = args.self_mode != 0;
+    a.rows = args.row_end - args.row_begin;
+    a.nB = args.nB;
+    a.k_count = args.k_count;
+    a.ss64 = args.ss64;
+    a.k_sliced = args.k_sliced != 0;
+    a.mid_band = args.mid_band != 0;
+    a.tail_slices = args.tail_slices;
+    a.n_cu = ctx->n_cu;
+    a.xcd_shift = args.xcd_shift;
+    a.knobs = ctx->knobs;
 #ifdef SKL_AB
-    const Knobs &kn = ctx->knobs;
-    if (kn.kslice_shape) shape = kn.kslice_shape;
-    if (kn.ksplit_rows) ksplit_rows = kn.ksplit_rows;
-    const bool try_kslice = kn.kernel != 3;
-    const int ablate = kn.kslice_ablate;
-#else
-    const bool try_kslice = true;
-    const int ablate = 0;
+    a.ab_build = true;
+    a.ab_kernel = ctx->knobs.kernel;
+    a.ab_kslice_shape = ctx->knobs.kslice_shape;
+    a.ab_ksplit_rows = ctx->knobs.ksplit_rows;
+    a.ab_kslice_ablate = ctx->knobs.kslice_ablate;
 #endif
-    args.no_half_tiles = ctx->knobs.half_tiles ? 0u : 1u;
-    // workgroups resident per CU: 4 for every shipped form (the A/B build's 3-wave all-k 32-row form: 3)
-    // (sketches beyond 65 535 bins: the k-sliced forms only -- they walk a k-mer length in segments, pair_kslice_walk.inc)
-    const bool big_sketch = args.ss64 > (uint32_t)KSLICE_MAX_U16_CHUNKS;
-    const bool sliced_launch = mode == MODE_JACCARD || (mode == MODE_COUNTS && (small || args.k_sliced || big_sketch));
-    const uint32_t wg_per_cu = ((shape == 3255 && !sliced_launch) || (shape == 3254 && sliced_launch)) ? 3u : 4u;
-    args.round_size = ctx->knobs.round_priority ? wg_per_cu * (uint32_t)ctx->n_cu / n_xcd : 0u;
-    if (args.tail_slices > 1u) {
-        // tail-sliced one-workgroup-per-unit launch: two planes whatever kernel ends up running (a
-        // kernel without the slices leaves plane 1 as it found it: zero)
-        args.tail_resident = wg_per_cu * (uint32_t)ctx->n_cu / n_xcd;
-    }
-    if (try_kslice) {
-        // single-k Jaccard: the sliced and the all-k form are the same work, the sliced one
-        // compiles to fewer registers; core/acc arrives here as MODE_COUNTS from dense_band when sliced
-        const bool sliced = sliced_launch;
-        if (kslice_supported(args, mode, sliced)) {
-            const int jl = (shape == 165 || shape == 325 || shape > 1000) ? 2 : shape % 10;
-            const int rr = shape > 1000 ? shape / 100 : shape / 10;
-            *name = "skl::pair_kernel_kslice<R=" + std::to_string(rr) + ", JL=" + std::to_string(jl) +
-                    ", " + m + (sliced ? ", k-sliced" : ", all k") + ((shape == 165 || shape == 325 || shape > 1000) ? ", tight" : "") + "> (" +
-                    std::to_string(rr) + "x" + std::to_string(jl * 64) + " tiles, chunks split over 4 waves" +
-                    (big_sketch ? "; segments of " + std::to_string(KSLICE_SEG_CHUNKS) + " chunks" : "") +
-                    (sliced && mode == MODE_COUNTS && args.tail_slices > 1u
-                         ? "; " + std::to_string(args.tail_slices) + " chunk slices per unit in the last round of workgroups" : "") + ")";
-            return launch_pair_kernel_kslice(args, mode, shape, sliced, ablate, tiles, stream);
-        }
-    }
-    *name = "skl::pair_kernel_ksplit<R=" + std::to_string(ksplit_rows) + ", " + m + "> (" + std::to_string(ksplit_rows) +
-            "x64 tiles, chunks split over 4 waves)";
-    return launch_pair_kernel_ksplit(args, mode, ksplit_rows, tiles, stream);
+    const PairShape s = plan_pair_shape(a);
+    args.no_half_tiles = s.no_half_tiles ? 1u : 0u;
+    args.round_size = s.round_size;
+    if (args.tail_slices > 1u) args.tail_resident = s.tail_resident;
+    const bool kslice = s.try_kslice && kslice_supported(args, mode, s.sliced_launch);
+    ctx->last_kernel = pair_kernel_name(s, kslice);
+    if (kslice) return launch_pair_kernel_kslice(args, mode, s.shape, s.sliced_launch, s.ablate, ctx->tile_scratch, stream);
+    return launch_pair_kernel_ksplit(args, mode, s.ksplit_rows, ctx->tile_scratch, stream);
 }
 
 // Launch the pair kernel bracketed by HIP events on the context's stream.
@@ -932,37 +888,6 @@ int fill_args(const skl_sketches *rows, const skl_sketches *cols, const skl_dist
     return SKL_OK;
 }
 
-// EARLY BREAK.  core_acc_dist leaves its loop over the k-mer lengths at the first one whose ln J lies below the tolerance
-// (jaccard.rs:89-91: J = 0, i.e. no more shared bins than chance -- expected_samebits, :26-31) and a fit over fewer than three
-// lengths is (1, 1) (:117): a pair that fails the test at one of its first lengths is decided by them alone, and between
-// unrelated genomes that is nearly every pair (a chance match at each of three lengths: 1.1 % of pairs at 4 096 bins,
-// 0.2-0.4 % at 2 048).  The counts + epilogue form can then count only the first ke lengths and let the epilogue complete the
-// pairs still in the running (epilogue.hip).  Whether that pays depends on the data -- completing a pair costs EB_COST x what
-// the tile kernel spends on a pair and length (a whole column slice read for ONE pair), and between close relatives every
-// pair stays in the running -- so the first dense call of a slab against a column slab SAMPLES the pair space: it is cut
-// into blocks of (row >> shift, column >> shift) sample ids (up to 64 x 64 of them, each a multiple of 256 samples), a few
-// dozen pairs of every block run the reference's loop, and every block takes the ke of {2, 3, 4} that minimises
-//     ke + EB_COST x share_alive(ke)      if that is at most 0.9 x nk,
-// else every length.  A database that is half one species therefore takes the early break between the species and skips
-// it within (round 5 decided once per slab pair).  Blocks of one mind give a plain launch; otherwise the pair kernel's
-// (tile, k index) workgroups look their block up and leave when k index >= its ke.
-// EB_COST, measured (profiles/r06_early_break_forced_lengths.md: whole calls with 2 / 3 lengths forced, T(3) - T(2) = one length's
-// kernel time - EB_COST x the difference of the alive shares): 15-22.  Beyond 65 535 bins a completion is a run of thousands of
-// dependent trips of one wave and comes to ~60: there the early break is taken only where hardly a pair stays in the running.
-// Pair spaces large enough for the blocked epilogue order (dense_plan.hpp) complete a pair for ~12-15: cfg 3 with 2 / 3 lengths 642 / 733
-// ms, n = 16 000 17.2 / 19.3.
-constexpr double EB_COST = 20.0, EB_COST_BLOCKED = 12.0, EB_COST_BIG = 60.0;
-static double eb_cost_of(const skl_sketches *rows, const skl_sketches *cols, int self_mode)
-{
-    if (rows->ss64 > (size_t)KSLICE_MAX_U16_CHUNKS) return EB_COST_BIG;
-    const uint64_t pairs = self_mode ? (uint64_t)rows->n * (rows->n - 1) / 2 : (uint64_t)rows->n * cols->n;
-    return pairs >= (48ull << 20) ? EB_COST_BLOCKED : EB_COST;
-}
-
-constexpr uint32_t EB_BLOCKS_MAX = 64;      // blocks per side
-constexpr uint32_t EB_SAMPLES_MIN = 128;    // sampled pairs per block
-constexpr uint32_t EB_SAMPLES_TOTAL = 4096; // ... and at least this many in all
-
 static std::atomic<uint64_t> g_next_gen{1};
 uint64_t next_generation() { return g_next_gen.fetch_add(1); }
 
@@ -972,6 +897,9 @@ static void free_plan(EbPlan *p)
     if (p->d_block_ke) (void)hipFree(p->d_block_ke);
     delete p;
 }
+struct EbPlanFree {
+    void operator()(EbPlan *p) const { free_plan(p); }
+};
 
 void free_plans(skl_ctx *ctx)
 {
@@ -980,100 +908,16 @@ void free_plans(skl_ctx *ctx)
     ctx->eb_last_plan = nullptr;
 }
 
-// ke of {2, 3, 4} with the lowest modelled cost for a histogram of `total` sampled pairs (hist[m]: pairs that pass the test at
-// exactly their first m lengths), or 0 when counting every length is cheaper.  `prior` (9 shares, or null) and its weight:
-// the block's estimate is pulled towards the pooled sample of the blocks that take the early break -- 128 pairs a block cannot
-// tell a 5 % share from a 9 % one, ten thousand can -- so that only a block that really differs decides differently.
-static int best_lengths(const uint32_t *hist, uint32_t total, size_t nk, double eb_cost, double *share_out, const double *prior = nullptr,
-                        double weight = 0.0, int preferred = 0)
+// The early break's sample: `g.samples` pairs of every block run the reference's loop on the device; *hist = [block][EB_HIST]
+// pairs that pass the test at exactly their first m lengths.
+static int eb_sample(skl_ctx *ctx, const skl_sketches *rows, const skl_sketches *cols, double cutoff, const EbGeometry &g, std::vector<uint32_t> *hist)
 {
-    int best_ke = 0;
-    double best = 0.9 * (double)nk, cost_of[5] = {0, 0, 0, 0, 0};
-    if (total == 0) return 0;
-    // (two lengths decide nothing by themselves -- a fit needs three -- but a pair that fails the test at one of them is
-    // decided all the same: (1, 1); ke = 2 leaves more pairs to complete and pays where few share a bin at all: 2 048 bins)
-    for (int ke = 2; ke <= 4 && ke < (int)nk; ++ke) {
-        double still = 0.0, prior_still = 0.0;
-        for (int m = ke; m <= 8; ++m) {
-            still += hist[m];
-            if (prior) prior_still += prior[m];
-        }
-        const double share = (still + weight * prior_still) / ((double)total + weight), cost = (double)ke + eb_cost * share;
-        cost_of[ke] = cost;
-        if (cost <= best) {
-            best = cost;
-            best_ke = ke;
-            if (share_out) *share_out = share;
-        }
-    }
-    // (the blocks' common choice stands unless this block's own is clearly better: the costs of 2 and 3 lengths are often a
-    // quarter of a length apart, and a plan whose blocks disagree pays for its table)
-    if (preferred >= 2 && preferred <= 4 && preferred < (int)nk && best_ke != preferred && cost_of[preferred] <= 0.9 * (double)nk &&
-        cost_of[preferred] <= best + 0.5) {
-        best_ke = preferred;
-    }
-    return best_ke;
-}
-
-int early_break_plan(skl_ctx *ctx, const skl_sketches *rows, const skl_sketches *cols, int self_mode, double cutoff, const EbPlan **out)
-{
-    *out = nullptr;
-    const int knob = ctx->knobs.early_break;
-    if (knob == 0 || rows->nk < 3 || rows->nk > 8) return SKL_OK;
-    if (rows->n * cols->n < 65536) return SKL_OK;
-    if (!ctx->eb_counter) {
-        HIP_TRY(hipMalloc((void **)&ctx->eb_counter, 1024 * sizeof(uint32_t)));   // 1 024 counter slots (diagnostic)
-        HIP_TRY(hipMemsetAsync(ctx->eb_counter, 0, 1024 * sizeof(uint32_t), ctx->stream));
-    }
     const bool has_comp = rows->d_comp != nullptr && cols->d_comp != nullptr;
-    for (const EbPlan *p : ctx->eb_plans) {
-        if (p->rows_gen == rows->gen && p->cols_gen == cols->gen && p->self_mode == self_mode && p->knob == knob && (!has_comp || p->cutoff == cutoff)) {
-            *out = p;
-            return SKL_OK;
-        }
-    }
-    EbPlan *plan = new EbPlan();
-    plan->rows_gen = rows->gen;
-    plan->cols_gen = cols->gen;
-    plan->self_mode = self_mode;
-    plan->cutoff = cutoff;
-    plan->knob = knob;
-    auto keep = [&]() {
-        if (ctx->eb_plans.size() >= 8) {
-            // (nothing in flight may still read the oldest plan's table: the streams are drained before it goes)
-            if (ctx->eb_plans.front()->d_block_ke != nullptr) {
-                (void)hipStreamSynchronize(ctx->stream);
-                if (ctx->epi_stream) (void)hipStreamSynchronize(ctx->epi_stream);
-            }
-            if (ctx->eb_last_plan == ctx->eb_plans.front()) ctx->eb_last_plan = nullptr;
-            free_plan(ctx->eb_plans.front());
-            ctx->eb_plans.erase(ctx->eb_plans.begin());
-        }
-        ctx->eb_plans.push_back(plan);
-        *out = plan;
-    };
-    if (knob >= 2) {   // forced (A/B build, tests)
-        plan->lengths = knob < (int)rows->nk ? knob : 0;
-        keep();
-        return SKL_OK;
-    }
-    // blocks: a power of two of samples per side, at least 256, at most EB_BLOCKS_MAX per side
-    auto shift_for = [](size_t n) {
-        uint32_t sh = 8;
-        while (((n + ((size_t)1 << sh) - 1) >> sh) > EB_BLOCKS_MAX) ++sh;
-        return sh;
-    };
-    plan->shift_r = shift_for(rows->n);
-    plan->shift_c = self_mode ? plan->shift_r : shift_for(cols->n);
-    plan->blk_rows = (uint32_t)((rows->n + ((size_t)1 << plan->shift_r) - 1) >> plan->shift_r);
-    plan->blk_cols = (uint32_t)((cols->n + ((size_t)1 << plan->shift_c) - 1) >> plan->shift_c);
-    const uint32_t n_blocks = plan->blk_rows * plan->blk_cols;
-    const uint32_t live_blocks = self_mode ? plan->blk_rows * (plan->blk_rows + 1) / 2 : n_blocks;
-    const uint32_t samples = std::max(EB_SAMPLES_MIN, (EB_SAMPLES_TOTAL + live_blocks - 1) / live_blocks);
     SKL_TRY(ensure_ytab(rows));
     DevBuf d_hist;
-    HIP_TRY(hipMalloc(&d_hist.p, (size_t)n_blocks * 9 * sizeof(uint32_t)));
-    HIP_TRY(hipMemsetAsync(d_hist.p, 0, (size_t)n_blocks * 9 * sizeof(uint32_t), ctx->stream));
+    hist->assign((size_t)g.n_blocks() * EB_HIST, 0u);
+    HIP_TRY(hipMalloc(&d_hist.p, hist->size() * sizeof(uint32_t)));
+    HIP_TRY(hipMemsetAsync(d_hist.p, 0, hist->size() * sizeof(uint32_t), ctx->stream));
     EbSampleArgs sa;
     memset(&sa, 0, sizeof sa);
     sa.rows_ref = rows->d_rows;
@@ -1082,12 +926,12 @@ int early_break_plan(skl_ctx *ctx, const skl_sketches *rows, const skl_sketches 
     sa.n_cols = (uint32_t)cols->n;
     sa.nk = (uint32_t)rows->nk;
     sa.ss64 = (uint32_t)rows->ss64;
-    sa.self_mode = (uint32_t)self_mode;
-    sa.samples = samples;
-    sa.blk_shift_r = plan->shift_r;
-    sa.blk_shift_c = plan->shift_c;
-    sa.blk_rows = plan->blk_rows;
-    sa.blk_cols = plan->blk_cols;
+    sa.self_mode = g.self_mode ? 1u : 0u;
+    sa.samples = g.samples;
+    sa.blk_shift_r = g.shift_r;
+    sa.blk_shift_c = g.shift_c;
+    sa.blk_rows = g.blk_rows;
+    sa.blk_cols = g.blk_cols;
     sa.min_alive = rows->min_alive;
     sa.has_comp = has_comp ? 1 : 0;
     if (has_comp) {
@@ -1101,64 +945,64 @@ int early_break_plan(skl_ctx *ctx, const skl_sketches *rows, const skl_sketches 
     sa.tolerance = std::log(2.0 / (double)((rows->ss64 * 64ull) * 64ull));  // jaccard.rs:75
     sa.hist = (uint32_t *)d_hist.p;
     HIP_TRY(launch_early_break_sample(sa, ctx->stream));
-    std::vector<uint32_t> hist((size_t)n_blocks * 9);
-    HIP_TRY(hipMemcpyAsync(hist.data(), d_hist.p, hist.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(hist->data(), d_hist.p, hist->size() * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
-    // the pooled decision (the kNN drivers' and the one-block case's)
-    uint32_t pooled[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0}, pooled_n = 0;
-    for (uint32_t b = 0; b < n_blocks; ++b) {
-        for (int m = 0; m <= 8; ++m) {
-            pooled[m] += hist[(size_t)b * 9 + m];
-            pooled_n += hist[(size_t)b * 9 + m];
+    return SKL_OK;
+}
+
+// The decision for a slab pair (eb_plan.hpp): applicable? -> kept from an earlier call? -> forced, or sampled and decided -> kept.
+int early_break_plan(skl_ctx *ctx, const skl_sketches *rows, const skl_sketches *cols, int self_mode, double cutoff, const EbPlan **out)
+{
+    *out = nullptr;
+    const int knob = ctx->knobs.early_break;
+    if (!eb_applicable(knob, rows->nk, rows->n, cols->n)) return SKL_OK;
+    if (!ctx->eb_counter) {
+        HIP_TRY(hipMalloc((void **)&ctx->eb_counter, 1024 * sizeof(uint32_t)));   // 1 024 counter slots (diagnostic)
+        HIP_TRY(hipMemsetAsync(ctx->eb_counter, 0, 1024 * sizeof(uint32_t), ctx->stream));
+    }
+    const bool has_comp = rows->d_comp != nullptr && cols->d_comp != nullptr;
+    for (const EbPlan *p : ctx->eb_plans) {
+        if (p->rows_gen == rows->gen && p->cols_gen == cols->gen && p->self_mode == self_mode && p->knob == knob && (!has_comp || p->cutoff == cutoff)) {
+            *out = p;
+            return SKL_OK;
         }
     }
-    const double eb_cost = eb_cost_of(rows, cols, self_mode);
-    plan->lengths = best_lengths(pooled, pooled_n, rows->nk, eb_cost, &plan->alive_share);
-    if (live_blocks > 1) {
-        // per block.  Pass 1: every block's own sample decides whether it takes the early break at all; pass 2: the blocks that
-        // do are pooled, and every block decides again with its estimate pulled towards that pool (weight: one block's sample).
-        const uint8_t all = (uint8_t)rows->nk;
-        std::vector<uint8_t> ke(n_blocks, all);
-        std::vector<uint32_t> tot(n_blocks, 0u);
-        double cold[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0}, cold_n = 0.0;
-        for (uint32_t b = 0; b < n_blocks; ++b) {
-            for (int m = 0; m <= 8; ++m) tot[b] += hist[(size_t)b * 9 + m];
-            if (best_lengths(&hist[(size_t)b * 9], tot[b], rows->nk, eb_cost, nullptr) > 0) {
-                for (int m = 0; m <= 8; ++m) cold[m] += hist[(size_t)b * 9 + m];
-                cold_n += tot[b];
-            }
-        }
-        int common = 0;
-        if (cold_n > 0.0) {
-            uint32_t cold_u[9];
-            for (int m = 0; m <= 8; ++m) cold_u[m] = (uint32_t)std::min(cold[m], 4.0e9);
-            common = best_lengths(cold_u, (uint32_t)std::min(cold_n, 4.0e9), rows->nk, eb_cost, nullptr);
-            for (int m = 0; m <= 8; ++m) cold[m] /= cold_n;
-        }
-        bool differ = false;
-        uint8_t first = 0;
-        for (uint32_t b = 0; b < n_blocks; ++b) {
-            if (self_mode && b % plan->blk_cols < b / plan->blk_cols) continue;   // below the diagonal: no pair
-            const int own = best_lengths(&hist[(size_t)b * 9], tot[b], rows->nk, eb_cost, nullptr, cold_n > 0.0 ? cold : nullptr, cold_n > 0.0 ? (double)samples : 0.0, common);
-            ke[b] = own > 0 ? (uint8_t)own : all;
-            if (first == 0) first = ke[b];
-            else if (ke[b] != first) differ = true;
-        }
-        if (differ) {
-            if (self_mode) {   // (mirror: a tile on the diagonal may look a block up from either side)
-                for (uint32_t r = 0; r < plan->blk_rows; ++r) {
-                    for (uint32_t c = 0; c < r && c < plan->blk_cols; ++c) ke[(size_t)r * plan->blk_cols + c] = ke[(size_t)c * plan->blk_cols + r];
-                }
-            }
-            plan->mixed = true;
-            plan->block_ke = ke;
-            HIP_TRY(hipMalloc((void **)&plan->d_block_ke, ke.size()));
-            HIP_TRY(hipMemcpy(plan->d_block_ke, ke.data(), ke.size(), hipMemcpyHostToDevice));
-        } else {
-            plan->lengths = first == all ? 0 : (int)first;   // one mind: a plain launch
-        }
+    EbGeometry geo;
+    EbDecision decision;
+    if (knob >= 2) {
+        decision = eb_forced(knob, rows->nk);
+    } else {
+        geo = eb_geometry(rows->n, cols->n, self_mode != 0);
+        std::vector<uint32_t> hist;
+        SKL_TRY(eb_sample(ctx, rows, cols, cutoff, geo, &hist));
+        decision = eb_decide(geo, rows->nk, eb_cost((uint32_t)rows->ss64, rows->n, cols->n, self_mode != 0), hist.data());
     }
-    keep();
+    // (owned here until it is kept: an upload that fails takes the plan and its table with it)
+    std::unique_ptr<EbPlan, EbPlanFree> plan(new EbPlan());
+    plan->rows_gen = rows->gen;
+    plan->cols_gen = cols->gen;
+    plan->self_mode = self_mode;
+    plan->cutoff = cutoff;
+    plan->knob = knob;
+    plan->geo = geo;
+    plan->decision = std::move(decision);
+    if (plan->decision.mixed) {
+        const std::vector<uint8_t> &ke = plan->decision.block_ke;
+        HIP_TRY(hipMalloc((void **)&plan->d_block_ke, ke.size()));
+        HIP_TRY(hipMemcpy(plan->d_block_ke, ke.data(), ke.size(), hipMemcpyHostToDevice));
+    }
+    if (ctx->eb_plans.size() >= EB_PLANS_KEPT) {
+        // (nothing in flight may still read the oldest plan's table: the streams are drained before it goes)
+        if (ctx->eb_plans.front()->d_block_ke != nullptr) {
+            (void)hipStreamSynchronize(ctx->stream);
+            if (ctx->epi_stream) (void)hipStreamSynchronize(ctx->epi_stream);
+        }
+        if (ctx->eb_last_plan == ctx->eb_plans.front()) ctx->eb_last_plan = nullptr;
+        free_plan(ctx->eb_plans.front());
+        ctx->eb_plans.erase(ctx->eb_plans.begin());
+    }
+    ctx->eb_plans.push_back(plan.get());
+    *out = plan.release();
     return SKL_OK;
 }
 
@@ -1169,7 +1013,7 @@ int early_break_lengths(skl_ctx *ctx, const skl_sketches *rows, const skl_sketch
     if (rows->d_comp != nullptr || cols->d_comp != nullptr || rows->ss64 > (size_t)KSLICE_MAX_U16_CHUNKS) return SKL_OK;
     const EbPlan *plan = nullptr;
     SKL_TRY(early_break_plan(ctx, rows, cols, self_mode, 0.0, &plan));
-    if (plan) *lengths = plan->lengths;
+    if (plan) *lengths = plan->decision.lengths;
     return SKL_OK;
 }
 
@@ -1178,21 +1022,23 @@ extern "C" int skl_ctx_early_break_blocks(skl_ctx *ctx, uint32_t *blk_rows, uint
 {
     SKL_TRY(ctx_bind(ctx));
     const EbPlan *p = ctx->eb_last_plan;
-    if (blk_rows) *blk_rows = p ? p->blk_rows : 0u;
-    if (blk_cols) *blk_cols = p ? p->blk_cols : 0u;
-    if (shift_rows) *shift_rows = p ? p->shift_r : 0u;
-    if (shift_cols) *shift_cols = p ? p->shift_c : 0u;
-    if (pooled_lengths) *pooled_lengths = p ? p->lengths : 0;
-    if (mixed) *mixed = p && p->mixed ? 1 : 0;
-    if (p && p->mixed && block_lengths) {
-        if (capacity < p->block_ke.size()) return fail(SKL_ERR_INVALID_ARG, "skl_ctx_early_break_blocks: %zu blocks, room for %zu", p->block_ke.size(), capacity);
-        memcpy(block_lengths, p->block_ke.data(), p->block_ke.size());
+    if (blk_rows) *blk_rows = p ? p->geo.blk_rows : 0u;
+    if (blk_cols) *blk_cols = p ? p->geo.blk_cols : 0u;
+    if (shift_rows) *shift_rows = p ? p->geo.shift_r : 0u;
+    if (shift_cols) *shift_cols = p ? p->geo.shift_c : 0u;
+    if (pooled_lengths) *pooled_lengths = p ? p->decision.lengths : 0;
+    if (mixed) *mixed = p && p->decision.mixed ? 1 : 0;
+    if (p && p->decision.mixed && block_lengths) {
+        const std::vector<uint8_t> &ke = p->decision.block_ke;
+        if (capacity < ke.size()) return fail(SKL_ERR_INVALID_ARG, "skl_ctx_early_break_blocks: %zu blocks, room for %zu", ke.size(), capacity);
+        memcpy(block_lengths, ke.data(), ke.size());
     }
     return SKL_OK;
 }
 
 static_assert(PLAN_MODE_COUNTS == MODE_COUNTS && PLAN_MODE_JACCARD == MODE_JACCARD && PLAN_MODE_COREACC == MODE_COREACC &&
-              PLAN_MAX_U16_CHUNKS == (uint32_t)KSLICE_MAX_U16_CHUNKS, "dense_plan.hpp restates these constants of kernels.h");
+              PLAN_MAX_U16_CHUNKS == (uint32_t)KSLICE_MAX_U16_CHUNKS && PLAN_SEG_CHUNKS == (uint32_t)KSLICE_SEG_CHUNKS,
+              "dense_plan.hpp restates these constants of kernels.h");
 
 // Which counts buffer a band's launch uses, and whether its epilogue runs on the second stream beside the next band's counts kernel.
 struct BandSlot {
@@ -1270,9 +1116,9 @@ static int run_counts_epilogue(skl_ctx *ctx, const skl_sketches *rows, const skl
     if (L.mixed) {
         g.xcd_interleave = 1;
         g.block_ke = plan->d_block_ke;
-        g.blk_shift_r = plan->shift_r;
-        g.blk_shift_c = plan->shift_c;
-        g.blk_cols = plan->blk_cols;
+        g.blk_shift_r = plan->geo.shift_r;
+        g.blk_shift_c = plan->geo.shift_c;
+        g.blk_cols = plan->geo.blk_cols;
     }
     void *counts = nullptr;
     SKL_TRY(ctx_scratch(ctx, L.plane_bytes * L.planes, &counts, slot.overlapped && slot.buf ? SCRATCH_COUNTS_2 : SCRATCH_COUNTS));
@@ -1332,10 +1178,10 @@ static int run_counts_epilogue(skl_ctx *ctx, const skl_sketches *rows, const skl
         ctx->eb_pairs += L.pairs;
         if (L.mixed) {
             e.block_ke = plan->d_block_ke;
-            e.blk_shift_r = plan->shift_r;
-            e.blk_shift_c = plan->shift_c;
-            e.blk_cols = plan->blk_cols;
-            ctx->last_kernel += " + early break: block by block (" + std::to_string(plan->blk_rows) + " x " + std::to_string(plan->blk_cols) + " blocks of sample ids), the pairs still in the running completed by the epilogue";
+            e.blk_shift_r = plan->geo.shift_r;
+            e.blk_shift_c = plan->geo.shift_c;
+            e.blk_cols = plan->geo.blk_cols;
+            ctx->last_kernel += " + early break: block by block (" + std::to_string(plan->geo.blk_rows) + " x " + std::to_string(plan->geo.blk_cols) + " blocks of sample ids), the pairs still in the running completed by the epilogue";
         } else {
             ctx->last_kernel += " + early break: " + std::to_string(L.lengths) + " of " + std::to_string(rows->nk) + " k-mer lengths counted, the pairs still in the running completed by the epilogue";
         }
@@ -1448,10 +1294,10 @@ int dense_band(skl_ctx *ctx, const skl_sketches *rows, const skl_sketches *cols,
     }
     if (plan) {
         c.eb_plan = true;
-        c.eb_lengths = plan->lengths;
-        c.eb_mixed = plan->mixed;
-        c.eb_alive_share = plan->alive_share;
-        if (plan->mixed || plan->lengths > 0) SKL_TRY(ensure_ytab(rows));   // (min_alive, which the rules read, is set with the table)
+        c.eb_lengths = plan->decision.lengths;
+        c.eb_mixed = plan->decision.mixed;
+        c.eb_alive_share = plan->decision.alive_share;
+        if (plan->decision.mixed || plan->decision.lengths > 0) SKL_TRY(ensure_ytab(rows));   // (min_alive, which the rules read, is set with the table)
     }
     c.min_alive = rows->min_alive;
 
@@ -1514,14 +1360,13 @@ static int dense_rows(skl_ctx *ctx, const skl_sketches *rows, const skl_sketches
     if (out_on_device) {
         return dense_band(ctx, rows, cols, p, mode, jout, self_mode, r0, r1, out);
     }
-    // host destination: bands of at most BAND_BYTES through two device buffers -- band i is
+    // host destination: the bands of plan_host_bands() (dense_plan.hpp) through two device buffers -- band i is
     // copied back on the auxiliary stream while band i + 1 is computed
+    const HostBands plan = plan_host_bands(self_mode != 0, n_cols, r0, r1, rec, BAND_BYTES);
     const uint64_t first = self_mode ? cond_index(r0, r0 + 1, n_cols) : r0 * n_cols;
     void *dev[2] = {nullptr, nullptr};
-    const uint64_t all_pairs = self_mode ? self_rows_pairs(r0, r1, n_cols) : (r1 - r0) * n_cols;
-    const size_t band_alloc = (size_t)std::min<uint64_t>(BAND_BYTES, all_pairs * rec);
-    SKL_TRY(ctx_scratch(ctx, band_alloc, &dev[0], SCRATCH_KEY_BAND));
-    SKL_TRY(ctx_scratch(ctx, all_pairs * rec > BAND_BYTES ? band_alloc : 16, &dev[1], SCRATCH_KEY_BAND_2));
+    SKL_TRY(ctx_scratch(ctx, plan.band_alloc, &dev[0], SCRATCH_KEY_BAND));
+    SKL_TRY(ctx_scratch(ctx, plan.second_alloc, &dev[1], SCRATCH_KEY_BAND_2));
     // A copy into pageable host memory does not return before it is done (the runtime stages it), so the copy of band i is
     // ISSUED after band i + 1's kernels are in the queue: the host blocks in the copy while the device computes.
     struct PendingCopy {
@@ -1536,40 +1381,27 @@ static int dense_rows(skl_ctx *ctx, const skl_sketches *rows, const skl_sketches
         HIP_TRY(hipEventRecord(ctx->knn_topk_done[c.buf], ctx->aux_stream));
         return SKL_OK;
     };
-    uint64_t b0 = r0;
-    size_t it = 0;
-    while (b0 < r1) {
-        uint64_t b1 = b0;
-        uint64_t pairs = 0;
-        while (b1 < r1) {
-            const uint64_t row_pairs = self_mode ? (n_cols - 1 - b1) : n_cols;
-            if (pairs && (pairs + row_pairs) * rec > BAND_BYTES) break;
-            pairs += row_pairs;
-            ++b1;
-        }
-        const int buf = (int)(it & 1);
-        void *band = dev[buf];
-        if (pairs * rec > band_alloc) {   // a single row wider than a band: its own buffer
+    for (size_t it = 0; it < plan.bands.size(); ++it) {
+        const HostBand &b = plan.bands[it];
+        if (b.own_buffer) {   // a single row wider than a band: its own buffer
             if (pending.bytes) {
                 SKL_TRY(issue_copy(pending));
                 pending.bytes = 0;
             }
             HIP_TRY(hipStreamSynchronize(ctx->aux_stream));
-            SKL_TRY(ctx_scratch(ctx, pairs * rec, &dev[buf], buf == 0 ? SCRATCH_KEY_BAND : SCRATCH_KEY_BAND_2));
-            band = dev[buf];
+            SKL_TRY(ctx_scratch(ctx, b.pairs * rec, &dev[b.buf], b.buf == 0 ? SCRATCH_KEY_BAND : SCRATCH_KEY_BAND_2));
         }
+        void *band = dev[b.buf];
         // the copy that read this buffer two bands ago must be done before it is overwritten
-        if (it >= 2) HIP_TRY(hipStreamWaitEvent(ctx->stream, ctx->knn_topk_done[buf], 0));
-        SKL_TRY(dense_band(ctx, rows, cols, p, mode, jout, self_mode, b0, b1, band));
-        HIP_TRY(hipEventRecord(ctx->knn_pair_done[buf], ctx->stream));
+        if (it >= 2) HIP_TRY(hipStreamWaitEvent(ctx->stream, ctx->knn_topk_done[b.buf], 0));
+        SKL_TRY(dense_band(ctx, rows, cols, p, mode, jout, self_mode, b.r0, b.r1, band));
+        HIP_TRY(hipEventRecord(ctx->knn_pair_done[b.buf], ctx->stream));
         if (pending.bytes) SKL_TRY(issue_copy(pending));   // the previous band's, behind this band's kernels
-        const uint64_t off = (self_mode ? cond_index(b0, b0 + 1, n_cols) : b0 * n_cols) - first;
+        const uint64_t off = (self_mode ? cond_index(b.r0, b.r0 + 1, n_cols) : b.r0 * n_cols) - first;
         pending.dst = (char *)out + off * rec;
         pending.src = band;
-        pending.bytes = pairs * rec;
-        pending.buf = buf;
-        b0 = b1;
-        ++it;
+        pending.bytes = b.pairs * rec;
+        pending.buf = b.buf;
     }
     if (pending.bytes) SKL_TRY(issue_copy(pending));
     HIP_TRY(hipStreamSynchronize(ctx->aux_stream));   // host memory is complete on return

@@ -1,8 +1,8 @@
 // capi_internal.hpp -- shared between the translation units that implement
 // include/sketchlib_dist.h (capi.cpp: contexts, slabs, dense calls; capi_knn.cpp: the kNN
 // drivers; capi_aux.cpp: candidate lists and sketching).  Not part of the public boundary.
-// How a dense call is launched is decided in dense_plan.hpp (pure, no HIP), reached through kernels.h; how the kNN drivers cut
-// and feed their bands in knn_plan.hpp (pure, no HIP).
+// How a dense call and each pair-kernel launch is shaped is decided in dense_plan.hpp (pure, no HIP), reached through kernels.h;
+// the early break's decision in eb_plan.hpp; how the kNN drivers cut and feed their bands in knn_plan.hpp (both pure, no HIP).
 #pragma once
 
 #include "../../include/sketchlib_dist.h"
@@ -16,6 +16,7 @@
 #include <vector>
 
 #include "kernels.h"
+#include "eb_plan.hpp"
 #include "knn_plan.hpp"
 #include "knobs.hpp"
 #include "roctx_ranges.hpp"
@@ -44,21 +45,19 @@ struct skl_sketches;
 
 SKL_INTERNAL Knobs read_knobs();
 
-// EARLY BREAK of the core/accessory calls, as decided for one (row slab, column slab) pair (capi.cpp early_break_plan): how many
-// k-mer lengths the pair kernel counts before the epilogue completes the pairs still in the running -- for the whole pair
-// space (`lengths`; what the kNN drivers take) and, when its blocks of (row >> shift_r, column >> shift_c) sample ids
-// disagree, per block.  Kept by the CONTEXT, keyed by the slabs' generation ids (never reused), not written through the
-// caller's const slab.
+// EARLY BREAK of the core/accessory calls, as decided for one (row slab, column slab) pair: how many k-mer lengths the pair
+// kernel counts before the epilogue completes the pairs still in the running -- for the whole pair space (`decision.lengths`;
+// what the kNN drivers take) and, when its blocks of (row >> shift_r, column >> shift_c) sample ids disagree, per block.
+// The rules -- when a decision is taken at all, the blocks, what the sampled histograms decide -- are eb_plan.hpp's (pure);
+// capi.cpp early_break_plan() samples and keeps the answer.  Kept by the CONTEXT, keyed by the slabs' generation ids (never
+// reused), not written through the caller's const slab.
 struct EbPlan {
     uint64_t rows_gen = 0, cols_gen = 0;
     int self_mode = 0, knob = 1;        // (knob: SKL_EARLY_BREAK as of the decision -- the A/B build may change it between calls)
     double cutoff = 0.0;                // completeness cutoff the sample was taken with (a correction changes ln J)
-    int lengths = 0;                    // pooled decision: lengths to count (0: all of them, no early break)
-    double alive_share = 0.0;           // sampled share of the pairs still in the running after them
-    bool mixed = false;                 // the blocks disagree: d_block_ke holds each block's count (nk: all of them)
-    uint32_t shift_r = 31, shift_c = 31, blk_rows = 1, blk_cols = 1;
-    std::vector<uint8_t> block_ke;      // [blk_rows * blk_cols], host copy (skl_ctx_early_break_blocks)
-    uint8_t *d_block_ke = nullptr;
+    skl::EbGeometry geo;                // the blocks
+    skl::EbDecision decision;           // (decision.block_ke: host copy of the table, skl_ctx_early_break_blocks)
+    uint8_t *d_block_ke = nullptr;      // the table on the device when the blocks disagree
 };
 
 // The context's grow-only scratch buffers (ctx_scratch).
@@ -176,7 +175,7 @@ SKL_INTERNAL std::pair<hipEvent_t, hipEvent_t> *timing_slot(skl_ctx *ctx);
 SKL_INTERNAL int check_params(const skl_sketches *a, const skl_sketches *b, const skl_dist_params *p);
 SKL_INTERNAL bool fused_coreacc_ok(const skl_sketches *s);
 // early break of the core/accessory calls (capi.cpp): the decision for this slab pair (sampled once, kept by the context);
-// *plan = null: not applicable (fewer than 3 or more than 8 k-mer lengths, a tiny pair space, switched off)
+// *plan = null: not applicable (eb_plan.hpp eb_applicable: fewer than 3 or more than 8 k-mer lengths, a tiny pair space, switched off)
 SKL_INTERNAL int early_break_plan(skl_ctx *ctx, const skl_sketches *rows, const skl_sketches *cols, int self_mode, double cutoff,
                                   const EbPlan **plan);
 // ... its pooled form, for the kNN drivers: k-mer lengths the pair kernel should count (0: all of them)

@@ -4,25 +4,31 @@
 // where to cut the call and plan_counts_launch() what each band launches, and executes the answer.  Nothing here touches a
 // device: no HIP header, plain C++17 (tests/native/dense_plan_check.cpp builds it with the host compiler alone).
 // The row bands are planned from the whole call, each band's launch from the band's own rows.
+// Every launch of the pair kernel then asks plan_pair_shape() for its tile shape and form (capi.cpp dispatch_pair_kernel), and
+// a host-destined call is cut by plan_host_bands() (capi.cpp dense_rows).
 #pragma once
 
 #include <stddef.h>
 #include <stdint.h>
 
 #include <algorithm>
+#include <string>
 #include <vector>
 
 #include "knobs.hpp"
 
 namespace skl {
 
-// = MODE_COUNTS / MODE_JACCARD / MODE_COREACC and KSLICE_MAX_U16_CHUNKS of kernels.h (capi.cpp asserts they agree)
+// = MODE_COUNTS / MODE_JACCARD / MODE_COREACC, KSLICE_MAX_U16_CHUNKS and KSLICE_SEG_CHUNKS of kernels.h (capi.cpp asserts they agree)
 constexpr int PLAN_MODE_COUNTS = 0, PLAN_MODE_JACCARD = 1, PLAN_MODE_COREACC = 2;
 constexpr uint32_t PLAN_MAX_U16_CHUNKS = 1023;   // sketches beyond it (65 535 bins): k-sliced forms only, u32 counts
+constexpr uint32_t PLAN_SEG_CHUNKS = 1016;       // ... walked in segments of this many chunks
 
-// Launch-size rule shared with dispatch_pair_kernel: core/acc launches below this many pairs
-// run k-sliced (counts + epilogue kernel), larger ones as one fused kernel.
+// Launch-size rule: core/acc launches below this many pairs run k-sliced (counts + epilogue kernel), larger ones as one
+// fused kernel; a launch that arrives at plan_pair_shape() as MODE_COUNTS with k_sliced set is one of the former.
 constexpr long long SLICED_MAX_PAIRS = 32ll << 20;   // n ~ 8000 all-vs-all: equal there (scripts/ab_sweep.py)
+constexpr uint64_t SMALL_LAUNCH_PAIRS = 8ull << 20;  // bin-match launches below this many pairs run one workgroup per (tile, k) whoever asks
+constexpr uint64_t BLOCKED_MIN_PAIRS = 48ull << 20;  // pair spaces from which the early break's epilogue walks in blocks (counts_basics; eb_plan.hpp prices a completion by it)
 constexpr size_t COUNTS_SCRATCH_MAX = 4ull << 30;    // bytes of bin-match counts one unfused core/accessory launch may park in HBM
 
 // A sketch of ss64 chunks cut into at most `wanted` chunk slices of whole stages: *chunks per slice (a multiple of 8, the
@@ -168,7 +174,7 @@ inline CountsBasics counts_basics(const DenseCall &c, uint64_t pairs)
     // 10.3 -> 9.9, 18.3 -> 17.2, 41.0 -> 38.0, 266 -> 234, 827 -> 642 ms; at 1.4 % alive (2 048 bins) +1 %: not taken.
     if (b.early) {
         b.blocked = c.knobs.eb_blocked >= 0 ? c.knobs.eb_blocked != 0   // (A/B build: forced)
-                                            : c.eb_plan && c.eb_alive_share >= 0.03 && pairs >= (48ull << 20) && c.ss64 <= PLAN_MAX_U16_CHUNKS;
+                                            : c.eb_plan && c.eb_alive_share >= 0.03 && pairs >= BLOCKED_MIN_PAIRS && c.ss64 <= PLAN_MAX_U16_CHUNKS;
     }
     b.lean_like = !b.mixed && (!c.has_comp || c.comp_unit) && c.min_alive != 0xFFFFFFFFu && b.lengths >= 2 && b.lengths <= 4;
     return b;
@@ -337,6 +343,155 @@ inline CountsLaunch plan_counts_launch(const DenseCall &c, uint64_t r0, uint64_t
                       c.ss64 <= PLAN_MAX_U16_CHUNKS;
     L.epilogue_r5 = c.knobs.epilogue_r5 && !b.mixed && !(b.early && (c.has_comp || c.ss64 > PLAN_MAX_U16_CHUNKS));
     return L;
+}
+
+// XCDs the device presents as one: an MI355X XCD has 32 CUs, so an unpartitioned (SPX) part shows 256 CUs = 8 XCDs, a CPX
+// partition 32 CUs = 1.  The tile order deals workgroups to XCDs by blockIdx mod that number; SKL_XCDS forces it (tests).
+inline uint32_t plan_xcd_shift(int n_cu, int knob_xcds)
+{
+    int x = knob_xcds > 0 ? knob_xcds : n_cu / 32;
+    uint32_t shift = 0;
+    while (shift < 3u && (2 << shift) <= x) ++shift;
+    return shift;
+}
+
+// ONE LAUNCH OF THE PAIR KERNEL: its tile shape and form.  Product library: the chunk-split kernel (pair_kslice.hip: 16 x 128
+// or 32 x 128 tiles, chunks split over the 4 waves, rows by LDS DMA; one workgroup per (tile, k) for small launches and for
+// single-k Jaccard, all k + fused regression otherwise) and, for the launches it does not take, pair_ksplit.hip.  The A/B
+// build adds the round-2/3 forms of the two tile shapes behind SKL_KSLICE_SHAPE and SKL_KERNEL=ksplit.
+constexpr int TILE_ROWS_SMALL = 16, TILE_ROWS_LARGE = 32;   // the two tile heights (a turned kNN record line holds whole tiles of either: knn_plan.hpp)
+struct PairLaunch {
+    int mode = PLAN_MODE_COUNTS;
+    bool self_mode = true;
+    uint64_t rows = 0;          // rows of the launch
+    uint32_t nB = 0, k_count = 0, ss64 = 0;
+    bool k_sliced = false;      // the caller asks for one workgroup per (tile, k-mer length)
+    bool mid_band = false;      // the mid-band rule (plan_counts_launch)
+    uint32_t tail_slices = 0;
+    int n_cu = 256;
+    uint32_t xcd_shift = 3;     // plan_xcd_shift()
+    Knobs knobs;
+    // the A/B build (-DSKL_AB) and the forms its switches force; the product library leaves all of it as it is
+    bool ab_build = false;
+    int ab_kernel = 0, ab_kslice_shape = 0, ab_ksplit_rows = 0, ab_kslice_ablate = 0;   // SKL_KERNEL, SKL_KSLICE_SHAPE, SKL_KSPLIT_ROWS, SKL_KSLICE_ABLATE
+};
+struct PairShape {
+    int shape = 165, ksplit_rows = 8;   // chunk-split kernel: tile shape; pair_ksplit.hip: rows per tile
+    int tile_rows = TILE_ROWS_SMALL;    // rows of the chunk-split kernel's tile
+    bool sliced_launch = false;         // one workgroup per (tile, k-mer length)
+    bool try_kslice = true;             // ask the chunk-split kernel first
+    int ablate = 0;
+    uint32_t wg_per_cu = 4, round_size = 0, tail_resident = 0;
+    bool no_half_tiles = false;
+    // what the name needs besides
+    int mode = PLAN_MODE_COUNTS;
+    bool big_sketch = false;
+    uint32_t tail_slices = 0;
+};
+inline PairShape plan_pair_shape(const PairLaunch &a)
+{
+    PairShape s;
+    s.mode = a.mode;
+    s.tail_slices = a.tail_slices;
+    const uint32_t n_xcd = 1u << a.xcd_shift;
+    const uint64_t pairs = a.self_mode ? a.rows * a.nB / 2 : a.rows * (uint64_t)a.nB;
+    const bool small = pairs < SMALL_LAUNCH_PAIRS;
+    // 165 = 16 x 128 tiles in the 128-register form (4 waves per SIMD): +3.5 % at n = 16 000 over the
+    // 141-register form 162 (3 waves), equal at n = 1 000 (profiles/r02_ab_tight.jsonl)
+    // 325 = 32 x 128 tiles (130-168 registers, 3 waves per SIMD) for launches of at least
+    // tile32_min pair x k-mer-length evaluations (~4 096 units of 32 x 128): every column register is
+    // used against 32 rows instead of 16, which halves the lane-slab traffic per pair -- HBM bytes per
+    // launch at n = 16 000 fall from 59.5 GB to 32.0 GB and the kernel gains 1.5-6 %
+    // (profiles/r02_tile32_*.md); smaller launches lose to the coarser tail (n = 1 000: +32 %).
+    s.shape = 165;
+    s.ksplit_rows = 8;   // 8 >= 4 rows from n = 1000 up once XCDs are balanced
+    {
+        const uint64_t k_walked = a.mode == PLAN_MODE_JACCARD ? 1u : a.k_count;
+        if (a.knobs.tile32_min >= 0 && pairs * k_walked >= (uint64_t)a.knobs.tile32_min) s.shape = 325;
+        if (a.mid_band) s.shape = 325;   // the mid-band rule (plan_counts_launch): 32-row tiles with the last round cut in 2
+    }
+    if (a.ab_build) {
+        if (a.ab_kslice_shape) s.shape = a.ab_kslice_shape;
+        if (a.ab_ksplit_rows) s.ksplit_rows = a.ab_ksplit_rows;
+        s.try_kslice = a.ab_kernel != 3;
+        s.ablate = a.ab_kslice_ablate;
+    }
+    s.tile_rows = s.shape > 1000 ? s.shape / 100 : s.shape / 10;
+    s.no_half_tiles = !a.knobs.half_tiles;
+    // workgroups resident per CU: 4 for every shipped form (the A/B build's 3-wave all-k 32-row form: 3)
+    // (sketches beyond 65 535 bins: the k-sliced forms only -- they walk a k-mer length in segments, pair_kslice_walk.inc)
+    s.big_sketch = a.ss64 > PLAN_MAX_U16_CHUNKS;
+    // single-k Jaccard: the sliced and the all-k form are the same work, the sliced one
+    // compiles to fewer registers; core/acc arrives here as MODE_COUNTS from dense_band when sliced
+    s.sliced_launch = a.mode == PLAN_MODE_JACCARD || (a.mode == PLAN_MODE_COUNTS && (small || a.k_sliced || s.big_sketch));
+    s.wg_per_cu = ((s.shape == 3255 && !s.sliced_launch) || (s.shape == 3254 && s.sliced_launch)) ? 3u : 4u;
+    s.round_size = a.knobs.round_priority ? s.wg_per_cu * (uint32_t)a.n_cu / n_xcd : 0u;
+    if (a.tail_slices > 1u) {
+        // tail-sliced one-workgroup-per-unit launch: two planes whatever kernel ends up running (a
+        // kernel without the slices leaves plane 1 as it found it: zero)
+        s.tail_resident = s.wg_per_cu * (uint32_t)a.n_cu / n_xcd;
+    }
+    return s;
+}
+
+// What skl_ctx_last_kernel() says of the launch; kslice_ok: the chunk-split kernel takes it (kslice_supported, pair_kslice.hip).
+inline std::string pair_kernel_name(const PairShape &s, bool kslice_ok)
+{
+    static const char *mode_names[] = {"COUNTS", "JACCARD", "COREACC"};
+    const std::string m = mode_names[s.mode];
+    if (s.try_kslice && kslice_ok) {
+        const int shape = s.shape;
+        const bool sliced = s.sliced_launch;
+        const int jl = (shape == 165 || shape == 325 || shape > 1000) ? 2 : shape % 10;
+        const int rr = s.tile_rows;
+        return "skl::pair_kernel_kslice<R=" + std::to_string(rr) + ", JL=" + std::to_string(jl) +
+               ", " + m + (sliced ? ", k-sliced" : ", all k") + ((shape == 165 || shape == 325 || shape > 1000) ? ", tight" : "") + "> (" +
+               std::to_string(rr) + "x" + std::to_string(jl * 64) + " tiles, chunks split over 4 waves" +
+               (s.big_sketch ? "; segments of " + std::to_string(PLAN_SEG_CHUNKS) + " chunks" : "") +
+               (sliced && s.mode == PLAN_MODE_COUNTS && s.tail_slices > 1u
+                    ? "; " + std::to_string(s.tail_slices) + " chunk slices per unit in the last round of workgroups" : "") + ")";
+    }
+    return "skl::pair_kernel_ksplit<R=" + std::to_string(s.ksplit_rows) + ", " + m + "> (" + std::to_string(s.ksplit_rows) +
+           "x64 tiles, chunks split over 4 waves)";
+}
+
+// HOST DESTINATION: rows [r0, r1) in bands of at most band_bytes through two device buffers -- band i is copied back while
+// band i + 1 is computed.  A band is whole rows, so a single row wider than a band is a band by itself and needs a buffer
+// of its own size.
+struct HostBand {
+    uint64_t r0 = 0, r1 = 0, pairs = 0;
+    int buf = 0;               // which of the two buffers
+    bool own_buffer = false;   // a single row wider than band_alloc: the buffer grows to it
+};
+struct HostBands {
+    std::vector<HostBand> bands;
+    size_t band_alloc = 0;        // bytes of the first buffer ...
+    size_t second_alloc = 16;     // ... and of the second (a call of one band never uses it)
+};
+inline HostBands plan_host_bands(bool self_mode, uint64_t n_cols, uint64_t r0, uint64_t r1, size_t rec, size_t band_bytes)
+{
+    HostBands out;
+    const uint64_t all_pairs = self_mode ? self_rows_pairs(r0, r1, n_cols) : (r1 - r0) * n_cols;
+    out.band_alloc = (size_t)std::min<uint64_t>(band_bytes, all_pairs * rec);
+    out.second_alloc = all_pairs * rec > band_bytes ? out.band_alloc : 16;
+    uint64_t b0 = r0;
+    while (b0 < r1) {
+        HostBand b;
+        b.r0 = b0;
+        uint64_t b1 = b0;
+        while (b1 < r1) {
+            const uint64_t row_pairs = self_mode ? (n_cols - 1 - b1) : n_cols;
+            if (b.pairs && (b.pairs + row_pairs) * rec > band_bytes) break;
+            b.pairs += row_pairs;
+            ++b1;
+        }
+        b.r1 = b1;
+        b.buf = (int)(out.bands.size() & 1);
+        b.own_buffer = b.pairs * rec > out.band_alloc;
+        out.bands.push_back(b);
+        b0 = b1;
+    }
+    return out;
 }
 
 }  // namespace skl

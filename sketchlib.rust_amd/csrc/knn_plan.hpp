@@ -218,7 +218,7 @@ struct KnnCall {
 // The call's geometry and the bytes of every scratch buffer it asks for: each holds the largest view any band of the call
 // can have.  With `overlap` the flag / bit arrays are two halves, the second one `*_half` words behind the first.
 struct KnnCallPlan {
-    size_t t_stride = 0;      // rows of a turned record line: whole tiles of either height (16 or 32 rows: dispatch_pair_kernel)
+    size_t t_stride = 0;      // rows of a turned record line: whole tiles of either height (TILE_ROWS_SMALL / TILE_ROWS_LARGE, dense_plan.hpp)
     size_t k_cols = 0;        // columns of a band's records (cross panel: the panel's)
     size_t bit_words = 0;     // words of a band row's marks (bit = 64-column block of the band's view)
     size_t tbit_words = 0;    // words of a column's marks in the turned band (bit = 32-row stretch; cross panel: nothing turned, 0)
@@ -235,7 +235,7 @@ inline KnnCallPlan plan_knn_call(const KnnCall &c)
     KnnCallPlan P;
     const size_t n = c.n_cols, rec = c.rec();
     P.turned = !c.cross();
-    P.t_stride = (c.band_rows + 31) / 32 * 32;
+    P.t_stride = (c.band_rows + TILE_ROWS_LARGE - 1) / TILE_ROWS_LARGE * TILE_ROWS_LARGE;
     P.k_cols = c.cross() ? c.win_hi - c.win_lo / 64 * 64 : n;   // (= win_hi - the 64-column block holding win_lo: the panel's view)
     P.key_band_bytes = c.band_rows * P.k_cols * rec;
     P.turned_band_bytes = P.turned ? n * P.t_stride * rec : 0;

@@ -3,6 +3,8 @@
 //   dense_plan_check pinned        : regimes whose plan is derived BY HAND from the rules (the arithmetic stands beside each case)
 //   dense_plan_check bands N       : the band cuts as a property over N seeded calls
 //   dense_plan_check consistency N : planes, record width and bytes agree with each other over N seeded launches
+//   dense_plan_check shape         : the pair kernel's tile shape, form and name for launches derived BY HAND (plan_pair_shape)
+//   dense_plan_check hostbands N   : the bands of a host-destined call, pinned cases and properties over N seeded calls
 // Prints one line per failed check and "ok <checks>" / "FAILED <failures> of <checks>"; the exit status says which.
 #include <cinttypes>
 #include <cstdint>
@@ -10,6 +12,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <random>
+#include <string>
 
 #include "../../sketchlib.rust_amd/csrc/dense_plan.hpp"
 
@@ -421,6 +424,247 @@ static void consistency(size_t n_cases)
     }
 }
 
+// One launch on an MI355X as one device (256 CUs, 8 XCDs: 4 x 256 / 8 = 128 resident workgroups per XCD), default switches.
+static PairLaunch launch_of(int mode, bool self_mode, uint64_t rows, uint32_t nB, uint32_t k_count, bool k_sliced)
+{
+    PairLaunch a;
+    a.mode = mode;
+    a.self_mode = self_mode;
+    a.rows = rows;
+    a.nB = nB;
+    a.k_count = k_count;
+    a.ss64 = 64;
+    a.k_sliced = k_sliced;
+    a.xcd_shift = plan_xcd_shift(a.n_cu, a.knobs.xcds);
+    return a;
+}
+#define CHECK_NAME(shape, ok, text)                                                                   \
+    do {                                                                                              \
+        ++g_checks;                                                                                   \
+        const std::string got_ = pair_kernel_name(shape, ok);                                         \
+        if (got_ != (text)) {                                                                         \
+            ++g_failed;                                                                               \
+            if (g_failed <= 40) printf("%s:%d: name \"%s\"\n", __FILE__, __LINE__, got_.c_str());     \
+        }                                                                                             \
+    } while (0)
+
+static void shape()
+{
+    // XCDs the tile order deals to: CUs / 32, at most 8, as a shift; SKL_XCDS overrides
+    CHECK_EQ(plan_xcd_shift(256, 0), 3);
+    CHECK_EQ(plan_xcd_shift(32, 0), 0);     // a CPX partition
+    CHECK_EQ(plan_xcd_shift(64, 0), 1);
+    CHECK_EQ(plan_xcd_shift(128, 0), 2);
+    CHECK_EQ(plan_xcd_shift(304, 0), 3);    // 9 "XCDs": capped at 8
+    CHECK_EQ(plan_xcd_shift(256, 2), 1);
+    CHECK_EQ(plan_xcd_shift(256, 4), 2);
+    CHECK_EQ(plan_xcd_shift(32, 8), 3);
+    CHECK_EQ(TILE_ROWS_SMALL, 16);
+    CHECK_EQ(TILE_ROWS_LARGE, 32);
+    {   // DESIGN.md 4.1, row 1 -- cfg 2: 1 000 genomes, early break at 2 lengths, tail slices: 499 500 pairs x 2 = 999 000 < 8 Mi
+        PairLaunch a = launch_of(PLAN_MODE_COUNTS, true, 999, 1000, 2, true);
+        a.tail_slices = 4;
+        const PairShape s = plan_pair_shape(a);
+        CHECK_EQ(s.shape, 165);
+        CHECK_EQ(s.tile_rows, 16);
+        CHECK(s.sliced_launch && s.try_kslice && !s.no_half_tiles);
+        CHECK_EQ(s.ablate, 0);
+        CHECK_EQ(s.wg_per_cu, 4);
+        CHECK_EQ(s.round_size, 128);       // 4 x 256 / 8
+        CHECK_EQ(s.tail_resident, 128);
+        CHECK_EQ(s.ksplit_rows, 8);
+        CHECK_NAME(s, true, "skl::pair_kernel_kslice<R=16, JL=2, COUNTS, k-sliced, tight> (16x128 tiles, chunks split over 4 waves; 4 chunk slices per unit in the last round of workgroups)");
+        CHECK_NAME(s, false, "skl::pair_kernel_ksplit<R=8, COUNTS> (8x64 tiles, chunks split over 4 waves)");   // the kernel declines: pair_ksplit.hip
+        a.tail_slices = 1;                 // tail_resident only with more than one slice
+        CHECK_EQ(plan_pair_shape(a).tail_resident, 0);
+        a.tail_slices = 0;
+        CHECK_EQ(plan_pair_shape(a).tail_resident, 0);
+        CHECK_NAME(plan_pair_shape(a), true, "skl::pair_kernel_kslice<R=16, JL=2, COUNTS, k-sliced, tight> (16x128 tiles, chunks split over 4 waves)");
+        a.tail_slices = 4;
+        a.knobs.round_priority = false;    // SKL_ROUND_PRIORITY=0: no rounds, the tail still needs its residency
+        CHECK_EQ(plan_pair_shape(a).round_size, 0);
+        CHECK_EQ(plan_pair_shape(a).tail_resident, 128);
+        a.knobs.half_tiles = false;
+        CHECK(plan_pair_shape(a).no_half_tiles);
+        a.n_cu = 32;                       // a CPX partition: 4 x 32 / 1
+        a.xcd_shift = 0;
+        a.knobs.round_priority = true;
+        CHECK_EQ(plan_pair_shape(a).round_size, 128);
+    }
+    {   // row 2 -- from 8 Mi = 8 388 608 evaluations 32 x 128 tiles: 3 000 genomes at 2 lengths: 4 498 500 x 2 = 8 997 000
+        const PairLaunch a = launch_of(PLAN_MODE_COUNTS, true, 2999, 3000, 2, true);
+        const PairShape s = plan_pair_shape(a);
+        CHECK_EQ(s.shape, 325);
+        CHECK_EQ(s.tile_rows, 32);
+        CHECK(s.sliced_launch);
+        CHECK_EQ(s.wg_per_cu, 4);
+        CHECK_NAME(s, true, "skl::pair_kernel_kslice<R=32, JL=2, COUNTS, k-sliced, tight> (32x128 tiles, chunks split over 4 waves)");
+        // the threshold itself, single k (one length walked whatever k_count says): 4 096 x 2 048 = 8 388 608
+        CHECK_EQ(plan_pair_shape(launch_of(PLAN_MODE_JACCARD, false, 4096, 2048, 5, false)).shape, 325);
+        CHECK_EQ(plan_pair_shape(launch_of(PLAN_MODE_JACCARD, false, 4095, 2048, 5, false)).shape, 165);
+        CHECK(plan_pair_shape(launch_of(PLAN_MODE_JACCARD, false, 4095, 2048, 1, false)).sliced_launch);   // single k: always k-sliced
+        CHECK_NAME(plan_pair_shape(launch_of(PLAN_MODE_JACCARD, false, 4096, 2048, 1, false)), true,
+                   "skl::pair_kernel_kslice<R=32, JL=2, JACCARD, k-sliced, tight> (32x128 tiles, chunks split over 4 waves)");
+        PairLaunch t = a;
+        t.knobs.tile32_min = -1;           // SKL_TILE32_MIN=-1: never
+        CHECK_EQ(plan_pair_shape(t).shape, 165);
+        t = launch_of(PLAN_MODE_COUNTS, true, 99, 100, 2, true);
+        CHECK_EQ(plan_pair_shape(t).shape, 165);
+        t.knobs.tile32_min = 0;            // 0: always
+        CHECK_EQ(plan_pair_shape(t).shape, 325);
+    }
+    {   // row 3 -- fused all-k core/accessory: 9 000 genomes, 40 495 500 pairs x 5
+        const PairShape s = plan_pair_shape(launch_of(PLAN_MODE_COREACC, true, 8999, 9000, 5, false));
+        CHECK_EQ(s.shape, 325);
+        CHECK(!s.sliced_launch);
+        CHECK_NAME(s, true, "skl::pair_kernel_kslice<R=32, JL=2, COREACC, all k, tight> (32x128 tiles, chunks split over 4 waves)");
+        CHECK(!plan_pair_shape(launch_of(PLAN_MODE_COREACC, true, 99, 100, 5, true)).sliced_launch);   // never sliced in this mode
+    }
+    {   // row 4 -- beyond 1 023 chunks the k-sliced form whatever the size; bin-match launches otherwise only below 8 Mi pairs
+        PairLaunch a = launch_of(PLAN_MODE_COUNTS, true, 4999, 5000, 5, false);   // 12 497 500 pairs
+        CHECK(!plan_pair_shape(a).sliced_launch && !plan_pair_shape(a).big_sketch);
+        CHECK_NAME(plan_pair_shape(a), true, "skl::pair_kernel_kslice<R=32, JL=2, COUNTS, all k, tight> (32x128 tiles, chunks split over 4 waves)");
+        a.ss64 = 1023;
+        CHECK(!plan_pair_shape(a).sliced_launch);
+        a.ss64 = 1024;
+        CHECK(plan_pair_shape(a).sliced_launch && plan_pair_shape(a).big_sketch);
+        CHECK_NAME(plan_pair_shape(a), true, "skl::pair_kernel_kslice<R=32, JL=2, COUNTS, k-sliced, tight> (32x128 tiles, chunks split over 4 waves; segments of 1016 chunks)");
+        CHECK(plan_pair_shape(launch_of(PLAN_MODE_COUNTS, true, 4095, 4096, 5, false)).sliced_launch);    // 4 095 x 4 096 / 2 = 8 386 560 < 8 388 608
+        CHECK(!plan_pair_shape(launch_of(PLAN_MODE_COUNTS, true, 4096, 4096, 5, false)).sliced_launch);   // 8 388 608
+        CHECK_EQ(SMALL_LAUNCH_PAIRS, 8388608);
+    }
+    {   // the mid band forces 32-row tiles below the threshold: 1 500 genomes x 5 lengths = 5 621 250 evaluations, last round in 2 slices
+        PairLaunch a = launch_of(PLAN_MODE_COUNTS, true, 1499, 1500, 5, true);
+        CHECK_EQ(plan_pair_shape(a).shape, 165);
+        a.mid_band = true;
+        a.tail_slices = 2;
+        const PairShape s = plan_pair_shape(a);
+        CHECK_EQ(s.shape, 325);
+        CHECK_EQ(s.tile_rows, 32);
+        CHECK_EQ(s.tail_resident, 128);
+        CHECK_NAME(s, true, "skl::pair_kernel_kslice<R=32, JL=2, COUNTS, k-sliced, tight> (32x128 tiles, chunks split over 4 waves; 2 chunk slices per unit in the last round of workgroups)");
+    }
+    {   // the A/B build's forms.  3254 = round 2's k-sliced 32-row form, 3255 its all-k form: 3 waves per SIMD = 3 workgroups per CU
+        // in THAT form, 4 in the other; 1651 / 1652 the 16-row forms
+        PairLaunch a = launch_of(PLAN_MODE_COUNTS, true, 999, 1000, 5, true);
+        a.ab_kslice_shape = 3254;
+        CHECK_EQ(plan_pair_shape(a).shape, 165);             // not the A/B build: the switches are not read
+        a.ab_build = true;
+        a.tail_slices = 4;
+        PairShape s = plan_pair_shape(a);
+        CHECK_EQ(s.shape, 3254);
+        CHECK_EQ(s.tile_rows, 32);
+        CHECK_EQ(s.wg_per_cu, 3);
+        CHECK_EQ(s.round_size, 96);                          // 3 x 256 / 8
+        CHECK_EQ(s.tail_resident, 96);
+        CHECK_NAME(s, true, "skl::pair_kernel_kslice<R=32, JL=2, COUNTS, k-sliced, tight> (32x128 tiles, chunks split over 4 waves; 4 chunk slices per unit in the last round of workgroups)");
+        a.ab_kslice_shape = 3255;
+        CHECK_EQ(plan_pair_shape(a).wg_per_cu, 4);           // sliced launch in the all-k shape
+        PairLaunch f = launch_of(PLAN_MODE_COREACC, true, 999, 1000, 5, false);
+        f.ab_build = true;
+        f.ab_kslice_shape = 3255;
+        s = plan_pair_shape(f);
+        CHECK_EQ(s.wg_per_cu, 3);
+        CHECK_EQ(s.round_size, 96);
+        CHECK_EQ(s.tail_resident, 0);
+        CHECK_NAME(s, true, "skl::pair_kernel_kslice<R=32, JL=2, COREACC, all k, tight> (32x128 tiles, chunks split over 4 waves)");
+        f.ab_kslice_shape = 3254;
+        CHECK_EQ(plan_pair_shape(f).wg_per_cu, 4);
+        f.ab_kslice_shape = 1652;
+        CHECK_EQ(plan_pair_shape(f).tile_rows, 16);
+        CHECK_NAME(plan_pair_shape(f), true, "skl::pair_kernel_kslice<R=16, JL=2, COREACC, all k, tight> (16x128 tiles, chunks split over 4 waves)");
+        f.ab_kslice_shape = 0;
+        f.ab_kslice_ablate = 2;
+        CHECK_EQ(plan_pair_shape(f).ablate, 2);
+        f.ab_kernel = 3;                                     // SKL_KERNEL=ksplit: the chunk-split kernel is not asked
+        f.ab_ksplit_rows = 4;
+        s = plan_pair_shape(f);
+        CHECK(!s.try_kslice);
+        CHECK_EQ(s.ksplit_rows, 4);
+        CHECK_NAME(s, true, "skl::pair_kernel_ksplit<R=4, COREACC> (4x64 tiles, chunks split over 4 waves)");
+    }
+}
+
+// plan_host_bands: four calls cut by hand, then what every cut must satisfy
+static void host_bands(size_t n_cases)
+{
+    {   // cross, 1 000 columns, 8-byte records, rows [0, 10), 24 000 B per band = 3 rows
+        const HostBands h = plan_host_bands(false, 1000, 0, 10, 8, 24000);
+        CHECK_EQ(h.bands.size(), 4);
+        CHECK_EQ(h.band_alloc, 24000);
+        CHECK_EQ(h.second_alloc, 24000);
+        const uint64_t r1[] = {3, 6, 9, 10}, pairs[] = {3000, 3000, 3000, 1000};
+        for (size_t b = 0; b < h.bands.size() && b < 4; ++b) {
+            CHECK_EQ(h.bands[b].r0, b ? r1[b - 1] : 0);
+            CHECK_EQ(h.bands[b].r1, r1[b]);
+            CHECK_EQ(h.bands[b].pairs, pairs[b]);
+            CHECK_EQ(h.bands[b].buf, b & 1);
+            CHECK(!h.bands[b].own_buffer);
+        }
+    }
+    {   // the same call under a bound it fits: one band, the second buffer a token
+        const HostBands h = plan_host_bands(false, 1000, 0, 10, 8, 1u << 30);
+        CHECK_EQ(h.bands.size(), 1);
+        CHECK_EQ(h.band_alloc, 80000);
+        CHECK_EQ(h.second_alloc, 16);
+        CHECK(h.bands.size() == 1 && h.bands[0].r0 == 0 && h.bands[0].r1 == 10 && h.bands[0].pairs == 10000 && !h.bands[0].own_buffer);
+    }
+    {   // a single row (8 000 B) wider than a band (4 000 B): every row its own band and its own buffer
+        const HostBands h = plan_host_bands(false, 1000, 2, 5, 8, 4000);
+        CHECK_EQ(h.bands.size(), 3);
+        CHECK_EQ(h.band_alloc, 4000);
+        for (size_t b = 0; b < h.bands.size(); ++b) {
+            CHECK(h.bands[b].own_buffer && h.bands[b].r1 == h.bands[b].r0 + 1 && h.bands[b].pairs == 1000);
+            CHECK_EQ(h.bands[b].r0, 2 + b);
+        }
+    }
+    {   // the triangle of 10 samples: rows hold 9, 8, ..., 1 pairs; 136 B = 17 pairs per band: 9 + 8 | 7 + 6 (+ 5 = 18) | 5 + 4 + 3 + 2 + 1 = 15
+        const HostBands h = plan_host_bands(true, 10, 0, 9, 8, 136);
+        CHECK_EQ(h.bands.size(), 3);
+        CHECK_EQ(h.band_alloc, 136);
+        if (h.bands.size() == 3) {
+            CHECK(h.bands[0].r0 == 0 && h.bands[0].r1 == 2 && h.bands[0].pairs == 17);
+            CHECK(h.bands[1].r0 == 2 && h.bands[1].r1 == 4 && h.bands[1].pairs == 13);
+            CHECK(h.bands[2].r0 == 4 && h.bands[2].r1 == 9 && h.bands[2].pairs == 15);
+            CHECK(h.bands[2].buf == 0 && !h.bands[0].own_buffer && !h.bands[2].own_buffer);
+        }
+    }
+    std::mt19937_64 rng(0xB05DBA9D);
+    for (size_t it = 0; it < n_cases; ++it) {
+        const bool self = (rng() & 1) != 0;
+        const uint64_t n = 2 + rng() % 5000;
+        const uint64_t row_limit = self ? n - 1 : 1 + rng() % 300;
+        const uint64_t r0 = rng() % row_limit, r1 = r0 + 1 + rng() % (row_limit - r0);
+        const size_t recs[] = {4, 8, 20};   // single k, core/accessory, bin-match counts of 5 lengths
+        const size_t rec = recs[rng() % 3];
+        const size_t band_bytes = 64 + (size_t)(rng() % (it % 4 == 0 ? 4000 : 4000000));
+        const HostBands h = plan_host_bands(self, n, r0, r1, rec, band_bytes);
+        const uint64_t all = self ? self_rows_pairs(r0, r1, n) : (r1 - r0) * n;
+        CHECK_EQ(h.band_alloc, std::min<uint64_t>(band_bytes, all * rec));
+        CHECK_EQ(h.second_alloc, all * rec > band_bytes ? h.band_alloc : 16);
+        CHECK(!h.bands.empty() && h.bands.front().r0 == r0 && h.bands.back().r1 == r1);
+        uint64_t sum = 0;
+        for (size_t b = 0; b < h.bands.size(); ++b) {
+            const HostBand &B = h.bands[b];
+            CHECK(B.r0 < B.r1);
+            if (b) CHECK_EQ(B.r0, h.bands[b - 1].r1);   // [r0, r1) once, in order
+            CHECK_EQ(B.buf, b & 1);
+            DenseCall c;
+            c.self_mode = self;
+            c.n_cols = n;
+            CHECK_EQ(B.pairs, pairs_by_rows(c, B.r0, B.r1));
+            const bool single = B.r1 - B.r0 == 1;
+            CHECK(B.pairs * rec <= band_bytes || single);          // within the bound unless it is a single row ...
+            CHECK_EQ(B.own_buffer, B.pairs * rec > h.band_alloc);  // ... which is then flagged
+            CHECK(!B.own_buffer || single);
+            // the band is full: the next row would not have fitted
+            if (B.r1 < r1) CHECK((B.pairs + (self ? n - 1 - B.r1 : n)) * rec > band_bytes);
+            sum += B.pairs;
+        }
+        CHECK_EQ(sum, all);   // (self mode: = self_rows_pairs(r0, r1, n))
+    }
+}
+
 int main(int argc, char **argv)
 {
     const char *what = argc > 1 ? argv[1] : "pinned";
@@ -428,6 +672,8 @@ int main(int argc, char **argv)
     if (!strcmp(what, "pinned")) pinned();
     else if (!strcmp(what, "bands")) bands(n);
     else if (!strcmp(what, "consistency")) consistency(n);
+    else if (!strcmp(what, "shape")) shape();
+    else if (!strcmp(what, "hostbands")) host_bands(n);
     else return 2;
     if (g_failed) printf("FAILED %ld of %ld\n", g_failed, g_checks);
     else printf("ok %ld\n", g_checks);

@@ -1,5 +1,6 @@
 """csrc/dense_plan.hpp decides HOW a dense distance call is launched -- fused kernel or counts + epilogue, the counts' record
-width, chunk slices and planes, the epilogue's order, the row bands and whether they overlap -- as pure functions of plain data.
+width, chunk slices and planes, the epilogue's order, the row bands and whether they overlap, each pair-kernel launch's tile shape
+and name, the bands of a host-destined call -- as pure functions of plain data.
 Here that decision is checked on the CPU: tests/native/dense_plan_check.cpp includes the header alone, is built with the host
 compiler (no ROCm include path: the header must not need one) and never loads the library.  The expected values of the pinned
 regimes are derived by hand from the rules; the GPU suites assert the same decisions through the kernel names they produce."""
@@ -36,3 +37,11 @@ def test_band_cuts_hold_their_properties(check):
 
 def test_planes_and_bytes_are_consistent(check):
     assert _run(check, "consistency", "20000") >= 20000
+
+
+def test_pair_kernel_shapes_and_names(check):
+    assert _run(check, "shape") >= 70
+
+
+def test_host_bands_hold_their_properties(check):
+    assert _run(check, "hostbands", "4000") >= 4000 * 8
