@@ -1212,6 +1212,7 @@ static int run_counts_epilogue(skl_ctx *ctx, const skl_sketches *rows, const skl
 #endif
     {
         if (coreacc_epilogue_is_lean(e)) ctx->last_kernel += e.cnt_u16 ? " [lean epilogue]" : " [lean epilogue, sliced counts]";
+        if (coreacc_epilogue_stages_rows(e)) ctx->last_kernel += " [row slices staged in LDS]";
         HIP_TRY(launch_coreacc_epilogue_r6(e, epi_stream));
     }
     if (slot.overlapped) HIP_TRY(hipEventRecord(ctx->eb_events[2 + slot.buf], epi_stream));

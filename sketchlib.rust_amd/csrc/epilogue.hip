@@ -179,7 +179,8 @@ __device__ __forceinline__ bool eb_stops(const EpilogueArgs &g, uint32_t same, d
 // run, or the next pair's first) is requested before trip n is counted, two register sets in turns; the row's slice
 // comes from the workgroup's LDS copy (row_off: 0 / 1, which of the staged rows).  Every request is unconditional (lanes
 // past the slice's end re-read its last half chunk and count nothing), so that the wait before a trip is counted stands for
-// the OLDER request only.  Returns, in lane l of a pair, the bins the pair shares at length index g.nk.
+// the OLDER request only; the one request past the wave's last pair re-reads one address of that pair's slice and is never
+// counted.  Returns, in lane l of a pair, the bins the pair shares at length index g.nk.
 struct EbTripIt {
     uint64_t mask;
     uint32_t l, trip;
@@ -187,10 +188,11 @@ struct EbTripIt {
     __device__ __forceinline__ bool valid() const { return mask != 0ull; }
     __device__ __forceinline__ void advance(uint32_t trips)
     {
+        if (mask == 0ull) return;   // past the last pair: stays on that pair's lane (a valid column for a request nobody counts)
         if (++trip == trips) {
             trip = 0u;
             mask &= mask - 1ull;
-            l = mask != 0ull ? (uint32_t)__builtin_ctzll(mask) : 0u;
+            if (mask != 0ull) l = (uint32_t)__builtin_ctzll(mask);
         }
     }
 };
@@ -198,7 +200,7 @@ struct EbTripIt {
 __device__ __forceinline__ void eb_request_cols(uint2 (&b)[7], const uint2 *cols_t, size_t sample_stride, uint32_t j, const EbTripIt &it, uint32_t halves, uint32_t lane)
 {
     const uint32_t j_l = (uint32_t)__builtin_amdgcn_readlane((int)j, (int)it.l);
-    const uint32_t h = min(it.trip * 64u + lane, halves - 1u);
+    const uint32_t h = it.valid() ? min(it.trip * 64u + lane, halves - 1u) : 0u;   // (past the last pair: every lane the same 56 bytes)
     const uint2 *pj = cols_t + (size_t)j_l * sample_stride + (size_t)h * 7;
 #pragma unroll
     for (int q = 0; q < 7; ++q) b[q] = pj[q];
@@ -239,23 +241,19 @@ __device__ __forceinline__ uint32_t eb_first_length_ahead(const EpilogueArgs &g,
     uint32_t left = (uint32_t)__popcll(mask) * trips;   // trips not yet counted; b0 holds the first of them
     eb_request_cols(b0, cols_t, sample_stride, j, rq, halves, lane);
     rq.advance(trips);
-    // (one exit, nothing conditional around a request: a wait in this loop stands for the older of the two requests in flight)
-    while (left > 2u) {
+    // (every count has exactly one request in front of it, whichever way the loop is left: the wait before a count stands for the
+    // older of the two requests in flight)
+    for (;;) {
         eb_request_cols(b1, cols_t, sample_stride, j, rq, halves, lane);
         rq.advance(trips);
         eb_count_trip(b0, lds_rows, row_off, ct, g.ss64, lane, part, result);
         ct.advance(trips);
+        if (--left == 0u) break;
         eb_request_cols(b0, cols_t, sample_stride, j, rq, halves, lane);
         rq.advance(trips);
         eb_count_trip(b1, lds_rows, row_off, ct, g.ss64, lane, part, result);
         ct.advance(trips);
-        left -= 2u;
-    }
-    if (left == 2u) eb_request_cols(b1, cols_t, sample_stride, j, rq, halves, lane);
-    eb_count_trip(b0, lds_rows, row_off, ct, g.ss64, lane, part, result);
-    if (left == 2u) {
-        ct.advance(trips);
-        eb_count_trip(b1, lds_rows, row_off, ct, g.ss64, lane, part, result);
+        if (--left == 0u) break;
     }
     return result;
 }
@@ -502,7 +500,8 @@ __device__ __forceinline__ bool eb_passes_comp(const EpilogueArgs &g, uint32_t s
 // with three divisions and three square roots for a pair whose fit has fewer than three points.  Here a pair that leaves the
 // reference's loop with fewer than three lengths (jaccard.rs:89-91, :117) is decided by NK integer compares and stored; the
 // pairs still in the running are completed as above (first length: requests one trip ahead from the LDS rows; later lengths one
-// after the other), their counts kept in registers; only a pair with three or more points looks its ln J up and runs the
+// after the other), their counts kept in registers.  The workgroup's row slices are requested at kernel entry, before the
+// counts, by every workgroup (their addresses need blockIdx alone; profiles/r07_cfg2_epilogue_chain.md); only a pair with three or more points looks its ln J up and runs the
 // reference's sums and regression, in the reference's order.  SLICED: u32 counts in n_slices planes (tail-sliced launches,
 // cfg 2), plane 1 re-zeroed; else u16 counts in one plane.
 template <bool SLICED, int NK, bool COMP>
@@ -533,6 +532,38 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5))) void c
         in_range = p_raw < g.n_pairs;
         p = in_range ? p_raw : g.n_pairs - 1;       // (lanes past the end shadow the last pair and store nothing)
     }
+    // the workgroup's row slices of length index NK, for LDS: requested here, stored once the counts have arrived, one barrier before the first completion
+    extern __shared__ __attribute__((aligned(16))) uint2 eb_lds_rows[];   // [2][2 ss64][7] (blocked order: one row)
+    uint32_t i_wg = 0, j_wg = 0;
+    bool have_wg = false;
+    // (i, j) in the flat order: the WORKGROUP's first pair is located once per wave (eb_pair_of: an f64 square root and its
+    // fix-ups in self mode, ~100 instructions), a lane's own pair follows from it by whole rows -- a workgroup's 256 pairs span two
+    // rows, a few more at the matrix' end -- instead of a second square root per wave
+    auto locate_wg = [&]() {
+        if (have_wg) return;
+        if (g.blocked) {
+            i_wg = i;
+        } else {
+            eb_pair_of(g, ((uint64_t)blockIdx.x + g.wg_base) * blockDim.x + g.out_base, i_wg, j_wg);
+        }
+        have_wg = true;
+    };
+    uint2 st[8];                            // (the launch gives the rows at most 16 KB: 8 x 256 uint2)
+    const bool staged = g.lds_rows != 0u;   // (workgroup-uniform; every thread is still here)
+    const uint32_t per_row = g.ss64 * 14u, n_stage = (g.blocked ? 1u : 2u) * per_row;
+    if (staged) {
+        locate_wg();
+        const uint2 *src = reinterpret_cast<const uint2 *>(g.rows_ref + (((uint64_t)i_wg * g.nk_total + NK) * g.ss64) * BBITS);
+        const size_t next_row = (size_t)g.nk_total * g.ss64 * BBITS;
+#pragma unroll
+        for (uint32_t q = 0; q < 8u; ++q) {
+            if (q * 256u < n_stage) {       // (uniform)
+                const uint32_t x = min(q * 256u + threadIdx.x, n_stage - 1u);
+                const uint32_t r = x >= per_row ? 1u : 0u;   // (the row slab ends in pad rows: row i_wg + 1 always exists)
+                st[q] = src[(size_t)r * next_row + (x - r * per_row)];
+            }
+        }
+    }
     // the counted lengths: how many pass before the first that does not (jaccard.rs:89-91 on the counts: count < min_alive <=> ln J < tolerance)
     uint32_t all[EB_MAXK];
 #pragma unroll
@@ -545,6 +576,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5))) void c
             if (g.rezero_plane1 && in_range) g.counts[p + ((uint64_t)NK + t) * g.k_stride] = 0u;   // plane 1 back to zero for the next tail-sliced launch
         } else {
             all[t] = (uint32_t)reinterpret_cast<const uint16_t *>(g.counts)[p + (uint64_t)t * g.k_stride];
+        }
+    }
+    if (staged) {                           // (the counts have arrived: so have the rows, requested before them)
+#pragma unroll
+        for (uint32_t q = 0; q < 8u; ++q) {
+            if (q * 256u + threadIdx.x < n_stage) eb_lds_rows[q * 256u + threadIdx.x] = st[q];
         }
     }
     uint32_t passed = 0;
@@ -586,20 +623,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5))) void c
     }
     const bool alive = in_range && run;     // (NK < nk_total: the host sends nothing else here)
     const uint64_t alive_mask = __ballot(alive);
-    // (i, j) in the flat order: the WORKGROUP's first pair is located once per wave (eb_pair_of: an f64 square root and its
-    // fix-ups in self mode, ~100 instructions), a lane's own pair follows from it by whole rows -- a workgroup's 256 pairs span two
-    // rows, a few more at the matrix' end -- instead of a second square root per wave
-    uint32_t i_wg = 0, j_wg = 0;
-    bool have_wg = false;
-    auto locate_wg = [&]() {
-        if (have_wg) return;
-        if (g.blocked) {
-            i_wg = i;
-        } else {
-            eb_pair_of(g, ((uint64_t)blockIdx.x + g.wg_base) * blockDim.x + g.out_base, i_wg, j_wg);
-        }
-        have_wg = true;
-    };
     if (alive_mask != 0ull) {           // (wave-uniform)
         if (!have_ij) {
             if (g.self_mode || g.nB_cols >= 64u) {
@@ -630,23 +653,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5))) void c
         }
         if (g.alive_count != nullptr && lane == 0u) atomicAdd(&g.alive_count[blockIdx.x & 1023u], (uint32_t)__popcll(alive_mask));
     }
-    extern __shared__ __attribute__((aligned(16))) uint2 eb_lds_rows[];   // [2][2 ss64][7]: the workgroup's row slices of length index NK (see above)
-    bool staged = false;
-    if (g.lds_rows) {                       // (workgroup-uniform; every thread is still here)
-        if (__syncthreads_or(alive ? 1 : 0)) {
-            locate_wg();
-            const uint32_t per_row = g.ss64 * 14u;
-            const uint2 *src = reinterpret_cast<const uint2 *>(g.rows_ref + (((uint64_t)i_wg * g.nk_total + NK) * g.ss64) * BBITS);
-            const size_t next_row = (size_t)g.nk_total * g.ss64 * BBITS;
-            const uint32_t staged_rows = g.blocked ? 1u : 2u;
-            for (uint32_t x = threadIdx.x; x < staged_rows * per_row; x += blockDim.x) {
-                const uint32_t r = x >= per_row ? 1u : 0u;   // (the row slab ends in pad rows: row i_wg + 1 always exists)
-                eb_lds_rows[x] = src[(size_t)r * next_row + (x - r * per_row)];
-            }
-            __syncthreads();
-            staged = true;
-        }
-    }
+    if (staged) __syncthreads();            // the rows are in LDS (the only barrier of the kernel)
     if (alive_mask != 0ull) {
         bool more = alive;
         uint32_t u_first = 0;             // this lane's first length index beyond NK not yet counted
@@ -1150,6 +1157,13 @@ bool coreacc_epilogue_is_lean(const EpilogueArgs &a)
            a.nk_total <= EB_MAXK && a.pair_stride == 1u && (a.cnt_u16 != 0u ? a.n_slices == 1u && a.rezero_plane1 == 0u : a.n_slices >= 1u);
 }
 
+// does that launch stage its workgroups' row slices in LDS?  (asked for, an early break with one ke for every pair, at most 16 KB)
+bool coreacc_epilogue_stages_rows(const EpilogueArgs &a)
+{
+    const bool early = a.nk_total > a.nk || a.block_ke != nullptr;
+    return early && a.block_ke == nullptr && a.ss64 * 224ull <= 16384ull && a.lds_rows != 0u;
+}
+
 hipError_t launch_coreacc_epilogue_r6(const EpilogueArgs &args, hipStream_t stream)
 {
     if (args.n_pairs == 0) return hipSuccess;
@@ -1169,7 +1183,7 @@ hipError_t launch_coreacc_epilogue_r6(const EpilogueArgs &args, hipStream_t stre
         blocks = (per_xcd * br) << a.xcd_shift;
         if (blocks >= (1ull << 32)) return hipErrorInvalidValue;
     }
-    const size_t lds = early && a.block_ke == nullptr && a.ss64 * 224ull <= 16384ull && a.lds_rows != 0u ? (size_t)a.ss64 * 224u : 0u;
+    const size_t lds = coreacc_epilogue_stages_rows(a) ? (size_t)a.ss64 * 224u : 0u;
     a.lds_rows = lds != 0 ? 1u : 0u;
     const bool lean = coreacc_epilogue_is_lean(a);
     // (a dispatch packet counts WORK-ITEMS in 32 bits: 2^23 workgroups of 256 per launch at most)
