@@ -318,6 +318,24 @@ def window_signs(files, k, rc=True, min_qual=20):
     return list(zip(starts, out)), codes, np.array(offs, dtype=np.uint64)
 
 
+def window_table(codes, offsets, k, rc=True):
+    """(starts int64[], signs uint64[]) of every valid window of one sample given as arrays, in start order: start s is
+    valid iff s + k <= len(codes) and no offset o has s < o < s + k; the signs are the oracle's non-rolling hashes
+    (oracle/sketcher.py kmer_hashes, pinned on the reference's .skd files) mod SIGN_MOD.  The vectorised counterpart
+    of window_signs; tests/test_sketch_reads_cpu.py ties the two together."""
+    from oracle.sketcher import kmer_hashes
+
+    codes = np.asarray(codes, dtype=np.uint8)
+    offs = np.sort(np.asarray(offsets, dtype=np.int64))
+    cand = np.arange(max(len(codes) - k + 1, 0), dtype=np.int64)
+    first_after = np.searchsorted(offs, cand, side="right")      # the first offset strictly above s ...
+    nxt = np.append(offs, np.iinfo(np.int64).max)[first_after]
+    starts = cand[nxt >= cand + k]                               # ... must not lie below s + k
+    signs = kmer_hashes(codes, offs, k, rc) % np.uint64(SIGN_MOD)
+    assert starts.size == signs.size
+    return starts, signs
+
+
 def random_genome(rng, n):
     return rng.choice(np.frombuffer(b"ACGT", dtype=np.uint8), size=n).tobytes()
 

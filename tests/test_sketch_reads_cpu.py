@@ -111,6 +111,37 @@ def test_single_fastq_file_and_padding_windows(tmp_path):
     assert n1 % 4 == 1 and any(n1 <= s < n1 + 3 for s, _ in wins)
 
 
+@pytest.fixture(scope="module")
+def abi_pair(tmp_path_factory):
+    """A read pair built as tests/test_gpu_sketch_reads.py's ABI test builds its own: a 2 kb genome, 120 reads per
+    file (here of 30-90 bases, so that k = 65 has windows) with 1 % N and 5 % low-quality bases, two padding bases
+    between the files at min_qual 53."""
+    d = tmp_path_factory.mktemp("abi_pair")
+    rng = np.random.default_rng(5)
+    genome = R.random_genome(rng, 2000)
+    files = []
+    for end in (1, 2):
+        reads = R.synthetic_reads(rng, genome, 120, (30, 90), 0.01, 0.01, 0.05)
+        if end == 1:
+            reads = R.pad_to_residue(reads, 53, 2)
+        path = str(d / f"abi_{end}.fastq.gz")
+        R.write_fastq(path, reads)
+        files.append(path)
+    return files
+
+
+@pytest.mark.parametrize("k,rc", [(1, True), (9, True), (32, False), (33, True), (65, True)])
+def test_window_table_equals_literal_iterator(abi_pair, k, rc):
+    """The vectorised window list the GPU survivor tests expect from (searchsorted mask, non-rolling hashes) against
+    the literal restatement of the reference's iterator (rolling hashes, next_iterator's restarts): the same starts
+    and the same signs, on the codes and offsets the literal one hands to the device."""
+    wins, codes, offs = R.window_signs(abi_pair, k, rc, 53)
+    starts, signs = R.window_table(codes, offs, k, rc)
+    assert wins   # (k = 65 leaves a handful on this input, k = 1 about 14 000)
+    assert starts.tolist() == [s for s, _ in wins]
+    assert signs.tolist() == [g for _, g in wins]
+
+
 def test_three_read_files_panic(tmp_path):
     f = PAIRS[0]
     _, res = run_sketch(tmp_path, "x", "-f", rfile(tmp_path, [f + [f[0]]]), "-k", "9", check=False)
