@@ -1,11 +1,14 @@
 // topk.hip -- k nearest neighbours per row on the device: the radix select (select_smallest,
 // topk_kernel for ragged candidate rows), the streaming running top-k of the dense kNN drivers
 // (topk_merge_kernel), the merge of partial states of a multi-GPU run (merge_states_kernel)
-// and the conversion of a state to the public output form.  mod.rs:41-48 semantics with the
-// canonical tie rule: smallest (key, index) first.
+// and the conversion of a state to the public output form: mod.rs:41-48 semantics with the
+// canonical tie rule, smallest (key, index) first.  Then the reference's tie order: its BinaryHeap
+// replayed, one-shot and resumable, by one workgroup or one wave per row.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cstddef>
+#include <type_traits>
 
 #include "kernels.h"
 
@@ -38,9 +41,11 @@ struct TopkShared {
     uint64_t items[TOPK_MAX];  // (sortable key << 32) | position
 };
 
-// Bitonic sort of items[0, m) (m a power of two), ascending.  `items` is the workgroup's own array: LDS, or --
-// for more neighbours than fit there -- global memory (a barrier orders a workgroup's global accesses too).
-__device__ __forceinline__ void sort_items(uint64_t *items, uint32_t m)
+// Bitonic sort of items[0, m) (m a power of two), ascending; a payload array (optional) travels with the items.  `items` is
+// the workgroup's own array: LDS, or -- for more neighbours than fit there -- global memory (a barrier orders a workgroup's
+// global accesses too).
+template <class Payload = std::nullptr_t>
+__device__ __forceinline__ void sort_items(uint64_t *items, uint32_t m, Payload payload = nullptr)
 {
     const uint32_t tid = threadIdx.x;
     for (uint32_t size = 2; size <= m; size <<= 1) {
@@ -53,11 +58,37 @@ __device__ __forceinline__ void sort_items(uint64_t *items, uint32_t m)
                 if ((a > b) == up) {
                     items[lo] = b;
                     items[hi] = a;
+                    if constexpr (!std::is_null_pointer_v<Payload>) {
+                        const auto pa = payload[lo];
+                        payload[lo] = payload[hi];
+                        payload[hi] = pa;
+                    }
                 }
             }
             __syncthreads();
         }
     }
+}
+
+// Mark words of one row (TopkMergeArgs::seg_bits, never null here): is position q inside a marked stretch ...
+__device__ __forceinline__ bool seg_marked(const uint32_t *bits, uint32_t seg_shift, uint32_t q)
+{
+    const uint32_t b = q >> seg_shift;
+    return ((bits[b >> 5] >> (b & 31u)) & 1u) != 0u;
+}
+
+// ... and is any stretch that overlaps positions [q_lo, q_hi) marked (q_lo < q_hi)
+__device__ __forceinline__ bool seg_any_marked(const uint32_t *bits, uint32_t seg_shift, uint32_t q_lo, uint32_t q_hi)
+{
+    const uint32_t b_lo = q_lo >> seg_shift, b_hi = (q_hi - 1u) >> seg_shift;
+    bool any = false;
+    for (uint32_t w = b_lo >> 5; w <= (b_hi >> 5); ++w) {
+        uint32_t word = bits[w];
+        if (w == (b_lo >> 5)) word &= ~0u << (b_lo & 31u);
+        if (w == (b_hi >> 5) && (b_hi & 31u) != 31u) word &= (2u << (b_hi & 31u)) - 1u;
+        any |= word != 0u;
+    }
+    return any;
 }
 
 // The knn_eff smallest (key, position) of positions [0, n_items) for which item(c, u) is true
@@ -240,10 +271,7 @@ __device__ __forceinline__ void topk_merge_row(const TopkMergeArgs &g, const uin
     // pruned tile, pair_kslice_walk.inc)
     const uint32_t *seg_bits = g.seg_bits != nullptr ? g.seg_bits + (size_t)row * g.seg_bits_stride : nullptr;
     const uint32_t seg_shift = g.seg_shift != 0u ? g.seg_shift : 6u;
-    auto marked = [&](uint32_t q) {
-        const uint32_t b = q >> seg_shift;
-        return seg_bits == nullptr || ((seg_bits[b >> 5] >> (b & 31u)) & 1u) != 0u;
-    };
+    auto marked = [&](uint32_t q) { return seg_bits == nullptr || seg_marked(seg_bits, seg_shift, q); };
 
     auto fresh = [&](uint32_t q, uint32_t &u) {   // new key at position q of this launch
         const uint32_t id = g.id_base + q;
@@ -295,19 +323,8 @@ __device__ __forceinline__ void topk_merge_row(const TopkMergeArgs &g, const uin
             // walks a whole row, so its memory-level parallelism is what the scan runs at)
             constexpr uint32_t UNROLL = 4;
             for (uint32_t q0 = begin; q0 < begin + len; q0 += TOPK_THREADS * UNROLL) {
-                if (seg_bits != nullptr) {
-                    // a stretch of 1 024 positions without a mark is not read at all
-                    const uint32_t *bits = seg_bits;
-                    const uint32_t b_lo = q0 >> seg_shift, b_hi = (min(q0 + TOPK_THREADS * UNROLL, begin + len) - 1u) >> seg_shift;
-                    bool any = false;
-                    for (uint32_t w = b_lo >> 5; w <= (b_hi >> 5); ++w) {
-                        uint32_t word = bits[w];
-                        if (w == (b_lo >> 5)) word &= ~0u << (b_lo & 31u);
-                        if (w == (b_hi >> 5) && (b_hi & 31u) != 31u) word &= (2u << (b_hi & 31u)) - 1u;
-                        any |= word != 0u;
-                    }
-                    if (!any) continue;   // (workgroup-uniform)
-                }
+                // a stretch of 1 024 positions without a mark is not read at all (workgroup-uniform)
+                if (seg_bits != nullptr && !seg_any_marked(seg_bits, seg_shift, q0, min(q0 + TOPK_THREADS * UNROLL, begin + len))) continue;
                 uint64_t item[UNROLL];
                 float raw[UNROLL];
 #pragma unroll
@@ -432,24 +449,7 @@ __global__ __launch_bounds__(TOPK_THREADS) void merge_states_kernel(const MergeS
         slot[x] = (uint16_t)x;
     }
     __syncthreads();
-    for (uint32_t size = 2; size <= m; size <<= 1) {
-        for (uint32_t stride = size >> 1; stride > 0; stride >>= 1) {
-            for (uint32_t x = tid; x < m / 2; x += TOPK_THREADS) {
-                const uint32_t lo = 2 * x - (x & (stride - 1));
-                const uint32_t hi = lo + stride;
-                const bool up = (lo & size) == 0;
-                const uint64_t a = items[lo], b = items[hi];
-                if ((a > b) == up) {
-                    items[lo] = b;
-                    items[hi] = a;
-                    const uint16_t sa = slot[lo];
-                    slot[lo] = slot[hi];
-                    slot[hi] = sa;
-                }
-            }
-            __syncthreads();
-        }
-    }
+    sort_items(items, m, slot);
     for (uint32_t x = tid; x < knn; x += TOPK_THREADS) {
         const size_t o = (size_t)row * knn + x;
         g.out_key[o] = (uint32_t)(items[x] >> 32);
@@ -484,11 +484,8 @@ hipError_t launch_merge_states(const MergeStatesArgs &args, hipStream_t stream)
 // swap(0, end) + sift_down_range); the test suite checks it against an independent CPU restatement.  Keys compare as f32
 // (SparseJaccard / SparseCoreAcc order on the distance alone, distance_matrix.rs:214-262).
 //
-// One workgroup per row.  All threads scan the row's records in candidate order and compact, IN ORDER, the ones
-// that could enter the heap as it stood at the last drain (not full, or key below its maximum: the maximum only
-// falls, so this is a superset of what the heap accepts) into an LDS buffer; thread 0 drains the buffer through
-// the exact push / pop sequence, which rejects the rest.  The heap lives in LDS (global memory beyond
-// REFHEAP_LDS_MAX neighbours).
+// Below: the heap, what the kernels share around it, the two feeds (one workgroup per row, one wave per row), the kernels
+// (one-shot and resumable in either form, and the resumable form's last step) and their launchers.
 // ---------------------------------------------------------------------------
 namespace {
 struct RefHeap {
@@ -497,6 +494,12 @@ struct RefHeap {
     uint32_t *id;     // [knn + 1]
     uint32_t len;
     bool two;
+
+    // an empty heap of up to knn items in the 3 * (knn + 1) words at base (LDS, or global memory beyond REFHEAP_LDS_MAX)
+    static __device__ __forceinline__ RefHeap at(float *base, uint32_t knn, bool two)
+    {
+        return RefHeap{base, base + (knn + 1u), reinterpret_cast<uint32_t *>(base + 2u * (knn + 1u)), 0u, two};
+    }
 
     struct Elt { float k, d; uint32_t i; };
     __device__ __forceinline__ Elt get(uint32_t p) const { return Elt{key[p], two ? d1[p] : 0.0f, id[p]}; }
@@ -570,7 +573,7 @@ struct RefHeap {
         }
         return false;
     }
-    __device__ void into_sorted()
+    __device__ void into_sorted()   // (len stays: callers hand it on to refheap_write_sorted)
     {
         uint32_t end = len;
         while (end > 1u) {
@@ -582,10 +585,7 @@ struct RefHeap {
         }
     }
 };
-}  // namespace
 
-// Shared scratch of the replay kernels: the candidates that passed the pre-filter since the last drain, in order.
-constexpr uint32_t REFHEAP_CAP = 2048;
 // ACCEPT LOG (RefHeapMergeArgs::log_*): every candidate a row's heap takes is appended to the row's log, in order -- what a
 // heap that arrives LATER with the row's earlier candidates already in it has to be shown of this launch's candidates (it
 // takes a subset: its maximum is never higher).  One thread writes (the one that pushes); len counts past cap (overflow).
@@ -593,6 +593,19 @@ struct RefHeapLog {
     float *rec = nullptr;
     uint32_t *id = nullptr;
     uint32_t cap = 0, len = 0, stride2 = 1;
+
+    static __device__ __forceinline__ RefHeapLog of(const RefHeapMergeArgs &g, size_t srow)   // the log of state row srow (off: no log_rec)
+    {
+        RefHeapLog alog;
+        if (g.log_rec != nullptr) {
+            alog.rec = g.log_rec + srow * g.log_cap * g.stride2;
+            alog.id = g.log_id + srow * g.log_cap;
+            alog.cap = g.log_cap;
+            alog.len = g.log_len[srow];
+            alog.stride2 = g.stride2;
+        }
+        return alog;
+    }
     __device__ __forceinline__ void add(const RefHeap::Elt &e)
     {
         if (rec == nullptr) return;
@@ -605,6 +618,78 @@ struct RefHeapLog {
     }
 };
 
+// The row of a one-shot call (RefHeapArgs): a whole row of a dense band, or (row_offsets != null) a ragged candidate row
+// whose position p stands for sample col_ids[row_offsets[row] + p] -- the candidates in the order they are LISTED (the
+// reference pushes in the order Inverted::any_shared_bins returns them, mod.rs:459-487).
+struct RefHeapRow {
+    const float *keys;
+    const uint32_t *ids;   // ragged: the listed sample ids, else null (position = id, self_id is not a candidate)
+    uint32_t cols, self_id;
+    bool ragged;
+};
+__device__ __forceinline__ RefHeapRow refheap_one_shot_row(const RefHeapArgs &g, uint32_t row)
+{
+    const bool ragged = g.row_offsets != nullptr;
+    const uint64_t row_base = ragged ? g.row_offsets[row] : 0ull;
+    return RefHeapRow{ragged ? g.keys + row_base * g.stride2 : g.keys + (size_t)row * g.key_stride, ragged ? g.col_ids + row_base : nullptr,
+                      ragged ? (uint32_t)(g.row_offsets[row + 1] - row_base) : g.cols,
+                      g.self_id_base == 0xFFFFFFFFu ? 0xFFFFFFFFu : g.self_id_base + row, ragged};
+}
+
+// A heap between the launches of the resumable form (h_key / h_id / h_d1 [.][knn], h_len [.], row srow) -> h's memory, by
+// a group of `width` threads of which the caller is number t; -> its length.  The caller orders the group afterwards.
+__device__ __forceinline__ uint32_t refheap_load_state(RefHeap &h, const float *h_key, const uint32_t *h_id, const float *h_d1,
+                                                       const uint32_t *h_len, size_t srow, uint32_t knn, uint32_t t, uint32_t width)
+{
+    const uint32_t len = h_len[srow];
+    for (uint32_t x = t; x < len; x += width) {
+        h.key[x] = h_key[srow * knn + x];
+        h.id[x] = h_id[srow * knn + x];
+        if (h.two) h.d1[x] = h_d1[srow * knn + x];
+    }
+    return len;
+}
+
+// ... and back, with its length and thr[.] (what the pair kernel's row / block flags compare with)
+__device__ __forceinline__ void refheap_store_state(const RefHeap &h, uint32_t len, const RefHeapMergeArgs &g, size_t srow, uint32_t t,
+                                                    uint32_t width)
+{
+    const uint32_t knn = g.knn;
+    for (uint32_t x = t; x < len; x += width) {
+        g.h_key[srow * knn + x] = h.key[x];
+        g.h_id[srow * knn + x] = h.id[x];
+        if (h.two) g.h_d1[srow * knn + x] = h.d1[x];
+    }
+    if (t == 0u) {
+        g.h_len[srow] = len;
+        g.thr[srow] = len < knn ? 0xFFFFFFFFu : sortable_bits(h.key[0]);
+    }
+}
+
+// h's memory after into_sorted -> row `row` of the public output form, by such a group; pad: entries [len, knn) become
+// (row, 1.0), what the reference lists behind fewer than knn candidates (mod.rs:535-546)
+__device__ __forceinline__ void refheap_write_sorted(const RefHeap &h, uint32_t len, uint32_t row, uint32_t knn, int ani_undo, bool pad,
+                                                     uint64_t *out_idx, float *out_d0, float *out_d1, uint32_t t, uint32_t width)
+{
+    for (uint32_t x = t; x < (pad ? knn : len); x += width) {
+        const size_t o = (size_t)row * knn + x;
+        if (x < len) {
+            out_idx[o] = h.id[x];
+            out_d0[o] = ani_undo ? 1.0f - h.key[x] : h.key[x];
+            if (h.two && out_d1) out_d1[o] = h.d1[x];
+        } else {
+            out_idx[o] = row;
+            out_d0[o] = 1.0f;
+        }
+    }
+}
+
+// ---- the feed of one workgroup per row ----
+// All threads scan the row's records in candidate order and compact, IN ORDER, the ones that could enter the heap as it
+// stood at the last drain (not full, or key below its maximum: the maximum only falls, so this is a superset of what the
+// heap accepts) into an LDS buffer; thread 0 drains the buffer through the exact push / pop sequence, which rejects the
+// rest.  The heap lives in LDS (global memory beyond REFHEAP_LDS_MAX neighbours).
+constexpr uint32_t REFHEAP_CAP = 2048;   // the candidates that passed the pre-filter since the last drain, in order
 struct RefHeapShared {
     float cand_key[REFHEAP_CAP], cand_d1[REFHEAP_CAP];
     uint32_t cand_id[REFHEAP_CAP];
@@ -639,17 +724,7 @@ __device__ __forceinline__ void refheap_feed(RefHeap &h, RefHeapShared &sh, cons
         __syncthreads();
     };
     for (uint32_t q0 = 0; q0 < cols; q0 += TOPK_THREADS * UNROLL) {
-        if (bits != nullptr) {
-            const uint32_t b_lo = q0 >> seg_shift, b_hi = (min(q0 + TOPK_THREADS * UNROLL, cols) - 1u) >> seg_shift;
-            bool marked = false;
-            for (uint32_t w = b_lo >> 5; w <= (b_hi >> 5); ++w) {
-                uint32_t word = bits[w];
-                if (w == (b_lo >> 5)) word &= ~0u << (b_lo & 31u);
-                if (w == (b_hi >> 5) && (b_hi & 31u) != 31u) word &= (2u << (b_hi & 31u)) - 1u;
-                marked |= word != 0u;
-            }
-            if (!marked) continue;   // (workgroup-uniform)
-        }
+        if (bits != nullptr && !seg_any_marked(bits, seg_shift, q0, min(q0 + TOPK_THREADS * UNROLL, cols))) continue;   // (workgroup-uniform)
         float k[UNROLL], d[UNROLL];
 #pragma unroll
         for (uint32_t j = 0; j < UNROLL; ++j) {   // unconditional (clamped) loads, all in flight together
@@ -667,8 +742,7 @@ __device__ __forceinline__ void refheap_feed(RefHeap &h, RefHeapShared &sh, cons
             const uint32_t q = q0 + j * TOPK_THREADS + tid;
             id[j] = 0u;
             // (an unmarked stretch is not a candidate: it may not have been written at all -- a pruned tile)
-            const uint32_t sb = q >> seg_shift;
-            const bool seg_ok = bits == nullptr || (q < cols && ((bits[sb >> 5] >> (sb & 31u)) & 1u) != 0u);
+            const bool seg_ok = bits == nullptr || (q < cols && seg_marked(bits, seg_shift, q));
             take[j] = q < cols && seg_ok && id_of(q, id[j]) && (open || k[j] < thr);
             any |= take[j] ? 1 : 0;
         }
@@ -710,183 +784,46 @@ __device__ __forceinline__ void refheap_feed(RefHeap &h, RefHeapShared &sh, cons
     drain();
 }
 
-// One-shot form: a whole row of a dense band, or (row_offsets != null) a ragged candidate row whose position p stands for
-// sample col_ids[row_offsets[row] + p] -- the candidates in the order they are LISTED (the reference pushes in the order
-// Inverted::any_shared_bins returns them, mod.rs:459-487) -- padded with (row, 1.0) behind fewer than knn candidates
-// (mod.rs:535-546).
-__global__ __launch_bounds__(TOPK_THREADS) void topk_refheap_kernel(const RefHeapArgs g)
-{
-    __shared__ float lds_heap[3 * (REFHEAP_LDS_MAX + 1)];
-    __shared__ RefHeapShared sh;
-    const uint32_t row = blockIdx.x + g.first_row, tid = threadIdx.x;
-    const uint32_t knn = g.knn, stride2 = g.stride2;
-    const bool ragged = g.row_offsets != nullptr;
-    const uint64_t row_base = ragged ? g.row_offsets[row] : 0ull;
-    const uint32_t cols = ragged ? (uint32_t)(g.row_offsets[row + 1] - row_base) : g.cols;
-    const uint32_t self_id = g.self_id_base == 0xFFFFFFFFu ? 0xFFFFFFFFu : g.self_id_base + row;
-    const float *keys = ragged ? g.keys + row_base * stride2 : g.keys + (size_t)row * g.key_stride;
-    const uint32_t *ids = ragged ? g.col_ids + row_base : nullptr;
-    float *base = g.heap_scratch ? g.heap_scratch + (size_t)blockIdx.x * 3u * (knn + 1u) : lds_heap;
-    RefHeap h{base, base + (knn + 1u), reinterpret_cast<uint32_t *>(base + 2u * (knn + 1u)), 0u, stride2 == 2u};
-    if (tid == 0) {
-        sh.len = 0;
-        sh.ncand = 0;
-        sh.thr = __builtin_inff();
-    }
-    __syncthreads();
-    if (cols != 0u) {
-        refheap_feed(h, sh, keys, stride2, cols, knn,
-                     [&](uint32_t q, uint32_t &id) {
-                         id = ids ? ids[q] : q;
-                         return q != self_id || ids != nullptr;
-                     },
-                     nullptr);
-    }
-    if (tid == 0) {
-        h.len = sh.len;
-        h.into_sorted();
-    }
-    __syncthreads();
-    const uint32_t len = sh.len;
-    for (uint32_t x = tid; x < knn; x += TOPK_THREADS) {
-        const size_t o = (size_t)row * knn + x;
-        if (x < len) {
-            g.out_idx[o] = h.id[x];
-            g.out_d0[o] = g.ani_undo ? 1.0f - h.key[x] : h.key[x];
-            if (stride2 == 2u && g.out_d1) g.out_d1[o] = h.d1[x];
-        } else if (ragged) {
-            g.out_idx[o] = row;
-            g.out_d0[o] = 1.0f;
-        }
-    }
-}
-
-constexpr uint32_t REFHEAP_WAVE_KNN_ONE_SHOT = 256;   // (= REFHEAP_WAVE_KNN below)
-__global__ void topk_refheap_wave_kernel(const RefHeapArgs g);
-
-hipError_t launch_topk_refheap(const RefHeapArgs &args, hipStream_t stream)
-{
-    if (args.rows == 0 || (args.cols == 0 && args.row_offsets == nullptr)) return hipSuccess;
-    if (args.knn == 0 || (args.knn > REFHEAP_LDS_MAX && args.heap_scratch == nullptr)) return hipErrorInvalidValue;
-    if (args.stride2 != 1 && args.stride2 != 2) return hipErrorInvalidValue;
-    if (args.row_offsets != nullptr && (args.col_ids == nullptr || args.stride2 != 1)) return hipErrorInvalidValue;
-    if (args.knn <= REFHEAP_WAVE_KNN_ONE_SHOT && !args.force_workgroup_form) {
-        hipLaunchKernelGGL(topk_refheap_wave_kernel, dim3((args.rows + 3u) / 4u), dim3(256), 0, stream, args);
-        return hipGetLastError();
-    }
-    hipLaunchKernelGGL(topk_refheap_kernel, dim3(args.rows), dim3(TOPK_THREADS), 0, stream, args);
-    return hipGetLastError();
-}
-
-// Resumable form (the one-evaluation self kNN in the reference's tie order): a row's heap lives in global memory
-// between launches -- RefHeapMergeArgs -- and each launch continues the replay with the row's next batch of candidates.
-// The drivers feed a row its candidates in ascending sample id over the sequence of launches, which is the order the
-// reference pushes them in (mod.rs:156-181), so the heap goes through the same states.
-__global__ __launch_bounds__(TOPK_THREADS) void refheap_merge_kernel(const RefHeapMergeArgs g)
-{
-    __shared__ float lds_heap[3 * (REFHEAP_LDS_MAX + 1)];
-    __shared__ RefHeapShared sh;
-    const uint32_t row = blockIdx.x, tid = threadIdx.x;
-    if (g.flag != nullptr && g.flag[row] != g.flag_value) return;
-    const uint32_t knn = g.knn, stride2 = g.stride2;
-    const size_t srow = (size_t)(g.state_row_base + row);
-    const uint32_t self_id = g.self_id_base == 0xFFFFFFFFu ? 0xFFFFFFFFu : g.self_id_base + row;
-    RefHeap h{lds_heap, lds_heap + (knn + 1u), reinterpret_cast<uint32_t *>(lds_heap + 2u * (knn + 1u)), 0u, stride2 == 2u};
-    const uint32_t len0 = g.h_len[srow];
-    for (uint32_t x = tid; x < len0; x += TOPK_THREADS) {
-        h.key[x] = g.h_key[srow * knn + x];
-        h.id[x] = g.h_id[srow * knn + x];
-        if (stride2 == 2u) h.d1[x] = g.h_d1[srow * knn + x];
-    }
-    if (tid == 0) {
-        sh.len = len0;
-        sh.ncand = 0;
-    }
-    __syncthreads();
-    if (tid == 0) sh.thr = len0 < knn ? __builtin_inff() : h.key[0];
-    __syncthreads();
-    RefHeapLog alog;   // (thread 0's copy is the one that counts)
-    if (g.log_rec != nullptr) {
-        alog.rec = g.log_rec + srow * g.log_cap * stride2;
-        alog.id = g.log_id + srow * g.log_cap;
-        alog.cap = g.log_cap;
-        alog.len = g.log_len[srow];
-        alog.stride2 = stride2;
-    }
-    const uint32_t cols = g.row_cols != nullptr ? min(g.cols, g.row_cols[row]) : g.cols;
-    const uint32_t *ids = g.cand_ids != nullptr ? g.cand_ids + (size_t)row * g.cols : nullptr;
-    refheap_feed(h, sh, g.keys + (size_t)row * g.key_stride, stride2, cols, knn,
-                 [&](uint32_t q, uint32_t &id) {
-                     id = ids != nullptr ? ids[q] : g.id_base + q;
-                     return id >= g.skip_below && id != self_id;
-                 },
-                 g.seg_bits ? g.seg_bits + (size_t)row * g.seg_bits_stride : nullptr, g.seg_shift != 0u ? g.seg_shift : 6u, &alog);
-    if (tid == 0 && g.log_rec != nullptr) g.log_len[srow] = alog.len;
-    const uint32_t len = sh.len;
-    for (uint32_t x = tid; x < len; x += TOPK_THREADS) {
-        g.h_key[srow * knn + x] = h.key[x];
-        g.h_id[srow * knn + x] = h.id[x];
-        if (stride2 == 2u) g.h_d1[srow * knn + x] = h.d1[x];
-    }
-    if (tid == 0) {
-        g.h_len[srow] = len;
-        g.thr[srow] = len < knn ? 0xFFFFFFFFu : sortable_bits(h.key[0]);
-    }
-}
-
-// The same with ONE WAVE per row (knn <= REFHEAP_WAVE_KNN): what the one-evaluation driver's merges look like at scale is
-// a million rows per band, each fed a few hundred to a few thousand records of which a handful enter the heap -- a
-// 256-thread workgroup per row spends its time in barriers and in the serial drain of one thread while three rows fit
-// a CU.  Here a workgroup is 4 independent rows: no barrier anywhere (a wave's LDS operations execute in order), the heap
-// and the candidate buffer of a row take 4.6 KB of LDS, and 24-32 rows are in flight per CU to hide each other's drains.
+// ---- the feed of one wave per row (knn <= REFHEAP_WAVE_KNN) ----
+// What the one-evaluation driver's merges look like at scale is a million rows per band, each fed a few hundred to a few
+// thousand records of which a handful enter the heap -- a 256-thread workgroup per row spends its time in barriers and in
+// the serial drain of one thread while three rows fit a CU.  Here a workgroup is 4 independent rows: no barrier anywhere (a
+// wave's LDS operations execute in order), the heap and the candidate buffer of a row take 4.6 KB of LDS, and 24-32 rows
+// are in flight per CU to hide each other's drains.
 constexpr uint32_t REFHEAP_WAVE_KNN = 256, REFHEAP_WAVE_CAND = 128;
-static_assert(REFHEAP_WAVE_KNN == REFHEAP_WAVE_KNN_ONE_SHOT, "one constant");
+struct RefHeapWaveShared {   // one row's: a workgroup declares 4
+    float heap[3 * (REFHEAP_WAVE_KNN + 1)];
+    float cand_key[REFHEAP_WAVE_CAND], cand_d1[REFHEAP_WAVE_CAND];
+    uint32_t cand_id[REFHEAP_WAVE_CAND];
+};
 
-__global__ __launch_bounds__(256) void refheap_merge_wave_kernel(const RefHeapMergeArgs g)
+__device__ __forceinline__ void wave_sync()   // orders this wave's LDS traffic as the program states it
 {
-    __shared__ float heap_mem[4][3 * (REFHEAP_WAVE_KNN + 1)];
-    __shared__ float cand_key[4][REFHEAP_WAVE_CAND], cand_d1[4][REFHEAP_WAVE_CAND];
-    __shared__ uint32_t cand_id[4][REFHEAP_WAVE_CAND];
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    const uint32_t row = blockIdx.x * 4u + wave;
-    if (row >= g.rows) return;
-    if (g.flag != nullptr && g.flag[row] != g.flag_value) return;
-    const uint32_t knn = g.knn, stride2 = g.stride2;
-    const uint32_t cols = g.row_cols != nullptr ? min(g.cols, g.row_cols[row]) : g.cols;
-    const uint32_t *ids = g.cand_ids != nullptr ? g.cand_ids + (size_t)row * g.cols : nullptr;
-    const size_t srow = (size_t)(g.state_row_base + row);
-    const uint32_t self_id = g.self_id_base == 0xFFFFFFFFu ? 0xFFFFFFFFu : g.self_id_base + row;
-    RefHeapLog alog;   // (lane 0's copy is the one that counts)
-    if (g.log_rec != nullptr) {
-        alog.rec = g.log_rec + srow * g.log_cap * stride2;
-        alog.id = g.log_id + srow * g.log_cap;
-        alog.cap = g.log_cap;
-        alog.len = g.log_len[srow];
-        alog.stride2 = stride2;
-    }
-    float *hm = heap_mem[wave];
-    RefHeap h{hm, hm + (knn + 1u), reinterpret_cast<uint32_t *>(hm + 2u * (knn + 1u)), 0u, stride2 == 2u};
-    auto wave_sync = [] {   // orders this wave's LDS traffic as the program states it
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-    };
-    uint32_t len = g.h_len[srow];
-    for (uint32_t x = lane; x < len; x += 64u) {
-        h.key[x] = g.h_key[srow * knn + x];
-        h.id[x] = g.h_id[srow * knn + x];
-        if (stride2 == 2u) h.d1[x] = g.h_d1[srow * knn + x];
-    }
-    wave_sync();
-    float thr = len < knn ? __builtin_inff() : h.key[0];
-    uint32_t ncand = 0;
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+}
+
+// refheap_feed for one wave: the same records, id_of, bits (seg_shift 6: one bit per 64 records, 5: per 32) and log; h's
+// memory is sh.heap, h.len (wave-uniform) and thr (the maximum; inf while the heap is not full) describe the heap on entry
+// and on return.  -> whether the heap took part in a drain, i.e. may have changed.  id_of is asked with the key loads, for
+// the marked blocks only and clamped to the row (q < cols is the feed's own test), so that listed ids (a ragged row,
+// explicit candidates) are in flight together with the keys.
+template <class IdOf>
+__device__ __forceinline__ bool refheap_feed_wave(RefHeap &h, RefHeapWaveShared &sh, float &thr, const float *keys, uint32_t stride2,
+                                                  uint32_t cols, uint32_t knn, const IdOf &id_of, const uint32_t *bits, uint32_t seg_shift,
+                                                  RefHeapLog *alog)
+{
+    constexpr uint32_t UNROLL = 4;
+    const uint32_t lane = threadIdx.x & 63u;
+    uint32_t len = h.len, ncand = 0;
     bool dirty = false;
     auto drain = [&]() {   // lane 0: the buffered candidates through the exact push / pop sequence, in order
         wave_sync();
         if (lane == 0u) {
             h.len = len;
             for (uint32_t c = 0; c < ncand; ++c) {
-                const RefHeap::Elt e{cand_key[wave][c], cand_d1[wave][c], cand_id[wave][c]};
-                if (h.push_heap(e, knn)) alog.add(e);
+                const RefHeap::Elt e{sh.cand_key[c], sh.cand_d1[c], sh.cand_id[c]};
+                if (h.push_heap(e, knn) && alog != nullptr) alog->add(e);
             }
             len = h.len;
             thr = h.len < knn ? __builtin_inff() : h.key[0];
@@ -897,10 +834,6 @@ __global__ __launch_bounds__(256) void refheap_merge_wave_kernel(const RefHeapMe
         dirty = dirty || ncand != 0u;
         ncand = 0;
     };
-    const float *keys = g.keys + (size_t)row * g.key_stride;
-    const uint32_t *bits = g.seg_bits ? g.seg_bits + (size_t)row * g.seg_bits_stride : nullptr;
-    constexpr uint32_t UNROLL = 4;
-    const uint32_t seg_shift = g.seg_shift != 0u ? g.seg_shift : 6u;   // 6: one bit per 64 records, 5: per 32
     for (uint32_t q0 = 0; q0 < cols; q0 += 64u * UNROLL) {
         uint32_t mask = (1u << UNROLL) - 1u;   // which 64-record blocks of this trip are read
         uint32_t lane_ok = mask;               // ... and, per block, whether THIS lane's record is in a marked stretch
@@ -920,26 +853,29 @@ __global__ __launch_bounds__(256) void refheap_merge_wave_kernel(const RefHeapMe
             if (mask == 0u) continue;
         }
         float k[UNROLL], d[UNROLL];
+        uint32_t id[UNROLL];
+        bool cand[UNROLL];
 #pragma unroll
-        for (uint32_t j = 0; j < UNROLL; ++j) {
+        for (uint32_t j = 0; j < UNROLL; ++j) {   // (clamped) loads of the marked blocks and their ids, all in flight together
             const uint32_t q = min(q0 + j * 64u + lane, cols - 1u);
             k[j] = (mask >> j) & 1u ? __builtin_nontemporal_load(&keys[(size_t)q * stride2]) : 0.0f;
             d[j] = (stride2 == 2u && ((mask >> j) & 1u)) ? __builtin_nontemporal_load(&keys[(size_t)q * 2u + 1u]) : 0.0f;
+            id[j] = 0u;
+            cand[j] = ((mask >> j) & 1u) && id_of(q, id[j]);
         }
 #pragma unroll
         for (uint32_t j = 0; j < UNROLL; ++j) {
             if (!((mask >> j) & 1u)) continue;
             const uint32_t q = q0 + j * 64u + lane;
-            const uint32_t id = ids != nullptr ? ids[min(q, cols - 1u)] : g.id_base + q;
-            const bool open = len < knn;
-            const bool take = q < cols && ((lane_ok >> j) & 1u) != 0u && id >= g.skip_below && id != self_id && (open || k[j] < thr);
+            const bool open = len < knn;   // not full: everything is pushed
+            const bool take = q < cols && ((lane_ok >> j) & 1u) != 0u && cand[j] && (open || k[j] < thr);
             const uint64_t votes = __ballot(take);
             if (votes == 0ull) continue;
-            if (take) {
+            if (take) {   // ordered compaction: position order = candidate order
                 const uint32_t pos = ncand + (uint32_t)__popcll(votes & ((1ull << lane) - 1ull));
-                cand_key[wave][pos] = k[j];
-                cand_d1[wave][pos] = d[j];
-                cand_id[wave][pos] = id;
+                sh.cand_key[pos] = k[j];
+                sh.cand_d1[pos] = d[j];
+                sh.cand_id[pos] = id[j];
             }
             ncand += (uint32_t)__popcll(votes);
             // (while the heap fills, drain at once: the threshold must exist before more is buffered)
@@ -947,106 +883,161 @@ __global__ __launch_bounds__(256) void refheap_merge_wave_kernel(const RefHeapMe
         }
     }
     if (ncand != 0u) drain();
-    if (lane == 0u && g.log_rec != nullptr) g.log_len[srow] = alog.len;
-    if (dirty) {
-        for (uint32_t x = lane; x < len; x += 64u) {
-            g.h_key[srow * knn + x] = h.key[x];
-            g.h_id[srow * knn + x] = h.id[x];
-            if (stride2 == 2u) g.h_d1[srow * knn + x] = h.d1[x];
-        }
-        if (lane == 0u) {
-            g.h_len[srow] = len;
-            g.thr[srow] = len < knn ? 0xFFFFFFFFu : sortable_bits(h.key[0]);
-        }
+    h.len = len;
+    return dirty;
+}
+}  // namespace
+
+// ---- kernels ----
+// One-shot form, one workgroup per row: the row of RefHeapRow, padded with (row, 1.0) behind fewer than knn candidates.
+__global__ __launch_bounds__(TOPK_THREADS) void topk_refheap_kernel(const RefHeapArgs g)
+{
+    __shared__ float lds_heap[3 * (REFHEAP_LDS_MAX + 1)];
+    __shared__ RefHeapShared sh;
+    const uint32_t row = blockIdx.x + g.first_row, tid = threadIdx.x;
+    const uint32_t knn = g.knn, stride2 = g.stride2;
+    const RefHeapRow r = refheap_one_shot_row(g, row);
+    RefHeap h = RefHeap::at(g.heap_scratch ? g.heap_scratch + (size_t)blockIdx.x * 3u * (knn + 1u) : lds_heap, knn, stride2 == 2u);
+    if (tid == 0) {
+        sh.len = 0;
+        sh.ncand = 0;
+        sh.thr = __builtin_inff();
     }
+    __syncthreads();
+    if (r.cols != 0u) {
+        refheap_feed(h, sh, r.keys, stride2, r.cols, knn,
+                     [&](uint32_t q, uint32_t &id) {
+                         id = r.ids ? r.ids[q] : q;
+                         return q != r.self_id || r.ids != nullptr;
+                     },
+                     nullptr);
+    }
+    if (tid == 0) {
+        h.len = sh.len;
+        h.into_sorted();
+    }
+    __syncthreads();
+    refheap_write_sorted(h, sh.len, row, knn, g.ani_undo, r.ragged, g.out_idx, g.out_d0, g.out_d1, tid, TOPK_THREADS);
 }
 
-// The ONE-SHOT replay (topk_refheap_kernel's job: a whole dense row, or a ragged candidate row of the precluster mode) with
-// one wave per row, for the same reason: the precluster call at 400 000 rows x ~800 listed candidates spent 64 ms in the
+// The same with one wave per row: the precluster call at 400 000 rows x ~800 listed candidates spent 64 ms in the
 // one-workgroup-per-row form -- as long as the distances themselves -- against 7 ms for the canonical radix select.
 __global__ __launch_bounds__(256) void topk_refheap_wave_kernel(const RefHeapArgs g)
 {
-    __shared__ float heap_mem[4][3 * (REFHEAP_WAVE_KNN + 1)];
-    __shared__ float cand_key[4][REFHEAP_WAVE_CAND], cand_d1[4][REFHEAP_WAVE_CAND];
-    __shared__ uint32_t cand_id[4][REFHEAP_WAVE_CAND];
+    __shared__ RefHeapWaveShared shared[4];
     const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
     if (blockIdx.x * 4u + wave >= g.rows) return;
     const uint32_t row = blockIdx.x * 4u + wave + g.first_row;
     const uint32_t knn = g.knn, stride2 = g.stride2;
-    const bool ragged = g.row_offsets != nullptr;
-    const uint64_t row_base = ragged ? g.row_offsets[row] : 0ull;
-    const uint32_t cols = ragged ? (uint32_t)(g.row_offsets[row + 1] - row_base) : g.cols;
-    const uint32_t self_id = g.self_id_base == 0xFFFFFFFFu ? 0xFFFFFFFFu : g.self_id_base + row;
-    const float *keys = ragged ? g.keys + row_base * stride2 : g.keys + (size_t)row * g.key_stride;
-    const uint32_t *ids = ragged ? g.col_ids + row_base : nullptr;
-    float *hm = heap_mem[wave];
-    RefHeap h{hm, hm + (knn + 1u), reinterpret_cast<uint32_t *>(hm + 2u * (knn + 1u)), 0u, stride2 == 2u};
-    auto wave_sync = [] {   // orders this wave's LDS traffic as the program states it
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-    };
-    uint32_t len = 0, ncand = 0;
+    const RefHeapRow r = refheap_one_shot_row(g, row);
+    RefHeapWaveShared &sh = shared[wave];
+    RefHeap h = RefHeap::at(sh.heap, knn, stride2 == 2u);
     float thr = __builtin_inff();
-    auto drain = [&]() {   // lane 0: the buffered candidates through the exact push / pop sequence, in order
-        wave_sync();
-        if (lane == 0u) {
-            h.len = len;
-            for (uint32_t c = 0; c < ncand; ++c) (void)h.push_heap(RefHeap::Elt{cand_key[wave][c], cand_d1[wave][c], cand_id[wave][c]}, knn);
-            len = h.len;
-            thr = h.len < knn ? __builtin_inff() : h.key[0];
-        }
-        wave_sync();
-        len = __shfl(len, 0);
-        thr = __shfl(thr, 0);
-        ncand = 0;
-    };
-    constexpr uint32_t UNROLL = 4;
-    for (uint32_t q0 = 0; q0 < cols; q0 += 64u * UNROLL) {
-        float k[UNROLL], d[UNROLL];
-        uint32_t id[UNROLL];
-#pragma unroll
-        for (uint32_t j = 0; j < UNROLL; ++j) {   // unconditional (clamped) loads, all in flight together
-            const uint32_t q = min(q0 + j * 64u + lane, cols - 1u);
-            k[j] = __builtin_nontemporal_load(&keys[(size_t)q * stride2]);
-            d[j] = stride2 == 2u ? __builtin_nontemporal_load(&keys[(size_t)q * 2u + 1u]) : 0.0f;
-            id[j] = ids ? ids[q] : q;
-        }
-#pragma unroll
-        for (uint32_t j = 0; j < UNROLL; ++j) {
-            const uint32_t q = q0 + j * 64u + lane;
-            const bool open = len < knn;
-            const bool take = q < cols && (ids != nullptr || q != self_id) && (open || k[j] < thr);
-            const uint64_t votes = __ballot(take);
-            if (votes == 0ull) continue;
-            if (take) {
-                const uint32_t pos = ncand + (uint32_t)__popcll(votes & ((1ull << lane) - 1ull));
-                cand_key[wave][pos] = k[j];
-                cand_d1[wave][pos] = d[j];
-                cand_id[wave][pos] = id[j];
-            }
-            ncand += (uint32_t)__popcll(votes);
-            // (while the heap fills, drain at once: the threshold must exist before more is buffered)
-            if (open || ncand + 64u > REFHEAP_WAVE_CAND) drain();
-        }
-    }
-    if (ncand != 0u) drain();
+    refheap_feed_wave(h, sh, thr, r.keys, stride2, r.cols, knn,
+                      [&](uint32_t q, uint32_t &id) {
+                          id = r.ids ? r.ids[q] : q;
+                          return q != r.self_id || r.ids != nullptr;
+                      },
+                      nullptr, 6u, nullptr);
     wave_sync();
-    if (lane == 0u) {
-        h.len = len;
-        h.into_sorted();
-    }
+    if (lane == 0u) h.into_sorted();
     wave_sync();
-    for (uint32_t x = lane; x < knn; x += 64u) {
-        const size_t o = (size_t)row * knn + x;
-        if (x < len) {
-            g.out_idx[o] = h.id[x];
-            g.out_d0[o] = g.ani_undo ? 1.0f - h.key[x] : h.key[x];
-            if (stride2 == 2u && g.out_d1) g.out_d1[o] = h.d1[x];
-        } else if (ragged) {
-            g.out_idx[o] = row;
-            g.out_d0[o] = 1.0f;
-        }
+    refheap_write_sorted(h, h.len, row, knn, g.ani_undo, r.ragged, g.out_idx, g.out_d0, g.out_d1, lane, 64u);
+}
+
+// Resumable form (the one-evaluation self kNN in the reference's tie order): a row's heap lives in global memory
+// between launches -- RefHeapMergeArgs -- and each launch continues the replay with the row's next batch of candidates.
+// The drivers feed a row its candidates in ascending sample id over the sequence of launches, which is the order the
+// reference pushes them in (mod.rs:156-181), so the heap goes through the same states.
+__global__ __launch_bounds__(TOPK_THREADS) void refheap_merge_kernel(const RefHeapMergeArgs g)
+{
+    __shared__ float lds_heap[3 * (REFHEAP_LDS_MAX + 1)];
+    __shared__ RefHeapShared sh;
+    const uint32_t row = blockIdx.x, tid = threadIdx.x;
+    if (g.flag != nullptr && g.flag[row] != g.flag_value) return;
+    const uint32_t knn = g.knn, stride2 = g.stride2;
+    const size_t srow = (size_t)(g.state_row_base + row);
+    const uint32_t self_id = g.self_id_base == 0xFFFFFFFFu ? 0xFFFFFFFFu : g.self_id_base + row;
+    RefHeap h = RefHeap::at(lds_heap, knn, stride2 == 2u);
+    const uint32_t len0 = refheap_load_state(h, g.h_key, g.h_id, g.h_d1, g.h_len, srow, knn, tid, TOPK_THREADS);
+    if (tid == 0) {
+        sh.len = len0;
+        sh.ncand = 0;
     }
+    __syncthreads();
+    if (tid == 0) sh.thr = len0 < knn ? __builtin_inff() : h.key[0];
+    __syncthreads();
+    RefHeapLog alog = RefHeapLog::of(g, srow);   // (thread 0's copy is the one that counts)
+    const uint32_t cols = g.row_cols != nullptr ? min(g.cols, g.row_cols[row]) : g.cols;
+    const uint32_t *ids = g.cand_ids != nullptr ? g.cand_ids + (size_t)row * g.cols : nullptr;
+    refheap_feed(h, sh, g.keys + (size_t)row * g.key_stride, stride2, cols, knn,
+                 [&](uint32_t q, uint32_t &id) {
+                     id = ids != nullptr ? ids[q] : g.id_base + q;
+                     return id >= g.skip_below && id != self_id;
+                 },
+                 g.seg_bits ? g.seg_bits + (size_t)row * g.seg_bits_stride : nullptr, g.seg_shift != 0u ? g.seg_shift : 6u, &alog);
+    if (tid == 0 && g.log_rec != nullptr) g.log_len[srow] = alog.len;
+    refheap_store_state(h, sh.len, g, srow, tid, TOPK_THREADS);
+}
+
+// The same with one wave per row; a heap that no drain touched is not written back.
+__global__ __launch_bounds__(256) void refheap_merge_wave_kernel(const RefHeapMergeArgs g)
+{
+    __shared__ RefHeapWaveShared shared[4];
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    const uint32_t row = blockIdx.x * 4u + wave;
+    if (row >= g.rows) return;
+    if (g.flag != nullptr && g.flag[row] != g.flag_value) return;
+    const uint32_t knn = g.knn, stride2 = g.stride2;
+    const uint32_t cols = g.row_cols != nullptr ? min(g.cols, g.row_cols[row]) : g.cols;
+    const uint32_t *ids = g.cand_ids != nullptr ? g.cand_ids + (size_t)row * g.cols : nullptr;
+    const size_t srow = (size_t)(g.state_row_base + row);
+    const uint32_t self_id = g.self_id_base == 0xFFFFFFFFu ? 0xFFFFFFFFu : g.self_id_base + row;
+    RefHeapLog alog = RefHeapLog::of(g, srow);   // (lane 0's copy is the one that counts)
+    RefHeapWaveShared &sh = shared[wave];
+    RefHeap h = RefHeap::at(sh.heap, knn, stride2 == 2u);
+    h.len = refheap_load_state(h, g.h_key, g.h_id, g.h_d1, g.h_len, srow, knn, lane, 64u);
+    wave_sync();
+    float thr = h.len < knn ? __builtin_inff() : h.key[0];
+    const bool dirty = refheap_feed_wave(h, sh, thr, g.keys + (size_t)row * g.key_stride, stride2, cols, knn,
+                                         [&](uint32_t q, uint32_t &id) {
+                                             id = ids != nullptr ? ids[q] : g.id_base + q;
+                                             return id >= g.skip_below && id != self_id;
+                                         },
+                                         g.seg_bits ? g.seg_bits + (size_t)row * g.seg_bits_stride : nullptr,
+                                         g.seg_shift != 0u ? g.seg_shift : 6u, &alog);
+    if (lane == 0u && g.log_rec != nullptr) g.log_len[srow] = alog.len;
+    if (dirty) refheap_store_state(h, h.len, g, srow, lane, 64u);
+}
+
+// ... and the resumable form's last step: into_sorted_vec of every row's heap -> the public output form.
+__global__ __launch_bounds__(64) void refheap_finalize_kernel(const float *h_key, const uint32_t *h_id, const float *h_d1, const uint32_t *h_len,
+                                                              uint32_t rows, uint32_t knn, int ani_undo, uint64_t *out_idx, float *out_d0,
+                                                              float *out_d1)
+{
+    __shared__ float lds_heap[3 * (REFHEAP_LDS_MAX + 1)];
+    const uint32_t row = blockIdx.x, tid = threadIdx.x;
+    RefHeap h = RefHeap::at(lds_heap, knn, h_d1 != nullptr);
+    h.len = refheap_load_state(h, h_key, h_id, h_d1, h_len, row, knn, tid, 64u);
+    __syncthreads();
+    if (tid == 0) h.into_sorted();
+    __syncthreads();
+    refheap_write_sorted(h, h.len, row, knn, ani_undo, false, out_idx, out_d0, out_d1, tid, 64u);
+}
+
+// ---- launchers ----
+hipError_t launch_topk_refheap(const RefHeapArgs &args, hipStream_t stream)
+{
+    if (args.rows == 0 || (args.cols == 0 && args.row_offsets == nullptr)) return hipSuccess;
+    if (args.knn == 0 || (args.knn > REFHEAP_LDS_MAX && args.heap_scratch == nullptr)) return hipErrorInvalidValue;
+    if (args.stride2 != 1 && args.stride2 != 2) return hipErrorInvalidValue;
+    if (args.row_offsets != nullptr && (args.col_ids == nullptr || args.stride2 != 1)) return hipErrorInvalidValue;
+    if (args.knn <= REFHEAP_WAVE_KNN && !args.force_workgroup_form) {
+        hipLaunchKernelGGL(topk_refheap_wave_kernel, dim3((args.rows + 3u) / 4u), dim3(256), 0, stream, args);
+        return hipGetLastError();
+    }
+    hipLaunchKernelGGL(topk_refheap_kernel, dim3(args.rows), dim3(TOPK_THREADS), 0, stream, args);
+    return hipGetLastError();
 }
 
 hipError_t launch_refheap_merge(const RefHeapMergeArgs &args, hipStream_t stream)
@@ -1061,34 +1052,6 @@ hipError_t launch_refheap_merge(const RefHeapMergeArgs &args, hipStream_t stream
     }
     hipLaunchKernelGGL(refheap_merge_kernel, dim3(args.rows), dim3(TOPK_THREADS), 0, stream, args);
     return hipGetLastError();
-}
-
-// ... and its last step: into_sorted_vec of every row's heap -> the public output form.
-__global__ __launch_bounds__(64) void refheap_finalize_kernel(const float *h_key, const uint32_t *h_id, const float *h_d1, const uint32_t *h_len,
-                                                              uint32_t rows, uint32_t knn, int ani_undo, uint64_t *out_idx, float *out_d0,
-                                                              float *out_d1)
-{
-    __shared__ float lds_heap[3 * (REFHEAP_LDS_MAX + 1)];
-    const uint32_t row = blockIdx.x, tid = threadIdx.x;
-    RefHeap h{lds_heap, lds_heap + (knn + 1u), reinterpret_cast<uint32_t *>(lds_heap + 2u * (knn + 1u)), 0u, h_d1 != nullptr};
-    const uint32_t len = h_len[row];
-    for (uint32_t x = tid; x < len; x += 64u) {
-        h.key[x] = h_key[(size_t)row * knn + x];
-        h.id[x] = h_id[(size_t)row * knn + x];
-        if (h_d1) h.d1[x] = h_d1[(size_t)row * knn + x];
-    }
-    __syncthreads();
-    if (tid == 0) {
-        h.len = len;
-        h.into_sorted();
-    }
-    __syncthreads();
-    for (uint32_t x = tid; x < len; x += 64u) {
-        const size_t o = (size_t)row * knn + x;
-        out_idx[o] = h.id[x];
-        out_d0[o] = ani_undo ? 1.0f - h.key[x] : h.key[x];
-        if (h_d1 && out_d1) out_d1[o] = h.d1[x];
-    }
 }
 
 hipError_t launch_refheap_finalize(const float *h_key, const uint32_t *h_id, const float *h_d1, const uint32_t *h_len, uint32_t rows,
