@@ -392,4 +392,46 @@ __device__ __forceinline__ void store_coreacc(const PairArgs &g, uint32_t i, uin
     ((float2 *)g.out)[pair_out_index(g, i, jcol)] = coreacc_value(g, i, jcol, s0, s1, s2);
 }
 
+// THE HALF-CHUNK COUNT: a wave reads a (sample, k) slice as ONE contiguous run, lane l the l-th half chunk of a trip (7 planes,
+// 56 bytes; a trip is 3 584 bytes -- the form pair_cand.hip measured at 0.88 of the HBM peak), and the two halves of a chunk
+// meet between neighbouring lanes.  Three steps, the loads left to the caller (who clamps the address, branches around the
+// load or requests a trip ahead -- that order is what was measured):
+//   half_chunk_fold   the mismatch words of this lane's seven planes, a against b;
+//   half_chunk_share  the other seven planes of the chunk sit in lane l ^ 1: a bin matches iff all 14 agree.  Returns the
+//                     MISMATCHES of the chunk in its even lane, 0 in the odd one and where the half chunk is not `counted`
+//                     (a lane past the slice's end);
+//   wave_sum          the 64 shares summed: four row shifts leave each row of 16 lanes' total in its last lane, four
+//                     v_readlane add them up (wave-uniform result).
+__device__ __forceinline__ void half_chunk_fold(const uint2 *a, const uint2 *b, uint32_t &mlo, uint32_t &mhi)
+{
+#pragma unroll
+    for (int q = 0; q < 7; ++q) {
+        mlo = acc_mismatch<true>(mlo, a[q].x, b[q].x);
+        mhi = acc_mismatch<true>(mhi, a[q].y, b[q].y);
+    }
+}
+
+__device__ __forceinline__ uint32_t half_chunk_share(uint32_t mlo, uint32_t mhi, uint32_t lane, bool counted)
+{
+    mlo |= (uint32_t)__builtin_amdgcn_update_dpp(0, (int)mlo, 0xB1, 0xF, 0xF, true);   // quad_perm [1, 0, 3, 2]
+    mhi |= (uint32_t)__builtin_amdgcn_update_dpp(0, (int)mhi, 0xB1, 0xF, 0xF, true);
+    return ((lane & 1u) == 0u && counted) ? (uint32_t)__builtin_popcount(mlo) + (uint32_t)__builtin_popcount(mhi) : 0u;
+}
+
+template <int CTRL>
+__device__ __forceinline__ uint32_t dpp_add(uint32_t v)
+{
+    return v + (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, CTRL, 0xF, 0xF, true);
+}
+
+__device__ __forceinline__ uint32_t wave_sum(uint32_t part)
+{
+    part = dpp_add<0x111>(part);   // row_shr:1
+    part = dpp_add<0x112>(part);   // row_shr:2
+    part = dpp_add<0x114>(part);   // row_shr:4
+    part = dpp_add<0x118>(part);   // row_shr:8
+    return (uint32_t)__builtin_amdgcn_readlane((int)part, 15) + (uint32_t)__builtin_amdgcn_readlane((int)part, 31) +
+           (uint32_t)__builtin_amdgcn_readlane((int)part, 47) + (uint32_t)__builtin_amdgcn_readlane((int)part, 63);
+}
+
 }  // namespace skl

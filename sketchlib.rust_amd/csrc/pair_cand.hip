@@ -90,10 +90,9 @@ __global__ __launch_bounds__(LANES *WAVES_PER_WG) void pair_cand_kernel(const Ca
 // lines at a time, and the HBM-side traffic runs at 4.5 TB/s for the 3.5 KB blocks it actually wants.  Here a wave takes
 // the candidates one after the other and reads each as ONE contiguous run (lane l takes the l-th half chunk: planes 0-6 or
 // 7-13 of a chunk, 56 bytes; sketches of more than 32 chunks take several trips), ORs the two halves of a chunk between
-// neighbouring lanes (DPP), counts, and sums the 64 partial counts with four DPP row shifts + four v_readlane.  ~3x the
+// neighbouring lanes (DPP), counts, and sums the 64 partial counts with four DPP row shifts + four v_readlane (half_chunk_fold,
+// half_chunk_share and wave_sum, device_common.hpp).  ~3x the
 // VALU instructions per pair of the form above, which is nothing: the kernel waits for memory either way.
-#define SKL_DPP_ADD(v, ctrl) ((v) + (uint32_t)__builtin_amdgcn_update_dpp(0, (int)(v), (ctrl), 0xF, 0xF, true))
-
 // TRIPS = 1 ... 5: sketches of up to 32 x TRIPS chunks -- the ROW's planes are read once per work item and stay in
 // registers (7 x 8 bytes per lane and trip), so a candidate costs seven loads per trip and nothing else; TRIPS = 0: any
 // size, the row's planes re-read (from L1) beside every candidate's.
@@ -136,16 +135,9 @@ __global__ __launch_bounds__(LANES *WAVES_PER_WG) void pair_cand_rows_kernel(con
                 uint2 b[7];
 #pragma unroll
                 for (int q = 0; q < 7; ++q) b[q] = pj[(size_t)h * 7 + q];      // one plane (lo, hi) each: the wave's 64 x 56 B are contiguous
-#pragma unroll
-                for (int q = 0; q < 7; ++q) {
-                    mlo = acc_mismatch<true>(mlo, a[q].x, b[q].x);
-                    mhi = acc_mismatch<true>(mhi, a[q].y, b[q].y);
-                }
+                half_chunk_fold(a, b, mlo, mhi);
             }
-            // the other seven planes of this chunk sit in the neighbouring lane (h ^ 1): a bin matches iff all 14 agree
-            mlo |= (uint32_t)__builtin_amdgcn_update_dpp(0, (int)mlo, 0xB1, 0xF, 0xF, true);   // quad_perm [1, 0, 3, 2]
-            mhi |= (uint32_t)__builtin_amdgcn_update_dpp(0, (int)mhi, 0xB1, 0xF, 0xF, true);
-            if ((lane & 1u) == 0u && h < halves) part += (uint32_t)__builtin_popcount(mlo) + (uint32_t)__builtin_popcount(mhi);
+            part += half_chunk_share(mlo, mhi, lane, h < halves);
         };
         if constexpr (TRIPS > 0) {
 #pragma unroll
@@ -159,13 +151,7 @@ __global__ __launch_bounds__(LANES *WAVES_PER_WG) void pair_cand_rows_kernel(con
                 one_trip(h, a);
             }
         }
-        // sum over the wave: four row shifts leave each row of 16 lanes' total in its last lane
-        part = SKL_DPP_ADD(part, 0x111);   // row_shr:1
-        part = SKL_DPP_ADD(part, 0x112);   // row_shr:2
-        part = SKL_DPP_ADD(part, 0x114);   // row_shr:4
-        part = SKL_DPP_ADD(part, 0x118);   // row_shr:8
-        const uint32_t total = (uint32_t)__builtin_amdgcn_readlane((int)part, 15) + (uint32_t)__builtin_amdgcn_readlane((int)part, 31) +
-                               (uint32_t)__builtin_amdgcn_readlane((int)part, 47) + (uint32_t)__builtin_amdgcn_readlane((int)part, 63);
+        const uint32_t total = wave_sum(part);
         if (lane == cc) mism_mine = total;
     }
     const bool active = lane < cnt && (!c.symmetric || j_mine > row);
@@ -182,7 +168,6 @@ __global__ __launch_bounds__(LANES *WAVES_PER_WG) void pair_cand_rows_kernel(con
         }
     }
 }
-#undef SKL_DPP_ADD
 
 hipError_t launch_pair_cand(const CandArgs &c_in, const PairArgs &g, hipStream_t stream)
 {

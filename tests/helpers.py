@@ -26,3 +26,13 @@ def load_fixture_bins(name):
 def rust_f32(x):
     """Rust's `{}` for f32: shortest round-trip digits, positional."""
     return np.format_float_positional(np.float32(x), unique=True, trim="-")
+
+
+def mixed(n, kmers, ss64, n_random, n_clusters=3, seed=11):
+    """The first n_random samples are random sketches (Set U: chance matches only), the others come in n_clusters clusters of
+    relatives (Set R), interleaved by cluster."""
+    from sketchlib.rust_amd import synth
+
+    u = synth.set_u(n_random, len(kmers), ss64, seed=synth.SEED_U + seed)
+    r = synth.set_r(n - n_random, kmers, ss64, n_clusters=n_clusters, seed=synth.SEED_R + seed)
+    return np.ascontiguousarray(np.concatenate([u, r], axis=0))

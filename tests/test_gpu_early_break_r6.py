@@ -12,19 +12,12 @@ Everything against the oracle's core_acc_dist."""
 import numpy as np
 import pytest
 
+from helpers import mixed as _mixed
 from sketchlib.rust_amd import synth
 
 pytestmark = pytest.mark.gpu
 
 KMERS = [15, 19, 23, 27, 31]
-
-
-def _mixed(n, kmers, ss64, n_random, n_clusters=3, seed=11):
-    """The first n_random samples are random sketches (Set U: chance matches only), the others come in n_clusters clusters of
-    relatives (Set R), interleaved by cluster."""
-    u = synth.set_u(n_random, len(kmers), ss64, seed=synth.SEED_U + seed)
-    r = synth.set_r(n - n_random, kmers, ss64, n_clusters=n_clusters, seed=synth.SEED_R + seed)
-    return np.ascontiguousarray(np.concatenate([u, r], axis=0))
 
 
 def _chance_regime_is_exercised(oracle, o, exp, ss64):
