@@ -363,14 +363,18 @@ static long long env_int(const char *name, long long dflt)
 Knobs read_knobs()
 {
     Knobs k;
-    // The product library reads NINE switches: the timing cadence, the device topology the tile order assumes, and the knobs
-    // with which the tests force the banded / sliced / 32-row forms (and the inverted query's bands) on inputs small enough for the oracle.  Everything that
+    // The product library reads TEN switches: the timing cadence, the device topology the tile order assumes, and the knobs
+    // with which the tests force the banded / sliced / 32-row forms (and the inverted query's bands, the sketching call's upload batches) on inputs small enough for the oracle.  Everything that
     // exists only to time one form against another ("A/B only, results identical") is read by the A/B build alone (-DSKL_AB),
     // where scripts/ab_sweep.py, scripts/forced_switch_suites.sh and the tests marked `ab_library` find it.
     k.timing_every = std::max(0ll, env_int("SKL_TIMING_EVERY", 0));
     k.sliced_max_pairs = env_int("SKL_SLICED_MAX_PAIRS", -1);
     k.knn_band_rows = std::max(0ll, env_int("SKL_KNN_BAND_ROWS", 0));
     k.invq_band_bytes = std::max(0ll, env_int("SKL_INVQ_BAND_BYTES", 0));
+    {
+        const long long w = env_int("SKL_SKETCH_BATCH_WORDS", 0);   // 0 or unset: 8 Mi; any other value: at least 1
+        k.sketch_batch_words = w == 0 ? 0 : std::max(1ll, w);
+    }
     k.tail_slices = (int)std::min(8ll, std::max(0ll, env_int("SKL_TAIL_SLICES", 4)));
     k.tail_max_pct = env_int("SKL_TAIL_MAX_PCT", 90);
     k.tile32_min = env_int("SKL_TILE32_MIN", 8ll << 20);

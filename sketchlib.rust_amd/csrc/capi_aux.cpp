@@ -175,8 +175,8 @@ static int sketch_signs_impl(skl_ctx *ctx, const uint8_t *codes, const uint32_t 
     a.signs = (uint64_t *)d_signs;
     a.lds_form = lds_form ? 1u : 0u;
 
-    // batches of whole samples, ~8 Mi words (128 Mi bases) each
-    constexpr uint64_t BATCH_WORDS = 8ull << 20;
+    // batches of whole samples, ~8 Mi words (128 Mi bases) each (SKL_SKETCH_BATCH_WORDS: tests cut small inputs into several)
+    const uint64_t BATCH_WORDS = ctx->knobs.sketch_batch_words > 0 ? (uint64_t)ctx->knobs.sketch_batch_words : 8ull << 20;
     std::vector<size_t> cuts{0};
     for (size_t s = 0; s < n_samples; ++s) {
         if (word_begin[s + 1] - word_begin[cuts.back()] >= BATCH_WORDS && s + 1 < n_samples) cuts.push_back(s + 1);
@@ -252,9 +252,12 @@ static int sketch_signs_impl(skl_ctx *ctx, const uint8_t *codes, const uint32_t 
         }
         SKL_TRY(download(b));
     }
-    ctx->last_kernel = lds_form ? "skl::nthash_binmin_lds_kernel (bases staged in LDS as 2-bit codes, 128 window starts per thread, rolling "
-                                  "canonical ntHash through a fused 16-entry step table, bin minima in LDS)"
-                                : "skl::nthash_binmin_kernel (256 window starts per thread, rolling canonical ntHash, atomicMin per bin)";
+    ctx->last_kernel = !lds_form ? "skl::nthash_binmin_kernel (256 window starts per thread, rolling canonical ntHash, atomicMin per bin)"
+                       : num_bins <= (uint64_t)sketch_lds_bins_max()
+                           ? "skl::nthash_binmin_lds_kernel (bases staged in LDS as 2-bit codes, 128 window starts per thread, rolling "
+                             "canonical ntHash through a fused 16-entry step table, bin minima in LDS)"
+                           : "skl::nthash_binmin_lds_kernel (bases staged in LDS as 2-bit codes, 128 window starts per thread, rolling "
+                             "canonical ntHash through a fused 16-entry step table, bin minima in global memory)";
     HIP_TRY(hipStreamSynchronize(ctx->aux_stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     // The sketching buffers belong to the context so that a run of sketch calls does not allocate per call -- but beyond 1 GiB

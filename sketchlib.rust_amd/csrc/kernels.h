@@ -352,6 +352,7 @@ hipError_t launch_sketch_signs(const SketchArgs &args, hipStream_t stream);
 int sketch_span();
 int sketch_span_lds();
 int sketch_wg_lds();   // threads (= spans) per workgroup of the LDS-staged kernel: a sample's span count is padded to a multiple
+int sketch_lds_bins_max();   // most bins whose minima the LDS-staged kernel keeps in LDS; above it they stay in global memory
 
 // Survivors of the read sketcher's count filter (read_survivors.hip, skl_reads_survivors): every valid window
 // of every (sample, k) stream in a range of window starts whose sign is below its bin's threshold.

@@ -307,5 +307,6 @@ hipError_t launch_sketch_signs(const SketchArgs &args, hipStream_t stream)
 int sketch_span() { return SKETCH_SPAN; }
 int sketch_span_lds() { return SPAN2; }
 int sketch_wg_lds() { return WG2; }
+int sketch_lds_bins_max() { return LDS_BINS_MAX; }
 
 }  // namespace skl
