@@ -427,6 +427,26 @@ int skl_self_dists_knn_candidates(skl_ctx *ctx, const skl_sketches *s, const skl
                                   size_t knn, const uint64_t *row_offsets, const uint32_t *cand,
                                   uint64_t *out_idx, float *out_d0);
 
+/* Distances of an explicit LIST of sample pairs: for every entry x the value the dense calls store for that pair --
+ * core_acc_dist + simple_linear_regression (src/distances/jaccard.rs:61-142) as (core, acc), or the single-k Jaccard
+ * distance / ANI (src/distances/mod.rs:83-100; what skl_self_dists_all stores, not the kNN key) -- at out[x * ncols ...),
+ * ncols = 2 (core, acc interleaved) or 1.  Output position equals input position: the list is neither sorted nor
+ * deduplicated, and any order, orientation and repeats are allowed.  Self form: both indices are samples of `s`, and an
+ * entry with pair_a[x] == pair_b[x] gets the distance of a sample to itself ((0, 0); 0; ANI 1).  Cross form: pair_ref[x]
+ * is a sample of `ref`, pair_query[x] one of `query`; a completeness correction applies when BOTH slabs carry a vector
+ * (jaccard.rs:36).  Consecutive entries with the same first sample are evaluated together (its sketch is read once per 64
+ * of them), so a list grouped by first sample -- the output of a kNN call -- is the cheap order; a shuffled list costs one
+ * more record read per entry.  The lists are host pointers; they are uploaded and processed in bands of 64 Mi entries
+ * (SKL_PAIRS_BAND).  An index >= the side's sample count is SKL_ERR_INVALID_ARG (the message names the entry) before
+ * anything is launched or written; n_pairs == 0 is SKL_OK and touches nothing.  With out_on_device != 0 the results are in
+ * place, and the stream idle, when the call returns.  Every k-mer count and sketch size the dense calls take. */
+int skl_self_dists_pairs(skl_ctx *ctx, const skl_sketches *s, const skl_dist_params *p,
+                         const uint32_t *pair_a, const uint32_t *pair_b, size_t n_pairs,
+                         float *out, int out_on_device);
+int skl_cross_dists_pairs(skl_ctx *ctx, const skl_sketches *ref, const skl_sketches *query, const skl_dist_params *p,
+                          const uint32_t *pair_ref, const uint32_t *pair_query, size_t n_pairs,
+                          float *out, int out_on_device);
+
 /* cross_dists_knn (src/distances/mod.rs:306-395): rows = queries, neighbours
  * index refs; knn must already be clamped to <= n_ref (mod.rs:325).
  * Against 131 072 references or more (single-k keys, no completeness correction) the references reach a query in ascending

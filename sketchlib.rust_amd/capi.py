@@ -102,6 +102,8 @@ _SIG = [
     ("skl_cross_dists_knn_rows", C.c_int, [_P, _P, _P, C.POINTER(DistParams), C.c_size_t,
                                            C.c_size_t, C.c_size_t, _P, _P, _P, C.c_int]),
     ("skl_self_dists_knn_candidates", C.c_int, [_P, _P, C.POINTER(DistParams), C.c_size_t, _P, _P, _P, _P]),
+    ("skl_self_dists_pairs", C.c_int, [_P, _P, C.POINTER(DistParams), _P, _P, C.c_size_t, _P, C.c_int]),
+    ("skl_cross_dists_pairs", C.c_int, [_P, _P, _P, C.POINTER(DistParams), _P, _P, C.c_size_t, _P, C.c_int]),
     ("skl_shared_bins_max_samples", C.c_size_t, []),
     ("skl_self_dists_knn_shared_bins", C.c_int, [_P, _P, C.POINTER(DistParams), C.c_size_t, _P, C.c_size_t, _P, _P, _P]),
     ("skl_knn_band_rows", C.c_size_t, [_P, C.POINTER(DistParams), C.c_size_t]),
@@ -584,6 +586,45 @@ def self_dists_knn_candidates(ctx, s, p, knn, row_offsets, cand):
                                                 cand.ctypes.data if cand.size else None, idx.ctypes.data,
                                                 d0.ctypes.data))
     return idx, d0
+
+
+def _pair_list(x):
+    x = np.asarray(x)
+    if x.dtype != np.uint32:
+        if x.size and not np.issubdtype(x.dtype, np.integer):
+            raise ValueError(f"sample indices must be integers, not {x.dtype}")
+        if x.size and (int(x.min()) < 0 or int(x.max()) > 0xFFFFFFFF):   # (would wrap in the conversion)
+            raise ValueError("sample index out of the uint32 range")
+    return np.ascontiguousarray(x, dtype=np.uint32).reshape(-1)
+
+
+def _pair_lists(a, b):
+    a, b = _pair_list(a), _pair_list(b)
+    if a.size != b.size:
+        raise ValueError(f"the two index lists differ in length ({a.size} and {b.size})")
+    return a, b
+
+
+def self_dists_pairs(ctx, s, p, a, b, out=None):
+    """Distances of the listed pairs (a[x], b[x]) of one slab -> [len(a), ncols] f32, entry x at out[x]
+    (skl_self_dists_pairs: any order, orientation and repeats; a[x] == b[x] allowed).  `out`: a numpy array or a
+    device tensor of that shape instead."""
+    a, b = _pair_lists(a, b)
+    if out is None:
+        out = np.zeros((a.size, ncols(p)), dtype=np.float32)
+    addr, dev = _ptr(out)
+    _check(load().skl_self_dists_pairs(ctx._h, s._h, C.byref(p), a.ctypes.data, b.ctypes.data, a.size, addr, dev))
+    return out
+
+
+def cross_dists_pairs(ctx, r, q, p, a, b, out=None):
+    """Distances of the listed pairs (reference a[x], query b[x]) -> [len(a), ncols] f32 (skl_cross_dists_pairs)."""
+    a, b = _pair_lists(a, b)
+    if out is None:
+        out = np.zeros((a.size, ncols(p)), dtype=np.float32)
+    addr, dev = _ptr(out)
+    _check(load().skl_cross_dists_pairs(ctx._h, r._h, q._h, C.byref(p), a.ctypes.data, b.ctypes.data, a.size, addr, dev))
+    return out
 
 
 def self_dists_knn_shared_bins(ctx, s, p, knn, skq):

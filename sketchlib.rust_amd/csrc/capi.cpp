@@ -363,8 +363,8 @@ static long long env_int(const char *name, long long dflt)
 Knobs read_knobs()
 {
     Knobs k;
-    // The product library reads TEN switches: the timing cadence, the device topology the tile order assumes, and the knobs
-    // with which the tests force the banded / sliced / 32-row forms (and the inverted query's bands, the sketching call's upload batches) on inputs small enough for the oracle.  Everything that
+    // The product library reads ELEVEN switches: the timing cadence, the device topology the tile order assumes, and the knobs
+    // with which the tests force the banded / sliced / 32-row forms (and the inverted query's bands, the sketching call's upload batches, the pair list's bands) on inputs small enough for the oracle.  Everything that
     // exists only to time one form against another ("A/B only, results identical") is read by the A/B build alone (-DSKL_AB),
     // where scripts/ab_sweep.py, scripts/forced_switch_suites.sh and the tests marked `ab_library` find it.
     k.timing_every = std::max(0ll, env_int("SKL_TIMING_EVERY", 0));
@@ -375,6 +375,7 @@ Knobs read_knobs()
         const long long w = env_int("SKL_SKETCH_BATCH_WORDS", 0);   // 0 or unset: 8 Mi; any other value: at least 1
         k.sketch_batch_words = w == 0 ? 0 : std::max(1ll, w);
     }
+    k.pairs_band = std::max(0ll, env_int("SKL_PAIRS_BAND", 0));
     k.tail_slices = (int)std::min(8ll, std::max(0ll, env_int("SKL_TAIL_SLICES", 4)));
     k.tail_max_pct = env_int("SKL_TAIL_MAX_PCT", 90);
     k.tile32_min = env_int("SKL_TILE32_MIN", 8ll << 20);
@@ -850,8 +851,16 @@ bool fused_coreacc_ok(const skl_sketches *s)
 int fill_args(const skl_sketches *rows, const skl_sketches *cols, const skl_dist_params *p,
                      int mode, int jout, PairArgs *g)
 {
-    memset(g, 0, sizeof *g);
     SKL_TRY(ensure_lanes(cols));
+    return fill_args_ref_layout(rows, cols, p, mode, jout, g);
+}
+
+// ... for the kernels that read BOTH sides in the reference layout (pair_list.hip): the lane-layout copy of `cols` is not
+// made; g->B is whatever the slab already has (possibly null)
+int fill_args_ref_layout(const skl_sketches *rows, const skl_sketches *cols, const skl_dist_params *p,
+                         int mode, int jout, PairArgs *g)
+{
+    memset(g, 0, sizeof *g);
     g->A = rows->d_rows;
     g->B = cols->d_lanes;
     g->nA = (uint32_t)rows->n;

@@ -1,6 +1,6 @@
 // capi_internal.hpp -- shared between the translation units that implement
 // include/sketchlib_dist.h (capi.cpp: contexts, slabs, dense calls; capi_knn.cpp: the kNN
-// drivers; capi_aux.cpp: candidate lists and sketching).  Not part of the public boundary.
+// drivers; capi_aux.cpp: candidate lists and sketching; capi_pairs.cpp: pair lists).  Not part of the public boundary.
 // How a dense call and each pair-kernel launch is shaped is decided in dense_plan.hpp (pure, no HIP), reached through kernels.h;
 // the early break's decision in eb_plan.hpp; how the kNN drivers cut and feed their bands in knn_plan.hpp (both pure, no HIP).
 #pragma once
@@ -183,6 +183,9 @@ SKL_INTERNAL int early_break_lengths(skl_ctx *ctx, const skl_sketches *rows, con
 // operand / epilogue fields common to every launch: `rows` is the scalar operand (A), `cols` the lane operand (B)
 SKL_INTERNAL int fill_args(const skl_sketches *rows, const skl_sketches *cols, const skl_dist_params *p, int mode,
                            int jout, skl::PairArgs *g);
+// ... the same without making the lane-layout copy of `cols` (kernels that read both sides in the reference layout)
+SKL_INTERNAL int fill_args_ref_layout(const skl_sketches *rows, const skl_sketches *cols, const skl_dist_params *p, int mode,
+                                      int jout, skl::PairArgs *g);
 // rows [r0, r1) of the pair space into `dst_dev` (device memory), launched as dense_plan.hpp decides
 SKL_INTERNAL int dense_band(skl_ctx *ctx, const skl_sketches *rows, const skl_sketches *cols,
                             const skl_dist_params *p, int mode, int jout, int self_mode, uint64_t r0, uint64_t r1,

@@ -346,8 +346,12 @@ __device__ __forceinline__ float2 coreacc_value(const PairArgs &g, uint32_t i, u
 }
 
 // ... the same from the bin-match counts themselves, same[t] = samebits of k index t (the fused epilogue of a k-sliced
-// counts launch): core_acc_dist + simple_linear_regression, jaccard.rs:61-142, operation for operation as above
-__device__ __forceinline__ float2 coreacc_value_counts(const PairArgs &g, uint32_t i, uint32_t jcol, const uint32_t *same_k)
+// counts launch, the pair-list kernels): core_acc_dist + simple_linear_regression, jaccard.rs:61-142, operation for operation
+// as above.  The ONE loop every caller with counts runs, so that one place has to stay bit-identical: kf = the k-mer lengths
+// as f64 (the kernel arguments' copy or a device array); UNROLL > 0: at most UNROLL lengths, the loop unrolled so that counts
+// kept in registers are indexed statically; UNROLL = 0: any number of lengths, counts and lengths in memory.
+template <int UNROLL>
+__device__ __forceinline__ float2 coreacc_fit_counts(const PairArgs &g, uint32_t i, uint32_t jcol, const uint32_t *same_k, const double *kf)
 {
     const uint32_t maxnbits = g.ss64 * 64u;
     double xsum = 0.0, ysum = 0.0, xysum = 0.0, xsquaresum = 0.0, ysquaresum = 0.0, n = 0.0;
@@ -357,32 +361,42 @@ __device__ __forceinline__ float2 coreacc_value_counts(const PairArgs &g, uint32
         c2 = g.compB[jcol];
     }
     bool alive = true;
-#pragma unroll
-    for (uint32_t t = 0; t < (uint32_t)MAX_FUSED_K; ++t) {
-        if (t < g.k_count) {
-            const uint32_t same = same_k[t] <= maxnbits ? same_k[t] : maxnbits;
-            double y;
-            if (!g.has_comp) {
-                y = g.ytab[same];
+    auto one_length = [&](uint32_t t) {
+        const uint32_t same = same_k[t] <= maxnbits ? same_k[t] : maxnbits;
+        double y;
+        if (!g.has_comp) {
+            y = g.ytab[same];
+        } else {
+            y = glibc_log(jaccard_from_samebits_dev(same, g.ss64, true, c1, c2, g.cutoff), g.log_variant);
+        }
+        if (alive) {
+            if (y < g.tolerance) {
+                alive = false;  // jaccard.rs:89-91: break
             } else {
-                y = glibc_log(jaccard_from_samebits_dev(same, g.ss64, true, c1, c2, g.cutoff), g.log_variant);
-            }
-            if (alive) {
-                if (y < g.tolerance) {
-                    alive = false;  // jaccard.rs:89-91: break
-                } else {
-                    const double k_fl = g.kf[t];
-                    xsum += k_fl;
-                    ysum += y;
-                    xysum += k_fl * y;
-                    xsquaresum += k_fl * k_fl;
-                    ysquaresum += y * y;
-                    n += 1.0;
-                }
+                const double k_fl = kf[t];
+                xsum += k_fl;
+                ysum += y;
+                xysum += k_fl * y;
+                xsquaresum += k_fl * k_fl;
+                ysquaresum += y * y;
+                n += 1.0;
             }
         }
+    };
+    if constexpr (UNROLL > 0) {
+#pragma unroll
+        for (uint32_t t = 0; t < (uint32_t)UNROLL; ++t) {
+            if (t < g.k_count) one_length(t);
+        }
+    } else {
+        for (uint32_t t = 0; t < g.k_count && alive; ++t) one_length(t);
     }
     return simple_linear_regression_dev(xsum, ysum, xysum, xsquaresum, ysquaresum, n);
+}
+
+__device__ __forceinline__ float2 coreacc_value_counts(const PairArgs &g, uint32_t i, uint32_t jcol, const uint32_t *same_k)
+{
+    return coreacc_fit_counts<MAX_FUSED_K>(g, i, jcol, same_k, g.kf);
 }
 
 __device__ __forceinline__ void store_coreacc(const PairArgs &g, uint32_t i, uint32_t jcol,

@@ -37,6 +37,8 @@ namespace {
 struct DistArgs {
     std::string ref_db;
     std::optional<std::string> query_db, output, subset, ref_completeness_file, query_completeness_file;
+    std::optional<std::string> pairs;   // --pairs <FILE>: distances of the listed pairs only
+    std::optional<std::string> multi_device_flag;   // "--gpus <N>" / "--devices <LIST>" as given
     std::optional<size_t> knn, kmer;
     int knn_ties = SKL_KNN_TIES_REFERENCE;
     bool ani = false;
@@ -82,6 +84,10 @@ void print_help()
         "                                  per row are the reference's, tied rows may list other ids).  Either rule\n"
         "                                  evaluates every pair once on any number of GPUs\n"
         "      --subset <SUBSET>           Sample names to analyse\n"
+        "      --pairs <FILE>              Only the distances of the sample pairs listed in FILE: one pair per line,\n"
+        "                                  name1<TAB>name2 (further columns ignored: the output of `dist --knn` is a valid\n"
+        "                                  pairs file); both names from REF_DB, or name1 from REF_DB and name2 from\n"
+        "                                  QUERY_DB.  One output line per input pair, in input order\n"
         "  -k <KMER>                       K-mer length (if provided only calculate Jaccard distance)\n"
         "      --ani                       Calculate ANI rather than Jaccard dists, using Poisson model\n"
         "      --threads <THREADS>         Number of CPU threads [default: 1]\n"
@@ -139,6 +145,7 @@ DistArgs parse_dist(int argc, char **argv, int first)
             else usage_error("invalid value '" + v + "' for '--knn-ties <RULE>': possible values: canonical, reference");
         }
         else if (arg == "--subset") a.subset = value("--subset <SUBSET>");
+        else if (arg == "--pairs") a.pairs = value("--pairs <FILE>");
         else if (arg == "-k") a.kmer = parse_usize("-k <KMER>", value("-k <KMER>"));
         else if (arg == "--ani") a.ani = true;
         else if (arg == "--threads") {
@@ -164,12 +171,14 @@ DistArgs parse_dist(int argc, char **argv, int first)
         else if (arg == "--band-mb") a.band_bytes = std::max<size_t>(1, parse_usize("--band-mb <MB>", value(arg))) << 20;
         else if (arg == "--gpus") {
             const size_t ngpu = parse_usize("--gpus <N>", value(arg));
+            a.multi_device_flag = "--gpus <N>";
             if (ngpu < 1) usage_error("invalid value for '--gpus <N>': must be one or higher");
             a.devices.clear();
             for (size_t d = 0; d < ngpu; ++d) a.devices.push_back((int)d);
         }
         else if (arg == "--devices") {
             a.devices.clear();
+            a.multi_device_flag = "--devices <LIST>";
             const std::string v = value(arg);
             size_t pos = 0;
             while (pos <= v.size()) {
@@ -193,6 +202,11 @@ DistArgs parse_dist(int argc, char **argv, int first)
     if (positional.size() == 2) a.query_db = positional[1];
     if (a.ani && !a.kmer) {  // #[arg(long, requires("kmer"))]
         usage_error("the following required arguments were not provided:\n  -k <KMER>");
+    }
+    if (a.pairs) {   // a list of pairs is neither a neighbour search nor a subset, and runs on one device as text
+        const char *other = a.knn ? "--knn <KNN>" : a.subset ? "--subset <SUBSET>" : a.npy ? "--npy" : nullptr;
+        if (other) usage_error(std::string("the argument '--pairs <FILE>' cannot be used with '") + other + "'");
+        if (a.multi_device_flag) usage_error("the argument '--pairs <FILE>' cannot be used with '" + *a.multi_device_flag + "'");
     }
     return a;
 }
@@ -374,7 +388,24 @@ int run_dist(const DistArgs &a)
     if ((ref_comp || query_comp) && (skl_ctx_flags(dev[0].ctx()) & SKL_CTX_FLAG_LOG_UNMATCHED)) log.warn(LOG_UNMATCHED_WARNING);
     const std::vector<double> *rc = ref_comp ? &*ref_comp : nullptr;
     const std::vector<double> *qc = query_comp ? &*query_comp : nullptr;
-    if (!queries) {
+    if (a.pairs) {
+        // an unreadable file, a malformed line or an unknown sample: "Error: ..." and exit code 1, like a bad completeness file
+        std::vector<std::string> ref_names, query_names;
+        for (size_t i = 0; i < n; ++i) ref_names.push_back(references.sketch_name(i));
+        if (queries) {
+            for (size_t i = 0; i < queries->number_samples_loaded(); ++i) query_names.push_back(queries->sketch_name(i));
+        }
+        const std::vector<std::string> &second_names = queries ? query_names : ref_names;
+        const PairsFile pairs = read_pairs_file(*a.pairs, ref_names, second_names, queries ? "query" : "reference");
+        log.info("Calculating the distances of " + std::to_string(pairs.size()) + " listed pairs");
+        if (dist_type.kind == DistType::CoreAcc && references.kmer_lengths().size() < 2) {
+            throw Panic("Need at least two k-mer lengths to calculate core/accessory distances");
+        }
+        if (pairs.size() != 0) {
+            distances::dists_pairs(dev[0], references, queries ? &*queries : nullptr, pairs, ref_names, second_names, dist_type, rc, qc,
+                                   a.completeness_cutoff, *sink, a.threads);
+        }
+    } else if (!queries) {
         if (!a.knn) {
             log.info("Calculating all ref vs ref distances");
             if (n < 2) {

@@ -456,6 +456,29 @@ void DistanceMatrix::write_rows(TextSink &sink, size_t r0, size_t r1, const floa
     });
 }
 
+void write_pair_list(TextSink &sink, const std::vector<std::string> &first_names, const std::vector<std::string> &second_names,
+                     const uint32_t *first, const uint32_t *second, size_t n_pairs, const float *dist, size_t ncols, size_t threads)
+{
+    constexpr size_t BLOCK_LINES = 1 << 15;   // as the dense and sparse listings
+    const size_t n_blocks = (n_pairs + BLOCK_LINES - 1) / BLOCK_LINES;
+    write_blocks_in_order(sink, n_blocks, threads, [&](size_t b, TextBlock &out) {
+        const size_t x1 = std::min(n_pairs, (b + 1) * BLOCK_LINES);
+        for (size_t x = b * BLOCK_LINES; x < x1; ++x) {
+            const std::string &name1 = first_names[first[x]];
+            const std::string &name2 = second_names[second[x]];
+            out.need(name1.size() + name2.size() + 2 * F32_TEXT_MAX + 4);
+            out.put(name1);
+            out.put('\t');
+            out.put(name2);
+            for (size_t cidx = 0; cidx < ncols; ++cidx) {
+                out.put('\t');
+                put_f32(out, dist[x * ncols + cidx]);
+            }
+            out.put('\n');
+        }
+    });
+}
+
 void SparseDistanceMatrix::write(std::ostream &os) const
 {
     StreamSink sink(os);

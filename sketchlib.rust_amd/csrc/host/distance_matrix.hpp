@@ -101,6 +101,12 @@ class DistanceMatrix {
 size_t host_cpu_budget();
 void testing_set_host_cpu_budget(size_t n);   // (tests: 0 = measure; n = pretend)
 
+// The listing of `dist --pairs`: one line per listed pair x, in list order -- first_names[first[x]] TAB
+// second_names[second[x]] TAB dist[x * ncols] (TAB dist[x * ncols + 1]) -- through the same block-parallel formatter and
+// f32 text as the dense and sparse listings.  ncols: 1 or 2.
+void write_pair_list(TextSink &sink, const std::vector<std::string> &first_names, const std::vector<std::string> &second_names,
+                     const uint32_t *first, const uint32_t *second, size_t n_pairs, const float *dist, size_t ncols, size_t threads);
+
 struct SparseJaccard {   // distance_matrix.rs:214
     size_t idx;
     float dist;

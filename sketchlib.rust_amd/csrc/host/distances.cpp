@@ -203,6 +203,31 @@ SparseDistanceMatrix cross_dists_knn(Device &dev, const MultiSketch &ref_sketche
 }
 
 // ---------------------------------------------------------------------------
+// pair list
+// ---------------------------------------------------------------------------
+
+void dists_pairs(Device &dev, const MultiSketch &ref_sketches, const MultiSketch *query_sketches, const PairsFile &pairs,
+                 const std::vector<std::string> &first_names, const std::vector<std::string> &second_names,
+                 const DistType &dist_type, const std::vector<double> *ref_completeness_vec,
+                 const std::vector<double> *query_completeness_vec, double completeness_cutoff, TextSink &sink,
+                 size_t threads)
+{
+    const size_t n_pairs = pairs.size();
+    const size_t ncols = dist_type.n_dist_cols();
+    const skl_dist_params p = to_params(dist_type, completeness_cutoff);
+    RawVec<float> dist(n_pairs * ncols);
+    if (query_sketches) {
+        Slab r(dev, ref_sketches, ref_completeness_vec);
+        Slab q(dev, *query_sketches, query_completeness_vec);
+        check(skl_cross_dists_pairs(dev.ctx(), r.h, q.h, &p, pairs.first.data(), pairs.second.data(), n_pairs, dist.data(), 0));
+    } else {
+        Slab s(dev, ref_sketches, ref_completeness_vec);
+        check(skl_self_dists_pairs(dev.ctx(), s.h, &p, pairs.first.data(), pairs.second.data(), n_pairs, dist.data(), 0));
+    }
+    write_pair_list(sink, first_names, second_names, pairs.first.data(), pairs.second.data(), n_pairs, dist.data(), ncols, threads);
+}
+
+// ---------------------------------------------------------------------------
 // precluster
 // ---------------------------------------------------------------------------
 

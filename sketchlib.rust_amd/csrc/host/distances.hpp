@@ -13,6 +13,7 @@
 #include "distance_matrix.hpp"
 #include "inverted.hpp"
 #include "multisketch.hpp"
+#include "pairs_file.hpp"
 
 struct skl_ctx;
 
@@ -91,6 +92,17 @@ void cross_dists_all_streamed(Device &dev, const MultiSketch &ref_sketches, cons
                               TextSink &sink, size_t threads, size_t band_bytes, bool npy = false);
 // The .npy v1.0 header of a (rows, cols) little-endian f32 array.
 std::string npy_header(size_t rows, size_t cols);
+
+// `dist --pairs` (no reference counterpart; the per-pair functions are jaccard.rs:61-142 and mod.rs:83-100): the distances
+// of the listed pairs (skl_self_dists_pairs, or skl_cross_dists_pairs when `query_sketches` is given: first index a
+// reference sample, second a query sample), written one line per pair in list order -- name1 TAB name2 TAB core TAB acc,
+// or one value for a single k-mer length -- through the text writer of the other listings.  first_names / second_names: the
+// sample names the list was looked up in (reference names twice, or reference and query names).
+void dists_pairs(Device &dev, const MultiSketch &ref_sketches, const MultiSketch *query_sketches, const PairsFile &pairs,
+                 const std::vector<std::string> &first_names, const std::vector<std::string> &second_names,
+                 const DistType &dist_type, const std::vector<double> *ref_completeness_vec,
+                 const std::vector<double> *query_completeness_vec, double completeness_cutoff, TextSink &sink,
+                 size_t threads);
 
 // self_dists_knn_precluster (mod.rs:399-553): kNN restricted to the candidates an inverted
 // index returns (any shared bin).  The candidate lists are built on the host from the index

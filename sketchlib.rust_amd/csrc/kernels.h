@@ -326,6 +326,30 @@ struct CandArgs {
 };
 hipError_t launch_pair_cand(const CandArgs &c, const PairArgs &g, hipStream_t stream);
 
+// Pair-list kernel (pair_list.hip): the distances of LISTED pairs, all k-mer lengths of a pair (core/accessory) or one
+// (single-k), result of list entry x at out[x].  A work item is a run of consecutive entries with the same `a`, cut at 64:
+// item w covers entries [work_start[w], work_start[w + 1]).  Both sides are read in the reference layout: PairArgs::A is
+// the A side's slab, b_rows the B side's (the same slab in self mode); PairArgs::B is not read.
+struct PairListArgs {
+    const uint32_t *pair_a, *pair_b;  // [entries of the band] sample of the A side / of the B side
+    const uint32_t *work_start;       // [n_work + 1] first entry of each work item; the last one = entries of the band
+    uint64_t n_work;
+    const uint64_t *b_rows;           // the B side's slab, reference layout [sample][nk][ss64][14]
+    uint32_t coreacc;                 // 1: (core, acc) per entry from all PairArgs::k_count lengths; 0: MODE_JACCARD's f32 of the one length at k_begin
+    void *out;                        // [entries] float2 / float
+    // more than MAX_FUSED_K lengths: the counts go to counts[entry * k_count + t] and a second launch fits them with the
+    // lengths read from kf (device array [k_count])
+    uint32_t *counts;
+    const double *kf;
+    uint64_t n_entries;               // entries of the band (the fit launch's extent)
+    // consecutive work items (a row's runs) stay on ONE XCD, as CandArgs has it; [work_base, work_end): the items of this
+    // launch (a launch takes at most 2^23 workgroups) -- all four set by the launcher
+    uint32_t xcd_shift, blocks_per_xcd;
+    uint64_t work_base, work_end;
+};
+hipError_t launch_pair_list(const PairListArgs &c, const PairArgs &g, hipStream_t stream);
+const char *pair_list_kernel_name(const PairArgs &g);   // the form launch_pair_list takes for these arguments
+
 // GPU sketching (sketch_kernel.hip): bin minima of the canonical ntHash of every valid k-mer.
 struct SketchArgs {
     const uint32_t *packed;        // 2-bit base codes, 16 per word (code c of a sample at bits 2 (c % 16) of its word c / 16)
