@@ -149,53 +149,6 @@ __device__ __forceinline__ uint64_t square_to_condensed_dev(uint64_t i, uint64_t
 }
 
 
-// Balanced, XCD-aware tile lookup.  Workgroups are dealt round-robin to the 8 XCDs, so
-// Row tiles column group `group` needs in self mode: those with some i < j, i.e. first row below the
-// group's last column (the host's plan_tiles counts the same way).
-__device__ __forceinline__ uint32_t group_row_tiles(const PairArgs &g, uint32_t group)
-{
-    const uint64_t last_col = (uint64_t)(group + 1u) * g.group_cols - 1u;
-    const uint32_t lim = last_col < g.row_end ? (uint32_t)last_col : g.row_end;
-    return lim > g.row_begin ? (lim - g.row_begin + g.tile_rows - 1u) / g.tile_rows : 0u;
-}
-
-// Tile u of super-group sg, self mode.  A super-group is group_span consecutive column groups; its
-// tiles are numbered row tile by row tile, the groups that need that row tile side by side.  Later
-// groups need more row tiles (the triangle), so row tile `at` belongs to the LAST groups of the
-// super-group: all of them up to the first group's count, one fewer up to the second's, ...
-__device__ __forceinline__ void tile_in_supergroup_self(const PairArgs &g, uint32_t sg, uint32_t u, uint32_t &group,
-                                                        uint32_t &row_tile)
-{
-    const uint32_t first = sg * g.group_span;
-    const uint32_t gcount = min(g.group_span, g.n_groups - first);
-    uint32_t lo_at = 0;
-    for (uint32_t gi = 0; gi + 1u < gcount; ++gi) {
-        const uint32_t width = gcount - gi;
-        const uint32_t n_gi = group_row_tiles(g, first + gi);
-        const uint32_t span = (n_gi - lo_at) * width;
-        if (u < span) {
-            row_tile = lo_at + u / width;
-            group = first + gi + (u - (u / width) * width);
-            return;
-        }
-        u -= span;
-        lo_at = n_gi;
-    }
-    row_tile = lo_at + u;
-    group = first + gcount - 1u;
-}
-
-// ... cross mode: every group needs all a_tiles row tiles
-__device__ __forceinline__ void tile_in_supergroup_cross(const PairArgs &g, uint32_t t, uint32_t &group, uint32_t &row_tile)
-{
-    const uint32_t per = g.group_span * g.a_tiles;
-    const uint32_t sg = t / per, u = t - sg * per;
-    const uint32_t first = sg * g.group_span;
-    const uint32_t gcount = min(g.group_span, g.n_groups - first);
-    row_tile = u / gcount;
-    group = first + (u - row_tile * gcount);
-}
-
 // f32 -> u32 whose unsigned order is the float order (the running top-k keeps its keys this way)
 __device__ __forceinline__ uint32_t sortable_bits(float f)
 {
@@ -203,47 +156,8 @@ __device__ __forceinline__ uint32_t sortable_bits(float f)
     return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
 }
 
-// blockIdx % (number of XCDs) labels the XCD (MI355X_MICROARCH.md; 8 on an unpartitioned MI355X, PairArgs::xcd_shift);
-// XCD x takes tiles
-// [x*tiles_per_xcd, (x+1)*tiles_per_xcd) of the super-group-major numbering of the ACTIVE
-// tiles: every XCD gets the same number of (equal-cost) tiles.  The ~100 workgroups resident on an
-// XCD are consecutive tiles = row tiles x group_span column groups, each row tile shared by
-// group_span neighbouring workgroups.  HBM bytes per launch at n = 16 000 with 32 x 128 tiles:
-// 44.8 GB numbered group by group, 31.6 GB with group_span = 2 (the default), 32.0 GB with 4; at
-// cfg 2 (k-sliced, 16 x 128): 261 / 257 / 321 MB (profiles/r02_tile32_*.md, r02c_*).
-// Returns false when this workgroup has no tile.
-__device__ __forceinline__ bool lookup_tile_at(const PairArgs &g, uint32_t xcd, uint32_t slot,
-                                               uint32_t &group, uint32_t &row_tile)
-{
-    if (slot >= g.tiles_per_xcd) return false;
-    const uint32_t t = g.xcd_interleave ? ((((slot >> 5) << g.xcd_shift) + xcd) << 5) + (slot & 31u) : xcd * g.tiles_per_xcd + slot;
-    if (t >= g.n_active_tiles) return false;
-    if (!g.self_mode) {
-        tile_in_supergroup_cross(g, t, group, row_tile);
-        return true;
-    }
-    const uint32_t n_super = (g.n_groups + g.group_span - 1u) / g.group_span;
-    if (g.n_prefix_inline != 0u) {   // the table rides in the kernel arguments: no global load before the first row DMA
-        uint32_t lo = 0, base = 0;
-#pragma unroll
-        for (int x = 1; x < TILE_PREFIX_INLINE; ++x) {
-            if ((uint32_t)x < n_super && g.tile_prefix_inline[x] <= t) {
-                lo = (uint32_t)x;
-                base = g.tile_prefix_inline[x];
-            }
-        }
-        tile_in_supergroup_self(g, lo, t - base, group, row_tile);
-        return true;
-    }
-    uint32_t lo = 0, hi = n_super;  // largest lo with prefix[lo] <= t
-    while (hi - lo > 1u) {
-        const uint32_t mid = (lo + hi) >> 1;
-        if (g.tile_prefix[mid] <= t) lo = mid; else hi = mid;
-    }
-    tile_in_supergroup_self(g, lo, t - g.tile_prefix[lo], group, row_tile);
-    return true;
-}
-
+// This workgroup's tile (work_map.hpp): blockIdx % (number of XCDs) labels the XCD (MI355X_MICROARCH.md; 8 on an
+// unpartitioned MI355X, PairArgs::xcd_shift), blockIdx / that number is its slot there.  False: it has none.
 __device__ __forceinline__ bool lookup_tile(const PairArgs &g, uint32_t &group, uint32_t &row_tile)
 {
     return lookup_tile_at(g, blockIdx.x & ((1u << g.xcd_shift) - 1u), blockIdx.x >> g.xcd_shift, group, row_tile);

@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "dense_plan.hpp"   // slice_plan()
+#include "work_map.hpp"     // which workgroup computes what: TILE_PREFIX_INLINE, the fields below it reads and plans
 
 namespace skl {
 
@@ -17,7 +18,6 @@ constexpr int BBITS = 14;          // src/sketch/mod.rs:34
 constexpr int LANES = 64;          // wavefront width on gfx950
 constexpr int WAVES_PER_WG = 4;    // 256-thread workgroups
 constexpr int MAX_FUSED_K = 6;     // k-mer lengths the fused core/acc epilogue packs (3 x 2 x u16)
-constexpr int TILE_PREFIX_INLINE = 16;
 constexpr int A_PAD_ROWS = 64;     // rows the scalar-operand slab is over-allocated by
 // pair_kslice.hip keeps a k-mer length's mismatch counts in u16 fields: whole sketches up to 1 023 chunks (65 472 bins);
 // larger ones are walked in segments of 1 016 chunks (a multiple of 8 = the chunks per stage of both tile heights)
@@ -69,7 +69,7 @@ struct PairArgs {
     // a binary search of dependent global loads -- the first thing every workgroup of a small launch waits for
     uint32_t inline_prefix_ok;    // host-side request (SKL_INLINE_PREFIX=0 clears it: A/B)
     uint32_t n_prefix_inline;     // entries valid in tile_prefix_inline (0: search tile_prefix)
-    uint32_t tile_prefix_inline[16];
+    uint32_t tile_prefix_inline[TILE_PREFIX_INLINE];
     uint64_t out_base;            // flat index of the first pair of this launch
     void *out;
     // MODE_COUNTS record layout: count of (pair p, k index kk) at out[p*cnt_pair_stride + kk*cnt_k_stride]
@@ -159,6 +159,7 @@ struct PairArgs {
     double tolerance;             // ln(2 / (sketch_size * 64))   jaccard.rs:75
     double kf[MAX_FUSED_K];       // k-mer lengths as f64
 };
+static_assert(sizeof(PairArgs) == 528, "PairArgs is the pair kernels' argument: its layout is pinned");
 
 // Device buffer the launchers may use for the tile-prefix table (owned by the context).
 struct TileScratch {
@@ -169,9 +170,8 @@ struct TileScratch {
     uint64_t cached_key[4] = {~0ull, ~0ull, ~0ull, ~0ull};
 };
 
-// Fills n_active_tiles / tiles_per_xcd / n_groups / tile_prefix of `args` for tiles of
-// rows_per_tile x cols_per_group; uploads the prefix table (self mode) on `stream`.
-// Returns the grid size (0 = nothing to do).
+// The tile map of work_map.hpp (plan_tile_geometry + plan_tile_numbering) for tiles of rows_per_tile x cols_per_group
+// written into `args`; uploads the prefix table (self mode) on `stream`.  Returns the grid size (0 = nothing to do).
 hipError_t plan_tiles(PairArgs &args, uint32_t rows_per_tile, uint32_t cols_per_group,
                       TileScratch &scratch, hipStream_t stream, uint64_t *grid_out);
 

@@ -24,39 +24,18 @@
 
 namespace skl {
 // ---------------------------------------------------------------------------
-// balanced tile enumeration (host side of device_common.hpp::lookup_tile)
+// balanced tile enumeration: the plan is work_map.hpp's, here it meets the device (the uploaded prefix table)
 // ---------------------------------------------------------------------------
 
 hipError_t plan_tiles(PairArgs &args, uint32_t rows_per_tile, uint32_t cols_per_group,
                       TileScratch &scratch, hipStream_t stream, uint64_t *grid_out)
 {
-    *grid_out = 0;
-    if (args.group_span == 0) args.group_span = 1;
-    args.tile_rows = rows_per_tile;
-    args.group_cols = cols_per_group;
-    const uint32_t rows = args.row_end - args.row_begin;
-    args.a_tiles = (rows + rows_per_tile - 1) / rows_per_tile;
-    args.n_jblocks = (args.nB + 63u) / 64u;
-    args.n_groups = (args.nB + cols_per_group - 1) / cols_per_group;
-    args.tile_prefix = nullptr;
-    uint64_t total;
-    if (!args.self_mode) {
-        total = (uint64_t)args.a_tiles * args.n_groups;
-    } else {
-        // group g is needed by the row tiles with a0 < (g+1)*W - 1 (some i < j exists)
-        const uint32_t n_super = (args.n_groups + args.group_span - 1) / args.group_span;
-        std::vector<uint32_t> prefix(n_super + 1);
-        total = 0;
-        for (uint32_t gi = 0; gi < args.n_groups; ++gi) {
-            if (gi % args.group_span == 0) prefix[gi / args.group_span] = (uint32_t)total;
-            const uint64_t last_col = (uint64_t)(gi + 1) * cols_per_group - 1;
-            const uint32_t lim = (uint32_t)std::min<uint64_t>(args.row_end, last_col);
-            total += lim > args.row_begin ? (lim - args.row_begin + rows_per_tile - 1) / rows_per_tile : 0u;
-        }
-        prefix[n_super] = (uint32_t)total;
-        if (total >= (1ull << 32)) return hipErrorInvalidValue;
+    plan_tile_geometry(args, rows_per_tile, cols_per_group);
+    std::vector<uint32_t> prefix(args.self_mode ? n_supergroups(args) + 1u : 0u);
+    if (!plan_tile_numbering(args, prefix.data(), grid_out)) return hipErrorInvalidValue;
+    if (args.self_mode) {
         const uint64_t key[4] = {((uint64_t)args.row_begin << 32) | args.row_end, ((uint64_t)args.group_span << 32) | args.nB,
-                                 ((uint64_t)rows_per_tile << 32) | cols_per_group, total};
+                                 ((uint64_t)rows_per_tile << 32) | cols_per_group, args.n_active_tiles};
         if (prefix.size() > scratch.capacity) {
             if (scratch.d_prefix) (void)hipFree(scratch.d_prefix);          // (synchronises the device)
             if (scratch.h_staging) (void)hipHostFree(scratch.h_staging);
@@ -91,19 +70,7 @@ hipError_t plan_tiles(PairArgs &args, uint32_t rows_per_tile, uint32_t cols_per_
             memcpy(scratch.cached_key, key, sizeof key);
         }
         args.tile_prefix = scratch.d_prefix;
-        args.n_prefix_inline = 0;
-        if (args.inline_prefix_ok && prefix.size() <= (size_t)TILE_PREFIX_INLINE) {
-            args.n_prefix_inline = (uint32_t)prefix.size();
-            for (size_t x = 0; x < prefix.size(); ++x) args.tile_prefix_inline[x] = prefix[x];
-        }
     }
-    if (total == 0) return hipSuccess;
-    if (total >= (1ull << 31)) return hipErrorInvalidValue;
-    args.n_active_tiles = (uint32_t)total;
-    const uint64_t n_xcd = 1ull << args.xcd_shift;
-    args.tiles_per_xcd = (uint32_t)((total + n_xcd - 1) / n_xcd);
-    if (args.xcd_interleave) args.tiles_per_xcd = (uint32_t)(((total + 31) / 32 + n_xcd - 1) / n_xcd * 32);   // whole blocks of 32 tiles, dealt in turns
-    *grid_out = n_xcd * args.tiles_per_xcd;
     return hipSuccess;
 }
 

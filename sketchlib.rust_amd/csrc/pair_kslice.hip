@@ -42,8 +42,6 @@
 
 namespace skl {
 
-constexpr uint32_t KSL_TILE_BLOCK = 32;   // k-sliced launches: tiles that walk a k-mer length together
-
 #ifdef SKL_TRACE
 // scripts/microbench/kslice_trace.hip: per-wave timeline (100 MHz wall clock) + hardware id,
 // and the shader-clock counter (s_memtime) at marks 1 and 2, i.e. around the streaming phase:
@@ -142,37 +140,13 @@ __global__ __launch_bounds__(LANES *WAVES_PER_WG, OCC != 0 ? OCC : (TIGHT ? (R >
 #endif
     SKL_TRACE_MARK(0);
 
-    // blockIdx -> (XCD, tile slot on that XCD[, k-mer length]): the k slices of a tile are
-    // neighbours in the per-XCD order
+    // blockIdx -> (XCD, slot on that XCD) -> (tile slot[, k-mer length[, chunk slice]]): work_map.hpp, which also says why
+    // the units of an XCD are ordered tile block by tile block and what tail slicing is
     const uint32_t xcd = blockIdx.x & ((1u << g.xcd_shift) - 1u), s_idx = blockIdx.x >> g.xcd_shift;
-    // k-sliced: blocks of KSL_TILE_BLOCK consecutive tiles of an XCD walk one k-mer length together
-    // (tile index fastest, then k, then block), so that the workgroups resident on an XCD at one time
-    // share a (column group, k) plane of the lane slab in its L2: 2 % at n = 4 000 ... 8 000 against
-    // k fastest (profiles/r02_ab_korder_l2prefetch.jsonl)
-    constexpr uint32_t KB = KSL_TILE_BLOCK;
-    // (MODE_COUNTS launches may also cut a k-mer length into g.k_slices chunk ranges, one workgroup
-    // each -- more, shorter workgroups for launches that would otherwise fill the chip 1.4 times;
-    // slice s of k index kk stores its counts as "k index" s * k_count + kk, summed by the epilogue)
-    // TAIL SLICING (g.tail_slices > 1, instead of the uniform slices): the workgroups of an XCD up to
-    // index tail_first -- its whole rounds of resident workgroups -- are whole units, the ones after
-    // are chunk slices of the remaining units.  The last round of a launch is then made of short
-    // workgroups that spread over all SIMDs instead of a few long ones that run 1-2 per SIMD at a lone
-    // wave's issue interval, and the rounds before it pay nothing.  Slice 0 stores, the others add
-    // into plane 1 (see kernels.h).
-    const bool tail_mode = KSL && MODE == MODE_COUNTS && g.tail_slices > 1u;
-    const bool in_tail = tail_mode && s_idx >= g.tail_first;
-    const uint32_t n_slices = in_tail ? g.tail_slices : (KSL && MODE == MODE_COUNTS && !tail_mode ? g.k_slices : 1u);
-    const uint32_t u_idx = in_tail ? g.tail_first + (s_idx - g.tail_first) / n_slices : s_idx;   // unit index (tail mode) / workgroup index
-    // (the last block of an XCD may be short: the grid has exactly tiles_per_xcd x k x slices workgroups
-    // per XCD, no padding slots that would be dispatched only to exit)
-    const uint32_t per_blk = KB * g.k_count * (tail_mode ? 1u : n_slices);
-    const uint32_t blk_ = u_idx / per_blk, rem_ = u_idx - blk_ * per_blk;
-    const uint32_t in_blk = KSL ? min(KB, g.tiles_per_xcd - min(g.tiles_per_xcd, blk_ * KB)) : 1u;
-    if (KSL && in_blk == 0u) return;
-    const uint32_t slot = KSL ? blk_ * KB + rem_ % in_blk : s_idx;
-    const uint32_t kslot = KSL ? rem_ / in_blk : 0u;
-    const uint32_t kk0 = tail_mode ? kslot : kslot / n_slices;  // first k index of this workgroup
-    const uint32_t slice = in_tail ? (s_idx - g.tail_first) % n_slices : (tail_mode ? 0u : kslot - kk0 * n_slices);
+    const KsliceUnit unit = kslice_unit(g, s_idx, KSL, MODE == MODE_COUNTS);
+    if (unit.none) return;
+    const bool tail_mode = unit.tail_mode, in_tail = unit.in_tail;
+    const uint32_t slot = unit.slot, kk0 = unit.kk0, slice = unit.slice, n_slices = unit.n_slices;
     const uint32_t nkk = KSL ? 1u : g.k_count;                  // k-mer lengths it walks
     // WAVE PRIORITY BY ROUND.  A SIMD issues for its oldest wave first, so the workgroups of a launch's
     // second round -- dispatched into the slots the first round's oldest waves free -- get what three
@@ -180,7 +154,7 @@ __global__ __launch_bounds__(LANES *WAVES_PER_WG, OCC != 0 ? OCC : (TIGHT ? (R >
     // that is the tail of every launch of 1-2.5 rounds.  Raising the priority of each later round by one
     // (s_setprio, capped at 3) lets them work from the moment they arrive: -3 ... -4 % at 900-1 200
     // genomes core/accessory, -7 % at 2 000 single-k (a second round of a few workgroups), +2 % at
-    // 2.5-2.7 rounds and nothing beyond, so the launcher asks for it up to 2.25 rounds
+    // 2.5-2.7 rounds and nothing beyond, so the plan (plan_kslice_grid) asks for it up to 2.25 rounds
     // (profiles/r02_ab_round_priority.jsonl).  Not for sliced launches (four quarter-rounds of short
     // workgroups: +6 % at 800 genomes).
     if (KSL && !tail_mode && g.round_size != 0u) {
@@ -189,10 +163,8 @@ __global__ __launch_bounds__(LANES *WAVES_PER_WG, OCC != 0 ? OCC : (TIGHT ? (R >
         else if (round_ == 2u) __builtin_amdgcn_s_setprio(2);
         else if (round_ >= 3u) __builtin_amdgcn_s_setprio(3);
     }
-    // chunk range of this workgroup: whole stages per slice, the last slice takes what is left (any sketch size)
-    const uint32_t per_slice = g.slice_chunks != 0u ? g.slice_chunks : g.ss64 / n_slices;
-    const uint32_t c_begin = n_slices > 1u ? min(g.ss64, slice * per_slice) : 0u;
-    const uint32_t c_end = n_slices > 1u ? min(g.ss64, c_begin + per_slice) : g.ss64;
+    uint32_t c_begin, c_end;   // chunk range of this workgroup
+    slice_chunk_range(g, n_slices, slice, c_begin, c_end);
     uint32_t jg, at;  // column group (JL blocks of 64), row tile
     if (!lookup_tile_at(g, xcd, slot, jg, at)) return;
     if constexpr ((ABL & 8) != 0) {   // timing only: every workgroup computes tile (0, group 1): all operands cache-hot
@@ -396,9 +368,8 @@ hipError_t launch_pair_kernel_kslice(const PairArgs &args_in, int mode, int shap
     const hipError_t pe = plan_tiles(args, (uint32_t)R, (uint32_t)JL * 64u, scratch, stream, &n_wg);
     if (pe != hipSuccess) return pe;
     if (n_wg == 0) return hipSuccess;
-    // k-sliced: exactly tiles_per_xcd x k [x slices] workgroups per XCD (the last tile block is short)
-    if (!(k_sliced && mode == MODE_COUNTS) || args.k_slices == 0) args.k_slices = 1;
-    if (!(k_sliced && mode == MODE_COUNTS)) args.tail_slices = 0;
+    // units, slices and workgroups of the grid (work_map.hpp): exactly tiles_per_xcd x k [x slices] per XCD when k-sliced
+    if (!plan_kslice_grid(args, k_sliced, mode == MODE_COUNTS, &n_wg)) return hipErrorInvalidValue;
     // the fused epilogue (A/B build): whole k-mer lengths only (no chunk slices), the two shipped shapes
 #ifndef SKL_AB
     if (args.fuse_counter != nullptr) return hipErrorInvalidValue;
@@ -407,39 +378,6 @@ hipError_t launch_pair_kernel_kslice(const PairArgs &args_in, int mode, int shap
                                           (shape == 165 || shape == 325) && args.k_count <= (uint32_t)MAX_FUSED_K && args.fuse_out != nullptr)) {
         return hipErrorInvalidValue;   // (the caller skips the epilogue launch when it asks for the fused one)
     }
-    if (args.tail_slices > 1u) {
-        // whole units for the XCD's whole rounds of resident workgroups, slices for the rest
-        // (counted on the real units: the padding slots of the last tile block exit at once)
-        if (args.tail_resident == 0) return hipErrorInvalidValue;
-        const uint32_t units_x = args.tiles_per_xcd * args.k_count;
-        args.tail_first = units_x / args.tail_resident * args.tail_resident;
-        args.k_slices = 1;
-    }
-    {   // whole stages per slice, every slice holds something
-        const uint32_t S = args.tail_slices > 1u ? args.tail_slices : args.k_slices;
-        if (S > 1u) {
-            if (args.slice_chunks == 0u) {
-                if (args.ss64 % (S * 8u) != 0) return hipErrorInvalidValue;
-            } else if (args.slice_chunks % 8u != 0 || (uint64_t)args.slice_chunks * (S - 1u) >= args.ss64 || (uint64_t)args.slice_chunks * S < args.ss64) {
-                return hipErrorInvalidValue;
-            }
-        } else {
-            args.slice_chunks = 0;
-        }
-    }
-    // wave priority by round: for launches of up to 2.25 rounds of workgroups (it costs 2 % at 2.5-2.7 rounds
-    // and is neutral beyond; profiles/r02_ab_round_priority.jsonl)
-    if (!k_sliced || (uint64_t)args.tiles_per_xcd * args.k_count * args.k_slices * 4u > 9ull * args.round_size) args.round_size = 0;
-    if (k_sliced) {
-        const uint64_t units_pad = (uint64_t)args.tiles_per_xcd * args.k_count;   // exact: the last tile block of an XCD is short
-        n_wg = ((uint64_t)units_pad << args.xcd_shift) * args.k_slices;
-        if (args.tail_slices > 1u) {
-            const uint64_t first = std::min<uint64_t>(args.tail_first, units_pad);
-            args.tail_first = (uint32_t)first;
-            n_wg = (first + (units_pad - first) * args.tail_slices) << args.xcd_shift;
-        }
-    }
-    if (n_wg >= (1ull << 31)) return hipErrorInvalidValue;
     const dim3 grid((unsigned)n_wg);
 #ifdef SKL_AB
     // timing-only: rows read as if the row slab were tile-major ([row tile][k][chunk][row][plane]: a wave's
