@@ -387,6 +387,32 @@ int skl_sketch_signs_packed(skl_ctx *ctx, const uint32_t *packed, const uint64_t
                             const uint64_t *offsets, const uint64_t *offset_begin, size_t n_samples,
                             const size_t *kmers, size_t nk, uint64_t num_bins, int rc, uint64_t *out_signs);
 
+/* GPU sketching of amino-acid sequences: bin minima of `aaHash % SIGN_MOD` over every window of k valid
+ * residues -- Sketch::get_signs_no_densify (src/sketch/mod.rs:156-176) over AaHashIterator
+ * (src/hashing/aahash_iterator.rs:138-210), forward hash only, all samples and k-mer lengths of the call.
+ * `residues`: one byte per STORED residue, a class code: 0 = separator (an invalid residue or a record end, the
+ * reference's SEQSEP), 1..20 = the letters ACDEFGHIKLMNPQRSTVWY in this order (either case); anything above 20 is
+ * refused.  Sample s owns residues[res_begin[s] .. res_begin[s+1]) (res_begin: n_samples + 1 entries, not decreasing).
+ * There is no offsets array: a window [p, p+k) is hashed iff none of its k codes is 0.  `level` 1 / 2 / 3 chooses the
+ * seed table (level 2 groups ST, DE, KQR, ILMV, FWY; level 3 also A with ST and N with DE).
+ * concat_end_rule != 0 reproduces the reference's iterator at the end of a sample: it seeds a window only where
+ * start < len - k, so the window at exactly len - k is hashed only when it is reached by rolling, i.e. when
+ * len - k >= 1 and the residue at len - k - 1 is valid too.  A sample that ends in a separator (every sample sketched
+ * without --concat-fasta) never shows the difference; concat_end_rule = 0 hashes every window of k valid residues.
+ * out_signs: [n_samples][nk][num_bins] u64, u64::MAX for an empty bin -- a sample without a hashed window (empty,
+ * shorter than k, all separators) comes back all-max and the error is the caller's to raise; densify_bin and the
+ * 14-plane transpose are the caller's too.  Any k from 1 to 65 535 works (k above skl_sketch_aa_shape(3, 0) takes the
+ * unstaged kernel for every sample).  The samples go in batches of whole samples of at most 256 MiB of signs
+ * (SKL_AA_BATCH_SIGN_BYTES) and 256 Mi residues; short samples share workgroups (csrc/aa_plan.hpp).  Host pointers. */
+int skl_sketch_signs_aa(skl_ctx *ctx, const uint8_t *residues, const uint64_t *res_begin, size_t n_samples,
+                        const size_t *kmers, size_t nk, uint64_t num_bins, int level, int concat_end_rule,
+                        uint64_t *out_signs);
+/* Shapes of that call's two kernels: what = 0 window starts per thread of the staged form, 1 its threads per workgroup,
+ * 2 most bins it keeps in LDS, 3 longest k-mer it takes, 4 residues from which a sample is staged (SKL_AA_LONG_MIN
+ * overrides), 5 window starts per thread of the unstaged form when the longest k-mer is kmax, 6 its threads per
+ * workgroup; -1 otherwise.  Needs no device. */
+int skl_sketch_aa_shape(int what, size_t kmax);
+
 /* Read sketching with a k-mer count filter.  The reference offers a window's sign to its count
  * filter only if the sign is below the current minimum of its bin (Sketch::bin_sign, src/sketch/mod.rs:198-210;
  * the filter: src/hashing/bloom_filter.rs), and a bin's minimum only ever falls.  So under any bin state the

@@ -117,6 +117,8 @@ _SIG = [
     ("skl_inverted_band_queries", C.c_size_t, [_P, _P, C.c_int]),
     ("skl_sketch_signs", C.c_int, [_P, _P, _P, _P, _P, C.c_size_t, _P, C.c_size_t, C.c_uint64, C.c_int, _P]),
     ("skl_sketch_signs_packed", C.c_int, [_P, _P, _P, _P, _P, C.c_size_t, _P, C.c_size_t, C.c_uint64, C.c_int, _P]),
+    ("skl_sketch_signs_aa", C.c_int, [_P, _P, _P, C.c_size_t, _P, C.c_size_t, C.c_uint64, C.c_int, C.c_int, _P]),
+    ("skl_sketch_aa_shape", C.c_int, [C.c_int, C.c_size_t]),
     ("skl_reads_create", C.c_int, [_P, _P, _P, _P, _P, C.c_size_t, _P, C.c_size_t, C.c_uint64, C.c_int, C.POINTER(_P)]),
     ("skl_reads_survivors", C.c_int, [_P, _P, _P, _P, C.c_uint64, _P, _P]),
     ("skl_reads_destroy", C.c_int, [_P]),
@@ -735,6 +737,39 @@ def sketch_signs_packed(ctx, packed, code_begin, offsets, offset_begin, kmers, n
     _check(load().skl_sketch_signs_packed(ctx._h, packed.ctypes.data if packed.size else None, code_begin.ctypes.data,
                                           offsets.ctypes.data if offsets.size else None, offset_begin.ctypes.data, n,
                                           kmers.ctypes.data, kmers.size, num_bins, int(rc), out.ctypes.data))
+    return out
+
+
+AA_LETTERS = "ACDEFGHIKLMNPQRSTVWY"
+
+
+def aa_codes(seq):
+    """Residue bytes -> the class codes skl_sketch_signs_aa takes: 1..20 for the letters of AA_LETTERS (either case), 0 (a
+    separator) for everything else."""
+    table = np.zeros(256, dtype=np.uint8)
+    for i, ch in enumerate(AA_LETTERS):
+        table[ord(ch)] = table[ord(ch.lower())] = i + 1
+    return table[np.frombuffer(bytes(seq), dtype=np.uint8)]
+
+
+def sketch_aa_shape():
+    """Shapes of the two kernels behind sketch_signs_aa (skl_sketch_aa_shape); short_span is a function of the longest k-mer."""
+    f = load().skl_sketch_aa_shape
+    return {"span_lds": f(0, 0), "wg_lds": f(1, 0), "lds_bins_max": f(2, 0), "k_staged_max": f(3, 0), "long_min": f(4, 0),
+            "short_span": lambda kmax: f(5, int(kmax)), "wg_short": f(6, 0)}
+
+
+def sketch_signs_aa(ctx, residues, res_begin, kmers, num_bins, level=1, concat_end_rule=False):
+    """skl_sketch_signs_aa: GPU bin minima of the forward aaHash over every window of k valid residues (class codes as
+    aa_codes gives them, 0 = separator) -> [n_samples, nk, num_bins] uint64, u64::MAX for empty bins."""
+    residues = np.ascontiguousarray(residues, dtype=np.uint8)
+    res_begin = np.ascontiguousarray(res_begin, dtype=np.uint64)
+    kmers = np.ascontiguousarray(kmers, dtype=np.uintp)
+    n = res_begin.size - 1
+    out = np.zeros((n, kmers.size, num_bins), dtype=np.uint64)
+    _check(load().skl_sketch_signs_aa(ctx._h, residues.ctypes.data if residues.size else None, res_begin.ctypes.data, n,
+                                      kmers.ctypes.data, kmers.size, num_bins, int(level), int(bool(concat_end_rule)),
+                                      out.ctypes.data))
     return out
 
 

@@ -375,6 +375,8 @@ Knobs read_knobs()
         const long long w = env_int("SKL_SKETCH_BATCH_WORDS", 0);   // 0 or unset: 8 Mi; any other value: at least 1
         k.sketch_batch_words = w == 0 ? 0 : std::max(1ll, w);
     }
+    k.aa_batch_sign_bytes = std::max(0ll, env_int("SKL_AA_BATCH_SIGN_BYTES", 0));
+    k.aa_long_min = std::max(0ll, env_int("SKL_AA_LONG_MIN", 0));
     k.pairs_band = std::max(0ll, env_int("SKL_PAIRS_BAND", 0));
     k.tail_slices = (int)std::min(8ll, std::max(0ll, env_int("SKL_TAIL_SLICES", 4)));
     k.tail_max_pct = env_int("SKL_TAIL_MAX_PCT", 90);

@@ -505,14 +505,19 @@ void print_sketch_help()
         "Usage: sketchlib sketch [OPTIONS] -o <OUTPUT> <--k-vals <K_VALS>|--k-seq <K_SEQ>> <SEQ_FILES|-f <FILE_LIST>>\n\n"
         "A sample whose first file starts with a FASTQ record is a read set (one or two files, e.g. a pair); its\n"
         "k-mers pass a count filter (--min-count) and its bases a quality filter (--min-qual).  FASTA samples\n"
-        "ignore both.\n\n"
+        "ignore both.  With --seq-type aa the files are protein FASTA: the 20 amino-acid letters are hashed (aaHash,\n"
+        "forward only), anything else breaks the windows it lies in.\n\n"
         "Options:\n"
         "  -f <FILE_LIST>                  File listing sample names and their files (name<TAB>file[<TAB>file])\n"
         "  -o <OUTPUT>                     Output prefix (.skm / .skd)\n"
         "  -k, --k-vals <K_VALS>           K-mer lengths (comma separated)\n"
         "      --k-seq <K_SEQ>             K-mer lengths as start,end,step\n"
         "  -s, --sketch-size <SIZE>        Bins per k-mer length [default: 1000]\n"
-        "      --single-strand             Ignore the reverse complement\n"
+        "      --seq-type <SEQ_TYPE>       Type of sequence to hash [default: dna] [possible values: dna, aa]\n"
+        "      --level <LEVEL>             aa: aaHash level; level2 groups ST, DE, KQR, ILMV, FWY, level3 also A with ST and\n"
+        "                                  N with DE [default: level1] [possible values: level1, level2, level3]\n"
+        "      --concat-fasta              aa: every FASTA record is a sample of its own, named <name>_<n>\n"
+        "      --single-strand             Ignore the reverse complement (aa: only the flag in the metadata changes)\n"
         "      --min-count <MIN_COUNT>     Read sets: minimum k-mer count [default: 5]\n"
         "      --min-qual <MIN_QUAL>       Read sets: minimum quality byte of a base, compared raw (no Phred offset)\n"
         "                                  [default: 20]\n"
@@ -542,6 +547,7 @@ int run_sketch(int argc, char **argv, int first, bool verbose, bool quiet)
 {
     g_usage = "sketchlib sketch [OPTIONS] -o <OUTPUT> <--k-vals <K_VALS>|--k-seq <K_SEQ>> <SEQ_FILES|-f <FILE_LIST>>";
     SketchArgs a;
+    SeqType seq;
     a.verbose = verbose;
     a.quiet = quiet;
     for (int i = first; i < argc; ++i) {
@@ -564,11 +570,18 @@ int run_sketch(int argc, char **argv, int first, bool verbose, bool quiet)
         else if (arg == "--device") a.gpu = (int)parse_usize("--device <D>", value(arg));
         else if (arg == "--seq-type") {
             const std::string v = value(arg);
-            if (v != "dna") { std::cerr << "error: this build sketches DNA only (--seq-type " << v << ")\n"; return 2; }
+            if (v == "pdb") { std::cerr << "error: structures are not part of this build (--seq-type pdb); it sketches dna and aa\n"; return 2; }
+            if (v != "dna" && v != "aa") usage_error("invalid value '" + v + "' for '--seq-type <SEQ_TYPE>'\n  [possible values: dna, aa, pdb]");
+            seq.aa = v == "aa";
         }
         else if (arg == "--min-count") a.min_count = (uint16_t)parse_bounded("--min-count <MIN_COUNT>", value(arg), 0xFFFF);
         else if (arg == "--min-qual") a.min_qual = (uint8_t)parse_bounded("--min-qual <MIN_QUAL>", value(arg), 0xFF);
-        else if (arg == "--level") (void)value(arg);
+        else if (arg == "--level") {
+            const std::string v = value(arg);
+            if (v != "level1" && v != "level2" && v != "level3") usage_error("invalid value '" + v + "' for '--level <LEVEL>'\n  [possible values: level1, level2, level3]");
+            seq.level = v.back() - '0';
+        }
+        else if (arg == "--concat-fasta") seq.concat_fasta = true;
         else if (arg.size() > 1 && arg[0] == '-') usage_error("unexpected argument '" + arg + "' found");
         else a.seq_files.push_back(arg);
     }
@@ -577,6 +590,8 @@ int run_sketch(int argc, char **argv, int first, bool verbose, bool quiet)
         usage_error("exactly one of <SEQ_FILES>... or -f <FILE_LIST> must be given");
     }
     if (a.k_vals.empty() == a.k_seq.empty()) usage_error("exactly one of --k-vals or --k-seq must be given");
+    if (seq.concat_fasta && !seq.aa) throw Panic("--concat-fasta currently only supported with --seq-type aa");   // lib.rs:258-260
+    if (!seq.aa) seq.level = 1;   // (--level is read with aa only)
     const Logger log{a.verbose && !a.quiet, !a.quiet};
     const std::vector<InputFastx> inputs = a.file_list ? read_rfile(*a.file_list) : read_input_fastas(a.seq_files);
     log.info("Parsed " + std::to_string(inputs.size()) + " samples in input list");
@@ -587,9 +602,9 @@ int run_sketch(int argc, char **argv, int first, bool verbose, bool quiet)
         if (a.gpu >= 0) {
             log.info("Hashing on GPU " + std::to_string(a.gpu));
             Device dev(a.gpu);
-            sketch_files_gpu(dev, *a.output, inputs, kmers, a.sketch_size, !a.single_strand, a.threads, a.min_count, a.min_qual);
+            sketch_files_gpu(dev, *a.output, inputs, kmers, a.sketch_size, !a.single_strand, a.threads, a.min_count, a.min_qual, seq);
         } else {
-            sketch_files(*a.output, inputs, kmers, a.sketch_size, !a.single_strand, a.threads, a.min_count, a.min_qual);
+            sketch_files(*a.output, inputs, kmers, a.sketch_size, !a.single_strand, a.threads, a.min_count, a.min_qual, seq);
         }
     } catch (const std::exception &e) {
         throw Panic(e.what());   // the reference panics on unreadable / empty input
@@ -1072,7 +1087,7 @@ int main(int argc, char **argv)
     }
     if (sub >= argc || strcmp(argv[sub], "-h") == 0 || strcmp(argv[sub], "--help") == 0) {
         std::cout << "Usage: sketchlib [OPTIONS] <COMMAND>\n\nCommands:\n"
-                     "  sketch  Create sketches from input data (DNA assemblies and read sets; CPU, or GPU with --gpu)\n"
+                     "  sketch  Create sketches from input data (DNA assemblies and read sets, amino-acid sequences; CPU, or GPU with --gpu)\n"
                      "  dist    Calculate pairwise distances using sketches (GPU)\n"
                      "  inverted build|query|precluster  Inverted index of single-k sketches; match queries against it (GPU);\n"
                      "                                   kNN restricted to its candidates (GPU)\n";

@@ -90,6 +90,7 @@ class MultiSketch {
     size_t sample_stride() const { return sample_stride_; }
     size_t kmer_stride() const { return kmer_stride_; }
     const std::string &hash_type() const { return hash_type_; }
+    void set_hash_type(const std::string &t) { hash_type_ = t; }   // "DNA" | "AA:Level1|2|3" (a database written by `sketch`)
     const std::string &version() const { return sketch_version_; }
     const std::vector<SketchMeta> &metadata() const { return sketch_metadata_; }
 

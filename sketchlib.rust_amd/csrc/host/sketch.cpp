@@ -1,4 +1,5 @@
 #include "sketch.hpp"
+#include "aahash.hpp"
 #include "inverted.hpp"
 #include "read_filter.hpp"
 
@@ -44,6 +45,8 @@ inline bool valid_base(uint8_t b)
 }
 inline uint8_t encode_base(uint8_t b) { return (b >> 1) & 0x3; }  // hashing/mod.rs:82-85
 
+}  // namespace
+
 std::string read_maybe_gz(const std::string &path)
 {
     gzFile f = gzopen(path.c_str(), "rb");  // transparently reads plain files too
@@ -61,8 +64,6 @@ std::string read_maybe_gz(const std::string &path)
     if (n < 0) throw std::runtime_error("Invalid FASTA/Q record in " + path);
     return data;
 }
-
-}  // namespace
 
 void add_fasta(const std::string &path, Sequence &s)
 {
@@ -451,24 +452,28 @@ std::vector<uint16_t> sketch_sample_inverted(const InputFastx &input, size_t k, 
 
 MultiSketch sketch_files(const std::string &output_prefix, const std::vector<InputFastx> &inputs,
                          const std::vector<size_t> &kmers, uint64_t sketch_size, bool rc, size_t threads,
-                         uint16_t min_count, uint8_t min_qual)
+                         uint16_t min_count, uint8_t min_qual, const SeqType &st)
 {
     const uint64_t ss64 = (sketch_size + 63) / 64;
     const size_t sample_words = (size_t)(ss64 * BBITS * kmers.size());
-    std::vector<SketchResult> results(inputs.size());
+    std::vector<std::vector<SketchResult>> results(inputs.size());   // (amino acids with --concat-fasta: a sample per record)
     std::atomic<size_t> next{0};
     std::string error;
-    std::mutex *err_mutex = nullptr;
-    (void)err_mutex;
+    // (fewer inputs than threads -- one FASTA of many proteins under --concat-fasta: the rest go to the samples inside an input)
+    const size_t inner_threads = std::max<size_t>(1, threads / std::max<size_t>(1, inputs.size()));
     auto worker = [&]() {
         for (;;) {
             const size_t i = next.fetch_add(1);
             if (i >= inputs.size()) break;
             try {
-                results[i] = sketch_sample(inputs[i], kmers, sketch_size, rc, min_count, min_qual);
+                if (st.aa) {
+                    results[i] = sketch_input_aa(inputs[i], kmers, sketch_size, rc, st, inner_threads);
+                } else {
+                    results[i].resize(1);
+                    results[i][0] = sketch_sample(inputs[i], kmers, sketch_size, rc, min_count, min_qual);
+                }
             } catch (const std::exception &e) {
-                results[i].meta.name.clear();
-                results[i].usigs.clear();
+                results[i].clear();
                 static std::mutex m;
                 std::lock_guard<std::mutex> lock(m);
                 if (error.empty()) error = e.what();
@@ -482,15 +487,20 @@ MultiSketch sketch_files(const std::string &output_prefix, const std::vector<Inp
     for (auto &t : pool) t.join();
     if (!error.empty()) throw std::runtime_error(error);
 
-    std::vector<uint64_t> bins(sample_words * inputs.size());
+    size_t n_samples = 0;
+    for (const auto &r : results) n_samples += r.size();
+    std::vector<uint64_t> bins(sample_words * n_samples);
     std::vector<SketchMeta> meta;
-    for (size_t i = 0; i < inputs.size(); ++i) {
-        std::copy(results[i].usigs.begin(), results[i].usigs.end(), bins.begin() + i * sample_words);
-        results[i].meta.index = i;
-        meta.push_back(results[i].meta);
+    for (auto &per_input : results) {
+        for (auto &r : per_input) {
+            std::copy(r.usigs.begin(), r.usigs.end(), bins.begin() + meta.size() * sample_words);
+            r.meta.index = meta.size();
+            meta.push_back(r.meta);
+        }
     }
     MultiSketch::write_sketch_data(output_prefix, bins.data(), bins.size());
     MultiSketch m(std::move(meta), ss64 * 64, kmers);
+    m.set_hash_type(st.hash_type());
     m.save_metadata(output_prefix);
     m.set_bins(std::move(bins));
     return m;

@@ -1,9 +1,9 @@
 // sketch.hpp -- CPU assembly sketcher: gz/plain FASTA -> canonical ntHash -> bin minima ->
 // densify -> 14-plane transpose, i.e. the producer of the `.skm/.skd` files the distance
 // path consumes.  Mirrors the reference's `sketch` command for DNA
-// assemblies (src/sketch/mod.rs:74-258,283-391, src/hashing/nthash_iterator.rs); reads
-// (FASTQ + k-mer count filter), amino-acid and structure alphabets are not part of this
-// build.
+// assemblies and read sets (src/sketch/mod.rs:74-258,283-391, src/hashing/nthash_iterator.rs; reads: FASTQ + k-mer count
+// filter, read_filter.hpp).  Amino-acid sequences (`--seq-type aa`, SeqType below) take the aaHash path of aahash.hpp and share
+// the bin minimum, densification, transpose and writers here; the structure alphabet (`pdb`) is not part of this build.
 #pragma once
 
 #include <cstdint>
@@ -19,6 +19,16 @@ constexpr uint64_t SIGN_MOD = (1ull << 61) - 1;  // src/sketch/mod.rs:36
 
 // (sample name, sequence files), one entry per sample (src/io.rs:20-40, rfile parsing)
 using InputFastx = std::pair<std::string, std::vector<std::string>>;
+
+// What is hashed (HashType, src/hashing/mod.rs:29-39; `sketch --seq-type / --level / --concat-fasta`, src/lib.rs:242-302)
+struct SeqType {
+    bool aa = false;             // amino acids (aaHash, forward only) instead of DNA (canonical ntHash)
+    int level = 1;               // aaHash grouping level 1 / 2 / 3 (aa only)
+    bool concat_fasta = false;   // every FASTA record a sample of its own, named <name>_<n> (aa only)
+    std::string hash_type() const { return aa ? "AA:Level" + std::to_string(level) : "DNA"; }   // as MultiSketch holds it
+};
+
+std::string read_maybe_gz(const std::string &path);   // a whole gz or plain file
 
 std::vector<InputFastx> read_input_fastas(const std::vector<std::string> &seq_files);  // io.rs:20-40
 std::vector<InputFastx> read_rfile(const std::string &file_list);                      // name<TAB>file[<TAB>file]
@@ -59,14 +69,14 @@ SketchResult sketch_sample(const InputFastx &input, const std::vector<size_t> &k
 // keep their input order (what the reference yields with --threads 1).
 MultiSketch sketch_files(const std::string &output_prefix, const std::vector<InputFastx> &inputs,
                          const std::vector<size_t> &kmers, uint64_t sketch_size, bool rc, size_t threads,
-                         uint16_t min_count = 5, uint8_t min_qual = 20);
+                         uint16_t min_count = 5, uint8_t min_qual = 20, const SeqType &st = SeqType());
 
 class Device;
 // The same with the hashing / bin-minimum loop on the GPU (SURVEY 8f row f4,
 // skl_sketch_signs): FASTA parsing, densification, transpose and the file writers stay on the
-// host.  Output files are byte-identical to sketch_files'.
+// host.  Amino acids: skl_sketch_signs_aa.  Output files are byte-identical to sketch_files'.
 MultiSketch sketch_files_gpu(Device &dev, const std::string &output_prefix, const std::vector<InputFastx> &inputs,
                              const std::vector<size_t> &kmers, uint64_t sketch_size, bool rc, size_t threads,
-                         uint16_t min_count = 5, uint8_t min_qual = 20);
+                             uint16_t min_count = 5, uint8_t min_qual = 20, const SeqType &st = SeqType());
 
 }  // namespace skl_host

@@ -14,6 +14,7 @@
 #include <stdexcept>
 #include <thread>
 
+#include "aahash.hpp"
 #include "distances.hpp"
 #include "read_filter.hpp"
 #include "sketch.hpp"
@@ -195,10 +196,130 @@ void reads_signs_gpu(Device &dev, const std::vector<Sequence> &seqs, const std::
 }
 }  // namespace
 
+namespace {
+// `sketch --gpu --seq-type aa`: protein FASTA parsed into residue codes on host threads (load_aa_samples), aaHash and bin
+// minima on the device (skl_sketch_signs_aa), densify / transpose / writers on the host.  One call takes
+// samples up to 1 Gi residues and 1 GiB of signs -- at 1 024 bins and one k-mer length a protein's signs are 8 KiB, so a
+// million proteins come back in eight calls -- and the library cuts a call into device batches of 256 MiB of signs.
+MultiSketch sketch_files_gpu_aa(Device &dev, const std::string &output_prefix, const std::vector<InputFastx> &inputs,
+                                const std::vector<size_t> &kmers, uint64_t sketch_size, bool rc, size_t threads, const SeqType &st)
+{
+    const size_t nk = kmers.size();
+    const uint64_t ss64 = (sketch_size + 63) / 64;
+    const uint64_t num_bins = ss64 * 64;
+    const size_t sample_words = (size_t)(ss64 * BBITS * nk);
+    const bool timing = std::getenv("SKL_CLI_TIMING") != nullptr;
+    const auto t_start = std::chrono::steady_clock::now();
+    auto since = [&] { return std::chrono::duration<double>(std::chrono::steady_clock::now() - t_start).count(); };
+
+    std::vector<std::vector<AaSample>> per_input(inputs.size());
+    std::vector<std::string> input_error(inputs.size());
+    parallel_for(inputs.size(), threads, [&](size_t i) {
+        try {
+            per_input[i] = load_aa_samples(inputs[i], st.concat_fasta);
+        } catch (const std::exception &e) {
+            input_error[i] = e.what();
+        }
+    });
+    for (const auto &e : input_error) {
+        if (!e.empty()) throw std::runtime_error(e);
+    }
+    std::vector<AaSample> samples;
+    for (auto &v : per_input) {
+        for (auto &a : v) samples.push_back(std::move(a));
+    }
+    per_input.clear();
+    const size_t n = samples.size();
+    const double t_parse = since();
+    double t_gpu = 0, t_finish = 0;
+
+    std::vector<uint64_t> bins(sample_words * n, 0);
+    std::vector<SketchMeta> meta(n);
+    std::vector<std::string> sample_error(n);
+    constexpr uint64_t CALL_RESIDUES = 1ull << 30, CALL_SIGN_BYTES = 1ull << 30;
+    const uint64_t sign_bytes = (uint64_t)nk * num_bins * sizeof(uint64_t);
+    std::unique_ptr<uint64_t[]> signs;
+    size_t signs_room = 0;
+    for (size_t b0 = 0; b0 < n;) {
+        size_t b1 = b0;
+        uint64_t residues_in_call = 0;
+        while (b1 < n && (b1 == b0 || (residues_in_call + samples[b1].codes.size() <= CALL_RESIDUES &&
+                                       (b1 - b0 + 1) * sign_bytes <= CALL_SIGN_BYTES))) {
+            residues_in_call += samples[b1].codes.size();
+            ++b1;
+        }
+        const size_t nb = b1 - b0;
+        std::vector<uint64_t> res_begin(nb + 1, 0);
+        for (size_t i = 0; i < nb; ++i) res_begin[i + 1] = res_begin[i] + samples[b0 + i].codes.size();
+        std::unique_ptr<uint8_t[]> residues(new uint8_t[std::max<uint64_t>(res_begin[nb], 1)]);
+        parallel_for(nb, threads, [&](size_t i) {
+            const auto &c = samples[b0 + i].codes;
+            if (!c.empty()) memcpy(residues.get() + res_begin[i], c.data(), c.size());
+        });
+        if (signs_room < nb * nk * num_bins) {   // (not zero-filled: the library writes every word; the first call is the largest but for a long sample later on)
+            signs_room = nb * nk * num_bins;
+            signs.reset(new uint64_t[signs_room]);
+        }
+        const double t0 = since();
+        if (skl_sketch_signs_aa(dev.ctx(), residues.get(), res_begin.data(), nb, kmers.data(), nk, num_bins, st.level,
+                                st.concat_fasta ? 1 : 0, signs.get()) != SKL_OK) {
+            throw std::runtime_error(skl_last_error());
+        }
+        const double t1 = since();
+        t_gpu += t1 - t0;
+        parallel_for(nb, threads, [&](size_t i) {
+            const size_t at = b0 + i;
+            const AaSample &a = samples[at];
+            if (a.codes.empty()) {
+                sample_error[at] = a.name + " has no valid sequence";
+                return;
+            }
+            bool densified = false;
+            for (size_t ki = 0; ki < nk; ++ki) {
+                const uint64_t *src = signs.get() + (i * nk + ki) * num_bins;
+                std::vector<uint64_t> sg(src, src + num_bins);
+                if (std::all_of(sg.begin(), sg.end(), [](uint64_t v) { return v == UINT64_MAX; })) {
+                    sample_error[at] = "K-mer larger than smallest valid sequence";   // as the CPU path
+                    return;
+                }
+                densified |= densify_bin(sg);
+                fill_usigs(bins.data() + at * sample_words + ki * ss64 * BBITS, sg);
+            }
+            SketchMeta &m = meta[at];
+            m.name = a.name;
+            m.rc = rc;
+            m.reads = false;
+            m.seq_length = a.codes.size();
+            m.densified = densified;
+            m.non_acgt = a.invalid;
+            m.index = at;
+        });
+        for (size_t at = b0; at < b1; ++at) {   // the first sample in input order that fails, as the CPU path on one thread
+            if (!sample_error[at].empty()) throw std::runtime_error(sample_error[at]);
+            std::vector<uint8_t>().swap(samples[at].codes);
+        }
+        t_finish += since() - t1;
+        b0 = b1;
+    }
+    const double t_before_write = since();
+    MultiSketch::write_sketch_data(output_prefix, bins.data(), bins.size());
+    MultiSketch m(std::move(meta), ss64 * 64, kmers);
+    m.set_hash_type(st.hash_type());
+    m.save_metadata(output_prefix);
+    m.set_bins(std::move(bins));
+    if (timing) {
+        std::fprintf(stderr, "TIMING sketch --gpu --seq-type aa: parse=%.3fs gather+upload+kernel+download=%.3fs densify+transpose=%.3fs write=%.3fs\n",
+                     t_parse, t_gpu, t_finish, since() - t_before_write);
+    }
+    return m;
+}
+}  // namespace
+
 MultiSketch sketch_files_gpu(Device &dev, const std::string &output_prefix, const std::vector<InputFastx> &inputs,
                              const std::vector<size_t> &kmers, uint64_t sketch_size, bool rc, size_t threads,
-                             uint16_t min_count, uint8_t min_qual)
+                             uint16_t min_count, uint8_t min_qual, const SeqType &st)
 {
+    if (st.aa) return sketch_files_gpu_aa(dev, output_prefix, inputs, kmers, sketch_size, rc, threads, st);
     const size_t n = inputs.size(), nk = kmers.size();
     const uint64_t ss64 = (sketch_size + 63) / 64;   // num_bins, sketch/mod.rs:49-54
     const uint64_t num_bins = ss64 * 64;

@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "dense_plan.hpp"   // slice_plan()
+#include "aa_plan.hpp"      // the amino-acid sketching call's work plan and locators
 #include "work_map.hpp"     // which workgroup computes what: TILE_PREFIX_INLINE, the fields below it reads and plans
 
 namespace skl {
@@ -377,6 +378,28 @@ int sketch_span();
 int sketch_span_lds();
 int sketch_wg_lds();   // threads (= spans) per workgroup of the LDS-staged kernel: a sample's span count is padded to a multiple
 int sketch_lds_bins_max();   // most bins whose minima the LDS-staged kernel keeps in LDS; above it they stay in global memory
+
+// GPU sketching of amino-acid sequences (aa_sketch_kernel.hip): bin minima of the forward aaHash of every window of k valid
+// residues.  One launch = the items [first_item, first_item + n_items) of one form (aa_plan.hpp), all of samples
+// [sample_base, ...) of one batch.
+struct AaSketchArgs {
+    const uint8_t *codes;          // residue codes of the batch (0 = separator, 1..20), 256-byte aligned, 8 readable bytes past the end
+    uint64_t res_base;             // res_begin of the batch's first sample: sample s starts at codes + res_begin[s] - res_base
+    const uint64_t *res_begin;     // [n_samples + 1], the whole call's
+    const uint64_t *item_begin;    // [n_samples + 1] AaPlan::wg_begin (staged) or span_begin (unstaged)
+    uint64_t first_item, n_items;
+    uint32_t n_samples, sample_base, nk;
+    const uint32_t *kmers;         // [nk]
+    const uint64_t *seeds;         // [21] by residue code at the call's level ([0] = 0)
+    const uint64_t *roll;          // [nk][21] srol^k of each seed
+    uint64_t num_bins, bin_size;
+    double inv_bin_size;
+    uint32_t end_rule;             // 1: the window at len - k is hashed only if the residue before it is valid
+    uint32_t short_span;           // window starts per thread of the unstaged form
+    uint32_t staged;               // 1: staged form (workgroup items), 0: unstaged form (thread items)
+    uint64_t *signs;               // [batch samples][nk][num_bins], pre-set to UINT64_MAX
+};
+hipError_t launch_aa_sketch_signs(const AaSketchArgs &args, hipStream_t stream);
 
 // Survivors of the read sketcher's count filter (read_survivors.hip, skl_reads_survivors): every valid window
 // of every (sample, k) stream in a range of window starts whose sign is below its bin's threshold.
