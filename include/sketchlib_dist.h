@@ -407,6 +407,39 @@ int skl_sketch_signs_packed(skl_ctx *ctx, const uint32_t *packed, const uint64_t
 int skl_sketch_signs_aa(skl_ctx *ctx, const uint8_t *residues, const uint64_t *res_begin, size_t n_samples,
                         const size_t *kmers, size_t nk, uint64_t num_bins, int level, int concat_end_rule,
                         uint64_t *out_signs);
+/* Finishing (sample, k) streams of bin minima on the device: Sketch::densify_bin (src/sketch/mod.rs:237-258)
+ * and the 14-plane transpose of fill_usigs (mod.rs:215-223), a workgroup per stream -- what a sketch file stores of a stream,
+ * num_bins / 64 * 14 u64 words instead of num_bins u64 signs.  `signs`: [n_streams][num_bins] as skl_sketch_signs* return
+ * them, u64::MAX for an empty bin.  out_usigs: [n_streams][num_bins / 64 * 14], word c * 14 + p = bit p of bins 64 c ..
+ * 64 c + 63 after densification, byte for byte what the host loops give.  out_first_sign: [n_streams] the densified
+ * signs[0] with all 64 bits (a read set's length estimate needs it), or null.  out_flags: [n_streams] bytes, bit 0
+ * (SKL_FINISH_DENSIFIED) at least one bin was empty and filled from another; bit 1 (SKL_FINISH_EMPTY) EVERY bin is
+ * u64::MAX -- the words are zeroed, the first sign is u64::MAX and the error is the caller's to raise, as the all-max
+ * convention of skl_sketch_signs* leaves it (the reference's loop does not end on such a stream; the kernel never probes
+ * it); bit 2 (SKL_FINISH_UNFINISHED) a bin needed more probes than the kernel's cap (2 048, csrc/finish_plan.hpp;
+ * SKL_FINISH_MAX_ATTEMPTS overrides), so the library finished that stream on the host from its raw signs: the bytes are
+ * the same, the flag only reports it.  num_bins must be a multiple of 64 (SKL_ERR_INVALID_ARG otherwise); up to 8 192
+ * bins a stream's targets live in LDS, above that in device scratch -- any size is finished on the device.
+ * SKL_SKETCH_FINISH=host finishes every stream on host threads instead (A/B timing, escape hatch).  Host pointers. */
+#define SKL_FINISH_DENSIFIED 1
+#define SKL_FINISH_EMPTY 2
+#define SKL_FINISH_UNFINISHED 4
+int skl_sketch_finish(skl_ctx *ctx, const uint64_t *signs, size_t n_streams, uint64_t num_bins, uint64_t *out_usigs,
+                      uint64_t *out_first_sign, uint8_t *out_flags);
+/* skl_sketch_signs_packed with every stream finished on the device: the finish launch follows each batch's bin-minimum
+ * launch on the same stream and only the finished words cross PCIe (1 792 B per stream at 1 024 bins instead of 8 192 B).
+ * out_usigs: [n_samples][nk][num_bins / 64 * 14] -- the layout of a sample's words in a .skd file; out_first_sign:
+ * [n_samples][nk] or null; out_flags: [n_samples][nk], as skl_sketch_finish.  A sample without a valid k-mer of some
+ * length comes back SKL_FINISH_EMPTY for that stream. */
+int skl_sketch_usigs_packed(skl_ctx *ctx, const uint32_t *packed, const uint64_t *code_begin,
+                            const uint64_t *offsets, const uint64_t *offset_begin, size_t n_samples,
+                            const size_t *kmers, size_t nk, uint64_t num_bins, int rc, uint64_t *out_usigs,
+                            uint64_t *out_first_sign, uint8_t *out_flags);
+/* skl_sketch_signs_aa with every stream finished on the device, batch by batch as that call cuts them; outputs as
+ * skl_sketch_usigs_packed. */
+int skl_sketch_usigs_aa(skl_ctx *ctx, const uint8_t *residues, const uint64_t *res_begin, size_t n_samples,
+                        const size_t *kmers, size_t nk, uint64_t num_bins, int level, int concat_end_rule,
+                        uint64_t *out_usigs, uint64_t *out_first_sign, uint8_t *out_flags);
 /* Shapes of that call's two kernels: what = 0 window starts per thread of the staged form, 1 its threads per workgroup,
  * 2 most bins it keeps in LDS, 3 longest k-mer it takes, 4 residues from which a sample is staged (SKL_AA_LONG_MIN
  * overrides), 5 window starts per thread of the unstaged form when the longest k-mer is kmax, 6 its threads per

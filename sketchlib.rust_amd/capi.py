@@ -119,6 +119,9 @@ _SIG = [
     ("skl_sketch_signs_packed", C.c_int, [_P, _P, _P, _P, _P, C.c_size_t, _P, C.c_size_t, C.c_uint64, C.c_int, _P]),
     ("skl_sketch_signs_aa", C.c_int, [_P, _P, _P, C.c_size_t, _P, C.c_size_t, C.c_uint64, C.c_int, C.c_int, _P]),
     ("skl_sketch_aa_shape", C.c_int, [C.c_int, C.c_size_t]),
+    ("skl_sketch_finish", C.c_int, [_P, _P, C.c_size_t, C.c_uint64, _P, _P, _P]),
+    ("skl_sketch_usigs_packed", C.c_int, [_P, _P, _P, _P, _P, C.c_size_t, _P, C.c_size_t, C.c_uint64, C.c_int, _P, _P, _P]),
+    ("skl_sketch_usigs_aa", C.c_int, [_P, _P, _P, C.c_size_t, _P, C.c_size_t, C.c_uint64, C.c_int, C.c_int, _P, _P, _P]),
     ("skl_reads_create", C.c_int, [_P, _P, _P, _P, _P, C.c_size_t, _P, C.c_size_t, C.c_uint64, C.c_int, C.POINTER(_P)]),
     ("skl_reads_survivors", C.c_int, [_P, _P, _P, _P, C.c_uint64, _P, _P]),
     ("skl_reads_destroy", C.c_int, [_P]),
@@ -772,6 +775,56 @@ def sketch_signs_aa(ctx, residues, res_begin, kmers, num_bins, level=1, concat_e
                                       out.ctypes.data))
     return out
 
+FINISH_DENSIFIED, FINISH_EMPTY, FINISH_UNFINISHED = 1, 2, 4
+BBITS = 14
+
+
+def sketch_finish(ctx, signs, num_bins=None):
+    """skl_sketch_finish: densify_bin + the 14-plane transpose of [..., num_bins] uint64 bin minima on the device ->
+    (usigs [..., num_bins // 64 * 14] uint64, first_sign [...] uint64, flags [...] uint8: FINISH_* bits)."""
+    signs = np.ascontiguousarray(signs, dtype=np.uint64)
+    num_bins = signs.shape[-1] if num_bins is None else int(num_bins)
+    lead = signs.shape[:-1]
+    n = int(np.prod(lead, dtype=np.int64))
+    usigs = np.zeros(lead + (num_bins // 64 * BBITS,), dtype=np.uint64)
+    first = np.zeros(lead, dtype=np.uint64)
+    flags = np.zeros(lead, dtype=np.uint8)
+    _check(load().skl_sketch_finish(ctx._h, signs.ctypes.data, n, num_bins, usigs.ctypes.data, first.ctypes.data, flags.ctypes.data))
+    return usigs, first, flags
+
+
+def sketch_usigs_packed(ctx, packed, code_begin, offsets, offset_begin, kmers, num_bins, rc=True):
+    """skl_sketch_usigs_packed: sketch_signs_packed with every (sample, k) stream finished on the device ->
+    (usigs [n, nk, num_bins // 64 * 14], first_sign [n, nk], flags [n, nk]) as sketch_finish."""
+    packed = np.ascontiguousarray(packed, dtype=np.uint32)
+    code_begin = np.ascontiguousarray(code_begin, dtype=np.uint64)
+    offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+    offset_begin = np.ascontiguousarray(offset_begin, dtype=np.uint64)
+    kmers = np.ascontiguousarray(kmers, dtype=np.uintp)
+    n = code_begin.size - 1
+    usigs = np.zeros((n, kmers.size, num_bins // 64 * BBITS), dtype=np.uint64)
+    first = np.zeros((n, kmers.size), dtype=np.uint64)
+    flags = np.zeros((n, kmers.size), dtype=np.uint8)
+    _check(load().skl_sketch_usigs_packed(ctx._h, packed.ctypes.data if packed.size else None, code_begin.ctypes.data,
+                                          offsets.ctypes.data if offsets.size else None, offset_begin.ctypes.data, n,
+                                          kmers.ctypes.data, kmers.size, num_bins, int(rc), usigs.ctypes.data, first.ctypes.data,
+                                          flags.ctypes.data))
+    return usigs, first, flags
+
+
+def sketch_usigs_aa(ctx, residues, res_begin, kmers, num_bins, level=1, concat_end_rule=False):
+    """skl_sketch_usigs_aa: sketch_signs_aa with every (sample, k) stream finished on the device; returns as sketch_usigs_packed."""
+    residues = np.ascontiguousarray(residues, dtype=np.uint8)
+    res_begin = np.ascontiguousarray(res_begin, dtype=np.uint64)
+    kmers = np.ascontiguousarray(kmers, dtype=np.uintp)
+    n = res_begin.size - 1
+    usigs = np.zeros((n, kmers.size, num_bins // 64 * BBITS), dtype=np.uint64)
+    first = np.zeros((n, kmers.size), dtype=np.uint64)
+    flags = np.zeros((n, kmers.size), dtype=np.uint8)
+    _check(load().skl_sketch_usigs_aa(ctx._h, residues.ctypes.data if residues.size else None, res_begin.ctypes.data, n,
+                                      kmers.ctypes.data, kmers.size, num_bins, int(level), int(bool(concat_end_rule)),
+                                      usigs.ctypes.data, first.ctypes.data, flags.ctypes.data))
+    return usigs, first, flags
 
 
 class Reads:

@@ -364,7 +364,7 @@ Knobs read_knobs()
 {
     Knobs k;
     // The product library reads ELEVEN switches: the timing cadence, the device topology the tile order assumes, and the knobs
-    // with which the tests force the banded / sliced / 32-row forms (and the inverted query's bands, the sketching call's upload batches, the pair list's bands) on inputs small enough for the oracle.  Everything that
+    // with which the tests force the banded / sliced / 32-row forms (and the inverted query's bands, the sketching call's upload batches, where and how far its streams are finished, the pair list's bands) on inputs small enough for the oracle.  Everything that
     // exists only to time one form against another ("A/B only, results identical") is read by the A/B build alone (-DSKL_AB),
     // where scripts/ab_sweep.py, scripts/forced_switch_suites.sh and the tests marked `ab_library` find it.
     k.timing_every = std::max(0ll, env_int("SKL_TIMING_EVERY", 0));
@@ -378,6 +378,11 @@ Knobs read_knobs()
     k.aa_batch_sign_bytes = std::max(0ll, env_int("SKL_AA_BATCH_SIGN_BYTES", 0));
     k.aa_long_min = std::max(0ll, env_int("SKL_AA_LONG_MIN", 0));
     k.pairs_band = std::max(0ll, env_int("SKL_PAIRS_BAND", 0));
+    k.finish_max_attempts = std::max(0ll, env_int("SKL_FINISH_MAX_ATTEMPTS", 0));
+    {
+        const char *fin = getenv("SKL_SKETCH_FINISH");
+        k.sketch_finish_host = fin && strcmp(fin, "host") == 0;
+    }
     k.tail_slices = (int)std::min(8ll, std::max(0ll, env_int("SKL_TAIL_SLICES", 4)));
     k.tail_max_pct = env_int("SKL_TAIL_MAX_PCT", 90);
     k.tile32_min = env_int("SKL_TILE32_MIN", 8ll << 20);

@@ -1,20 +1,22 @@
-// capi_aa.cpp -- skl_sketch_signs_aa of include/sketchlib_dist.h: GPU sketching of amino-acid sequences.
+// capi_aa.cpp -- skl_sketch_signs_aa and skl_sketch_usigs_aa of include/sketchlib_dist.h: GPU sketching of amino-acid sequences.
 // Kernels: aa_sketch_kernel.hip; who hashes what: aa_plan.hpp (pure); seeds and roll values: aa_seeds.hpp.
 #include "capi_internal.hpp"
 
 #include <algorithm>
+#include <memory>
 #include <cstring>
 
 #include "aa_seeds.hpp"
 
 using namespace skl;
 
-extern "C" int skl_sketch_signs_aa(skl_ctx *ctx, const uint8_t *residues, const uint64_t *res_begin, size_t n_samples,
-                                   const size_t *kmers, size_t nk, uint64_t num_bins, int level, int concat_end_rule,
-                                   uint64_t *out_signs)
+// fin: every stream is finished on the device behind its batch's bin minima and goes there; out_signs unused
+static int sketch_signs_aa_impl(skl_ctx *ctx, const uint8_t *residues, const uint64_t *res_begin, size_t n_samples,
+                                const size_t *kmers, size_t nk, uint64_t num_bins, int level, int concat_end_rule,
+                                uint64_t *out_signs, const FinishDest *fin)
 {
     SKL_TRY(ctx_bind(ctx));
-    if (!res_begin || !kmers || !out_signs) return fail(SKL_ERR_INVALID_ARG, "null argument");
+    if (!res_begin || !kmers || (!out_signs && !fin)) return fail(SKL_ERR_INVALID_ARG, "null argument");
     if (n_samples == 0 || nk == 0) return SKL_OK;
     if (num_bins == 0 || num_bins > 0xFFFFFFFFull) return fail(SKL_ERR_INVALID_ARG, "num_bins out of range");
     if (n_samples >= 0xFFFFFFFFull) return fail(SKL_ERR_INVALID_ARG, "too many samples");
@@ -53,6 +55,8 @@ extern "C" int skl_sketch_signs_aa(skl_ctx *ctx, const uint8_t *residues, const 
     void *d_codes = nullptr, *d_signs = nullptr, *d_small = nullptr;
     SKL_TRY(ctx_scratch(ctx, most_residues + 16, &d_codes, SCRATCH_SKETCH_BASES));   // (8 readable bytes past the last residue)
     SKL_TRY(ctx_scratch(ctx, most_samples * per_sample * sizeof(uint64_t), &d_signs, SCRATCH_SKETCH_SIGNS));
+    FinishDev fin_dev;
+    if (fin) SKL_TRY(finish_reserve(ctx, most_samples * nk, num_bins, &fin_dev));
     std::vector<uint64_t> small;
     auto put = [&](const uint64_t *v, size_t count) {
         const size_t at = small.size();
@@ -110,6 +114,13 @@ extern "C" int skl_sketch_signs_aa(skl_ctx *ctx, const uint8_t *residues, const 
             HIP_TRY(launch_aa_sketch_signs(a, ctx->stream));
             if (tev) HIP_TRY(hipEventRecord(tev->second, ctx->stream));
         }
+        if (fin) {   // densify + transpose behind the batch's bin minima; the words, first signs and flags come back
+            SKL_TRY(finish_launch(ctx, (const uint64_t *)d_signs, (s1 - s0) * nk, num_bins, fin_dev, 0));
+            SKL_TRY(finish_download(fin_dev, 0, (s1 - s0) * nk, num_bins, *fin, s0 * nk, ctx->stream));
+            HIP_TRY(hipStreamSynchronize(ctx->stream));
+            SKL_TRY(finish_fallback((const uint64_t *)d_signs, (s1 - s0) * nk, num_bins, *fin, s0 * nk));   // (before the next batch overwrites the signs)
+            continue;
+        }
         HIP_TRY(hipMemcpyAsync(out_signs + s0 * per_sample, d_signs, (s1 - s0) * per_sample * sizeof(uint64_t),
                                hipMemcpyDeviceToHost, ctx->stream));
         HIP_TRY(hipStreamSynchronize(ctx->stream));
@@ -121,6 +132,7 @@ extern "C" int skl_sketch_signs_aa(skl_ctx *ctx, const uint8_t *residues, const 
     ctx->last_kernel = any_staged && any_unstaged ? std::string(staged_name) + " + " + unstaged_name
                        : any_staged               ? staged_name
                                                   : unstaged_name;
+    if (fin) ctx->last_kernel += std::string(" + ") + finish_kernel_name(ctx, num_bins);
     if (ctx->scratch_bytes[SCRATCH_SKETCH_BASES] + ctx->scratch_bytes[SCRATCH_SKETCH_SIGNS] > (1ull << 30)) {   // as skl_sketch_signs
         for (int slot : {SCRATCH_SKETCH_BASES, SCRATCH_SKETCH_SIGNS}) {
             if (ctx->scratch[slot]) HIP_TRY(hipFree(ctx->scratch[slot]));
@@ -128,6 +140,32 @@ extern "C" int skl_sketch_signs_aa(skl_ctx *ctx, const uint8_t *residues, const 
             ctx->scratch_bytes[slot] = 0;
         }
     }
+    return SKL_OK;
+}
+
+extern "C" int skl_sketch_signs_aa(skl_ctx *ctx, const uint8_t *residues, const uint64_t *res_begin, size_t n_samples,
+                                   const size_t *kmers, size_t nk, uint64_t num_bins, int level, int concat_end_rule,
+                                   uint64_t *out_signs)
+{
+    return sketch_signs_aa_impl(ctx, residues, res_begin, n_samples, kmers, nk, num_bins, level, concat_end_rule, out_signs, nullptr);
+}
+
+// The same call with every (sample, k) stream finished (SKL_SKETCH_FINISH=host: the signs come back and host threads finish them).
+extern "C" int skl_sketch_usigs_aa(skl_ctx *ctx, const uint8_t *residues, const uint64_t *res_begin, size_t n_samples,
+                                   const size_t *kmers, size_t nk, uint64_t num_bins, int level, int concat_end_rule,
+                                   uint64_t *out_usigs, uint64_t *out_first_sign, uint8_t *out_flags)
+{
+    SKL_TRY(ctx_bind(ctx));
+    if (!out_usigs || !out_flags) return fail(SKL_ERR_INVALID_ARG, "null argument");
+    SKL_TRY(finish_check_bins(num_bins));
+    const FinishDest dst{out_usigs, out_first_sign, out_flags};
+    if (!ctx->knobs.sketch_finish_host) {
+        return sketch_signs_aa_impl(ctx, residues, res_begin, n_samples, kmers, nk, num_bins, level, concat_end_rule, nullptr, &dst);
+    }
+    std::unique_ptr<uint64_t[]> signs(new uint64_t[std::max<size_t>(n_samples * nk * num_bins, 1)]);   // (not zero-filled: the call writes every word)
+    SKL_TRY(sketch_signs_aa_impl(ctx, residues, res_begin, n_samples, kmers, nk, num_bins, level, concat_end_rule, signs.get(), nullptr));
+    finish_on_host(signs.get(), n_samples * nk, num_bins, dst, false);
+    ctx->last_kernel += std::string(" + ") + finish_kernel_name(ctx, num_bins);
     return SKL_OK;
 }
 

@@ -4,6 +4,7 @@
 #include "capi_internal.hpp"
 
 #include <algorithm>
+#include <memory>
 #include <atomic>
 #include <cstring>
 #include <thread>
@@ -84,10 +85,11 @@ static void pack_samples(const uint8_t *codes, const uint64_t *code_begin, const
 // are packed on host threads straight into a pinned two-batch ring, so their upload is a true DMA.
 static int sketch_signs_impl(skl_ctx *ctx, const uint8_t *codes, const uint32_t *packed, const uint64_t *code_begin,
                              const uint64_t *offsets, const uint64_t *offset_begin, size_t n_samples,
-                             const size_t *kmers, size_t nk, uint64_t num_bins, int rc, uint64_t *out_signs)
+                             const size_t *kmers, size_t nk, uint64_t num_bins, int rc, uint64_t *out_signs,
+                             const FinishDest *fin = nullptr)   // fin: the streams are finished on the device and go there; out_signs unused
 {
     SKL_TRY(ctx_bind(ctx));
-    if (!code_begin || !offset_begin || !kmers || !out_signs) return fail(SKL_ERR_INVALID_ARG, "null argument");
+    if (!code_begin || !offset_begin || !kmers || (!out_signs && !fin)) return fail(SKL_ERR_INVALID_ARG, "null argument");
     if (n_samples == 0 || nk == 0) return SKL_OK;
     if (num_bins == 0) return fail(SKL_ERR_INVALID_ARG, "num_bins is zero");
     const uint64_t n_codes = code_begin[n_samples], n_offs = offset_begin[n_samples];
@@ -135,6 +137,8 @@ static int sketch_signs_impl(skl_ctx *ctx, const uint8_t *codes, const uint32_t 
     SKL_TRY(ctx_scratch(ctx, sign_words * sizeof(uint64_t), &d_signs, SCRATCH_SKETCH_SIGNS));
     const size_t small_words = 4 * (n_samples + 1) + n_offs + 9 * nk + 8;   // u64 each (the k-mer lengths: two per word)
     SKL_TRY(ctx_scratch(ctx, small_words * sizeof(uint64_t), &d_small, SCRATCH_SKETCH_SMALL));
+    FinishDev fin_dev;
+    if (fin) SKL_TRY(finish_reserve(ctx, n_samples * nk, num_bins, &fin_dev));
     std::vector<uint64_t> small;
     small.reserve(small_words);
     auto put = [&](const uint64_t *v, size_t count) {
@@ -233,12 +237,17 @@ static int sketch_signs_impl(skl_ctx *ctx, const uint8_t *codes, const uint32_t 
         if (tev) HIP_TRY(hipEventRecord(tev->first, ctx->stream));
         HIP_TRY(launch_sketch_signs(a, ctx->stream));
         if (tev) HIP_TRY(hipEventRecord(tev->second, ctx->stream));
+        if (fin) {   // densify + transpose behind the batch's bin minima, ahead of its download
+            const size_t s0 = cuts[b], s1 = cuts[b + 1];
+            SKL_TRY(finish_launch(ctx, (const uint64_t *)d_signs + s0 * nk * num_bins, (s1 - s0) * nk, num_bins, fin_dev, s0 * nk));
+        }
         HIP_TRY(hipEventRecord(ev[3 * b + 1], ctx->stream));
         return SKL_OK;
     };
     auto download = [&](size_t b) -> int {   // (a copy into pageable memory blocks its caller: issued after the next batch's launch)
         const size_t s0 = cuts[b], s1 = cuts[b + 1];
         HIP_TRY(hipStreamWaitEvent(ctx->aux_stream, ev[3 * b + 1], 0));
+        if (fin) return finish_download(fin_dev, s0 * nk, (s1 - s0) * nk, num_bins, *fin, s0 * nk, ctx->aux_stream);
         HIP_TRY(hipMemcpyAsync(out_signs + s0 * nk * num_bins, (const uint64_t *)d_signs + s0 * nk * num_bins,
                                (s1 - s0) * nk * num_bins * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->aux_stream));
         return SKL_OK;
@@ -260,6 +269,10 @@ static int sketch_signs_impl(skl_ctx *ctx, const uint8_t *codes, const uint32_t 
                              "canonical ntHash through a fused 16-entry step table, bin minima in global memory)";
     HIP_TRY(hipStreamSynchronize(ctx->aux_stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
+    if (fin) {   // (the call's signs are all still on the device)
+        ctx->last_kernel += std::string(" + ") + finish_kernel_name(ctx, num_bins);
+        SKL_TRY(finish_fallback((const uint64_t *)d_signs, n_samples * nk, num_bins, *fin, 0));
+    }
     // The sketching buffers belong to the context so that a run of sketch calls does not allocate per call -- but beyond 1 GiB
     // they would sit in the way of what follows (the kNN drivers size their bands by the free memory): released, with the
     // pinned ring.  (Both streams are idle here.)
@@ -291,6 +304,28 @@ extern "C" int skl_sketch_signs_packed(skl_ctx *ctx, const uint32_t *packed, con
 {
     if (!packed && code_begin && n_samples && code_begin[n_samples]) return fail(SKL_ERR_INVALID_ARG, "null argument");
     return sketch_signs_impl(ctx, nullptr, packed, code_begin, offsets, offset_begin, n_samples, kmers, nk, num_bins, rc, out_signs);
+}
+
+// The same call with every (sample, k) stream finished: densify_bin and the 14-plane transpose on the device, behind each
+// batch's bin minima (SKL_SKETCH_FINISH=host: the signs come back and host threads finish them, as callers did before).
+extern "C" int skl_sketch_usigs_packed(skl_ctx *ctx, const uint32_t *packed, const uint64_t *code_begin,
+                                       const uint64_t *offsets, const uint64_t *offset_begin, size_t n_samples,
+                                       const size_t *kmers, size_t nk, uint64_t num_bins, int rc, uint64_t *out_usigs,
+                                       uint64_t *out_first_sign, uint8_t *out_flags)
+{
+    SKL_TRY(ctx_bind(ctx));
+    if (!out_usigs || !out_flags) return fail(SKL_ERR_INVALID_ARG, "null argument");
+    if (!packed && code_begin && n_samples && code_begin[n_samples]) return fail(SKL_ERR_INVALID_ARG, "null argument");
+    SKL_TRY(finish_check_bins(num_bins));
+    const FinishDest dst{out_usigs, out_first_sign, out_flags};
+    if (!ctx->knobs.sketch_finish_host) {
+        return sketch_signs_impl(ctx, nullptr, packed, code_begin, offsets, offset_begin, n_samples, kmers, nk, num_bins, rc, nullptr, &dst);
+    }
+    std::unique_ptr<uint64_t[]> signs(new uint64_t[std::max<size_t>(n_samples * nk * num_bins, 1)]);   // (not zero-filled: the call writes every word)
+    SKL_TRY(sketch_signs_impl(ctx, nullptr, packed, code_begin, offsets, offset_begin, n_samples, kmers, nk, num_bins, rc, signs.get()));
+    finish_on_host(signs.get(), n_samples * nk, num_bins, dst, false);
+    ctx->last_kernel += std::string(" + ") + finish_kernel_name(ctx, num_bins);
+    return SKL_OK;
 }
 
 // The last step of a candidate-list call: the per-row selection of rows [r, r + rows) -- `launch(first_row, rows)` --

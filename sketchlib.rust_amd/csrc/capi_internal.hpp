@@ -1,6 +1,6 @@
 // capi_internal.hpp -- shared between the translation units that implement
 // include/sketchlib_dist.h (capi.cpp: contexts, slabs, dense calls; capi_knn.cpp: the kNN
-// drivers; capi_aux.cpp: candidate lists and sketching; capi_pairs.cpp: pair lists).  Not part of the public boundary.
+// drivers; capi_aux.cpp: candidate lists and sketching; capi_pairs.cpp: pair lists; capi_finish.cpp: finishing sketch streams).  Not part of the public boundary.
 // How a dense call and each pair-kernel launch is shaped is decided in dense_plan.hpp (pure, no HIP), reached through kernels.h;
 // the early break's decision in eb_plan.hpp; how the kNN drivers cut and feed their bands in knn_plan.hpp (both pure, no HIP).
 #pragma once
@@ -78,7 +78,9 @@ enum ScratchSlot : int {
     SCRATCH_SKETCH_SIGNS = 13,     // signs,
     SCRATCH_SKETCH_SMALL = 14,     // small arrays
     SCRATCH_COUNTS_2 = 15,         // second counts band (early break of the core/accessory kNN; odd bands of an overlapped dense call)
-    SCRATCH_SLOTS = 16
+    SCRATCH_SKETCH_FINISHED = 16,  // GPU sketching: finished words, first signs and flags on their way to the host,
+    SCRATCH_SKETCH_TARGETS = 17,   // the finish kernel's target arrays (global form)
+    SCRATCH_SLOTS = 18
 };
 
 struct skl_ctx {
@@ -190,3 +192,29 @@ SKL_INTERNAL int fill_args_ref_layout(const skl_sketches *rows, const skl_sketch
 SKL_INTERNAL int dense_band(skl_ctx *ctx, const skl_sketches *rows, const skl_sketches *cols,
                             const skl_dist_params *p, int mode, int jout, int self_mode, uint64_t r0, uint64_t r1,
                             void *dst_dev);
+
+// ---- finishing streams of bin minima on the device (capi_finish.cpp; sketch_finish.hip, finish_plan.hpp) ----
+// where a call's finished streams go on the host: [streams][finish_words(num_bins)], [streams] (may be null), [streams]
+struct FinishDest {
+    uint64_t *usigs, *first_sign;
+    uint8_t *flags;
+};
+// ... and where the kernel leaves them on the device (SCRATCH_SKETCH_FINISHED), with the global form's target arrays
+struct FinishDev {
+    uint64_t *usigs = nullptr, *first_sign = nullptr;
+    uint8_t *flags = nullptr;
+    uint32_t *targets = nullptr;
+};
+SKL_INTERNAL int finish_check_bins(uint64_t num_bins);   // a multiple of 64 that a u32 indexes, or SKL_ERR_INVALID_ARG
+SKL_INTERNAL int finish_reserve(skl_ctx *ctx, uint64_t streams, uint64_t num_bins, FinishDev *dev);
+// streams [0, n_streams) of d_signs into dev's streams [at, at + n_streams), on the context's stream
+SKL_INTERNAL int finish_launch(skl_ctx *ctx, const uint64_t *d_signs, uint64_t n_streams, uint64_t num_bins, const FinishDev &dev, uint64_t at);
+// dev's streams [at, at + n_streams) to dst's [dst_at, ...), queued on `stream`
+SKL_INTERNAL int finish_download(const FinishDev &dev, uint64_t at, uint64_t n_streams, uint64_t num_bins, const FinishDest &dst, uint64_t dst_at,
+                                 hipStream_t stream);
+// once the download has landed: dst's streams [dst_at, dst_at + n_streams) that are flagged FINISH_UNFINISHED are finished on
+// the host from their signs in d_signs (stream s of the range at d_signs + s * num_bins); they keep the flag
+SKL_INTERNAL int finish_fallback(const uint64_t *d_signs, uint64_t n_streams, uint64_t num_bins, const FinishDest &dst, uint64_t dst_at);
+// every stream (or only those flagged FINISH_UNFINISHED) of host signs [n_streams][num_bins] on host threads
+SKL_INTERNAL void finish_on_host(const uint64_t *signs, uint64_t n_streams, uint64_t num_bins, const FinishDest &dst, bool only_unfinished);
+SKL_INTERNAL const char *finish_kernel_name(const skl_ctx *ctx, uint64_t num_bins);   // what skl_ctx_last_kernel() says of the finish

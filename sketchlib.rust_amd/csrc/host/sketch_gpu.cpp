@@ -1,7 +1,8 @@
-// sketch_gpu.cpp -- `sketchlib sketch --gpu`: FASTA / FASTQ parsing on host threads, hashing and bin
-// minima on the device (skl_sketch_signs), densify / transpose / file writers on the host.  Read sets
+// sketch_gpu.cpp -- `sketchlib sketch --gpu`: FASTA / FASTQ parsing on host threads; hashing, bin minima,
+// densification and the 14-plane transpose on the device (skl_sketch_usigs_packed), whose words
+// land in the `.skd` image as they come back; file writers on the host.  Read sets
 // with a count filter (min_count >= 2) hash on the device too (skl_reads_survivors), in chunks of window
-// starts, and the host replays the survivors through the filter.
+// starts, and the host replays the survivors through the filter and finishes their signs itself.
 #include <algorithm>
 #include <atomic>
 #include <chrono>
@@ -198,9 +199,10 @@ void reads_signs_gpu(Device &dev, const std::vector<Sequence> &seqs, const std::
 
 namespace {
 // `sketch --gpu --seq-type aa`: protein FASTA parsed into residue codes on host threads (load_aa_samples), aaHash and bin
-// minima on the device (skl_sketch_signs_aa), densify / transpose / writers on the host.  One call takes
-// samples up to 1 Gi residues and 1 GiB of signs -- at 1 024 bins and one k-mer length a protein's signs are 8 KiB, so a
-// million proteins come back in eight calls -- and the library cuts a call into device batches of 256 MiB of signs.
+// minima on the device and densify / transpose behind them (skl_sketch_usigs_aa, §4.7): the finished words
+// come back straight into the `.skd` image, 1 792 B per protein and k-mer length at 1 024 bins.  One call takes samples up to
+// 1 Gi residues and 1 GiB of signs ON THE DEVICE -- at 1 024 bins and one k-mer length a protein's signs are 8 KiB, so a
+// million proteins take eight calls -- and the library cuts a call into device batches of 256 MiB of signs.
 MultiSketch sketch_files_gpu_aa(Device &dev, const std::string &output_prefix, const std::vector<InputFastx> &inputs,
                                 const std::vector<size_t> &kmers, uint64_t sketch_size, bool rc, size_t threads, const SeqType &st)
 {
@@ -238,8 +240,7 @@ MultiSketch sketch_files_gpu_aa(Device &dev, const std::string &output_prefix, c
     std::vector<std::string> sample_error(n);
     constexpr uint64_t CALL_RESIDUES = 1ull << 30, CALL_SIGN_BYTES = 1ull << 30;
     const uint64_t sign_bytes = (uint64_t)nk * num_bins * sizeof(uint64_t);
-    std::unique_ptr<uint64_t[]> signs;
-    size_t signs_room = 0;
+    std::vector<uint8_t> flags;
     for (size_t b0 = 0; b0 < n;) {
         size_t b1 = b0;
         uint64_t residues_in_call = 0;
@@ -256,34 +257,30 @@ MultiSketch sketch_files_gpu_aa(Device &dev, const std::string &output_prefix, c
             const auto &c = samples[b0 + i].codes;
             if (!c.empty()) memcpy(residues.get() + res_begin[i], c.data(), c.size());
         });
-        if (signs_room < nb * nk * num_bins) {   // (not zero-filled: the library writes every word; the first call is the largest but for a long sample later on)
-            signs_room = nb * nk * num_bins;
-            signs.reset(new uint64_t[signs_room]);
-        }
+        flags.assign(nb * nk, 0);
         const double t0 = since();
-        if (skl_sketch_signs_aa(dev.ctx(), residues.get(), res_begin.data(), nb, kmers.data(), nk, num_bins, st.level,
-                                st.concat_fasta ? 1 : 0, signs.get()) != SKL_OK) {
+        // the finished words of samples [b0, b1) are exactly their part of the `.skd` image
+        if (skl_sketch_usigs_aa(dev.ctx(), residues.get(), res_begin.data(), nb, kmers.data(), nk, num_bins, st.level,
+                                st.concat_fasta ? 1 : 0, bins.data() + b0 * sample_words, nullptr, flags.data()) != SKL_OK) {
             throw std::runtime_error(skl_last_error());
         }
         const double t1 = since();
         t_gpu += t1 - t0;
-        parallel_for(nb, threads, [&](size_t i) {
+        for (size_t i = 0; i < nb; ++i) {
             const size_t at = b0 + i;
             const AaSample &a = samples[at];
             if (a.codes.empty()) {
                 sample_error[at] = a.name + " has no valid sequence";
-                return;
+                continue;
             }
-            bool densified = false;
+            bool densified = false, empty = false;
             for (size_t ki = 0; ki < nk; ++ki) {
-                const uint64_t *src = signs.get() + (i * nk + ki) * num_bins;
-                std::vector<uint64_t> sg(src, src + num_bins);
-                if (std::all_of(sg.begin(), sg.end(), [](uint64_t v) { return v == UINT64_MAX; })) {
-                    sample_error[at] = "K-mer larger than smallest valid sequence";   // as the CPU path
-                    return;
-                }
-                densified |= densify_bin(sg);
-                fill_usigs(bins.data() + at * sample_words + ki * ss64 * BBITS, sg);
+                densified |= (flags[i * nk + ki] & SKL_FINISH_DENSIFIED) != 0;
+                empty |= (flags[i * nk + ki] & SKL_FINISH_EMPTY) != 0;
+            }
+            if (empty) {
+                sample_error[at] = "K-mer larger than smallest valid sequence";   // as the CPU path
+                continue;
             }
             SketchMeta &m = meta[at];
             m.name = a.name;
@@ -293,7 +290,7 @@ MultiSketch sketch_files_gpu_aa(Device &dev, const std::string &output_prefix, c
             m.densified = densified;
             m.non_acgt = a.invalid;
             m.index = at;
-        });
+        }
         for (size_t at = b0; at < b1; ++at) {   // the first sample in input order that fails, as the CPU path on one thread
             if (!sample_error[at].empty()) throw std::runtime_error(sample_error[at]);
             std::vector<uint8_t>().swap(samples[at].codes);
@@ -361,7 +358,8 @@ MultiSketch sketch_files_gpu(Device &dev, const std::string &output_prefix, cons
     t_parse = since();
     std::vector<uint64_t> bins(sample_words * n, 0);
     std::vector<SketchMeta> meta(n);
-    // densify + transpose + metadata of sample `at` from its [nk][num_bins] signs (host threads)
+    // densify + transpose + metadata of sample `at` from its [nk][num_bins] signs on host threads: read sets under a count
+    // filter, whose signs are produced on the host
     std::string finish_error;
     std::mutex finish_mu;
     auto finish = [&](size_t at, const uint64_t *sample_signs, const char *any_window) {
@@ -397,11 +395,12 @@ MultiSketch sketch_files_gpu(Device &dev, const std::string &output_prefix, cons
             if (finish_error.empty()) finish_error = e.what();
         }
     };
-    // read sets under a count filter go their own way; assemblies (and read sets without one) take the bin-minimum kernel
+    // read sets under a count filter go their own way; assemblies (and read sets without one) take the bin-minimum kernel and
+    // the finish kernel behind it
     std::vector<size_t> plain, filtered;
     for (size_t i = 0; i < n; ++i) (seqs[i].reads && min_count >= 2 ? filtered : plain).push_back(i);
 
-    // 2. hash + bin minima on the device, in batches of at most ~4 G bases
+    // 2. hash + bin minima + densify + transpose on the device, in batches of at most ~4 G bases
     constexpr uint64_t BATCH_CODES = 4ull << 30;
     for (size_t b0 = 0; b0 < plain.size();) {
         size_t b1 = b0;
@@ -423,16 +422,40 @@ MultiSketch sketch_files_gpu(Device &dev, const std::string &output_prefix, cons
         }
         std::unique_ptr<uint32_t[]> packed(new uint32_t[std::max<uint64_t>(word_begin[nb], 1)]);   // not zero-filled
         parallel_for(nb, threads, [&](size_t i) { pack_codes(seqs[plain[b0 + i]].codes, packed.get() + word_begin[i]); });
-        std::vector<uint64_t> signs(nb * nk * num_bins);
+        // Hash, bin minima, densify and transpose on the device.  A batch's finished words are its samples' part of the `.skd`
+        // image when the samples are consecutive in input order (always, unless read sets under a count filter lie between them).
+        const bool in_place = plain[b1 - 1] - plain[b0] == nb - 1;
+        std::vector<uint64_t> staged_words(in_place ? 0 : nb * sample_words), first_signs(nb * nk);
+        std::vector<uint8_t> flags(nb * nk, 0);
+        uint64_t *words = in_place ? bins.data() + plain[b0] * sample_words : staged_words.data();
         const double t0 = since();
         t_pack += t0 - (t_parse + t_pack + t_gpu + t_finish);
-        const int rc_ = skl_sketch_signs_packed(dev.ctx(), packed.get(), code_begin.data(), offsets.data(), offset_begin.data(),
-                                                nb, kmers.data(), nk, num_bins, rc ? 1 : 0, signs.data());
+        const int rc_ = skl_sketch_usigs_packed(dev.ctx(), packed.get(), code_begin.data(), offsets.data(), offset_begin.data(),
+                                                nb, kmers.data(), nk, num_bins, rc ? 1 : 0, words, first_signs.data(), flags.data());
         if (rc_ != SKL_OK) throw std::runtime_error(skl_last_error());
         t_gpu += since() - t0;
-        // 3. densify + transpose (host threads)
-        parallel_for(nb, threads, [&](size_t i) { finish(plain[b0 + i], signs.data() + i * nk * num_bins, nullptr); });
-        if (!finish_error.empty()) throw std::runtime_error(finish_error);
+        // 3. metadata from the flags and first signs
+        for (size_t i = 0; i < nb; ++i) {
+            const size_t at = plain[b0 + i];
+            const Sequence &s = seqs[at];
+            bool densified = false;
+            for (size_t ki = 0; ki < nk; ++ki) {
+                if (flags[i * nk + ki] & SKL_FINISH_EMPTY) throw std::runtime_error("K-mer larger than smallest valid sequence");   // as the CPU path: the first such sample in input order
+                densified |= (flags[i * nk + ki] & SKL_FINISH_DENSIFIED) != 0;
+            }
+            if (!in_place) memcpy(bins.data() + at * sample_words, words + i * sample_words, sample_words * sizeof(uint64_t));
+            SketchMeta &m = meta[at];
+            m.name = inputs[at].first;
+            m.rc = rc;
+            m.reads = s.reads;
+            uint64_t total = 0;
+            for (uint64_t c : s.acgt) total += c;
+            m.seq_length = s.reads ? reads_seq_length(std::vector<uint64_t>(first_signs.begin() + i * nk, first_signs.begin() + (i + 1) * nk)) : total;
+            m.densified = densified;
+            for (int x = 0; x < 4; ++x) m.acgt[x] = s.acgt[x];
+            m.non_acgt = s.non_acgt;
+            m.index = at;
+        }
         for (size_t i = b0; i < b1; ++i) Sequence().codes.swap(seqs[plain[i]].codes);   // release
         b0 = b1;
         t_finish = since() - t_parse - t_pack - t_gpu;

@@ -11,6 +11,7 @@
 
 #include "dense_plan.hpp"   // slice_plan()
 #include "aa_plan.hpp"      // the amino-acid sketching call's work plan and locators
+#include "finish_plan.hpp"  // device-side densify + transpose: launch rules, flag bits, the shared target rule
 #include "work_map.hpp"     // which workgroup computes what: TILE_PREFIX_INLINE, the fields below it reads and plans
 
 namespace skl {
@@ -400,6 +401,20 @@ struct AaSketchArgs {
     uint64_t *signs;               // [batch samples][nk][num_bins], pre-set to UINT64_MAX
 };
 hipError_t launch_aa_sketch_signs(const AaSketchArgs &args, hipStream_t stream);
+
+// Finishing streams of bin minima on the device (sketch_finish.hip, finish_plan.hpp): densify_bin and the 14-plane transpose of
+// fill_usigs, a workgroup per (sample, k) stream.
+struct FinishArgs {
+    const uint64_t *signs;         // [n_streams][num_bins] bin minima, u64::MAX for an empty bin
+    uint64_t n_streams;
+    uint32_t num_bins;             // a multiple of 64
+    uint32_t max_attempts;         // probe cap per bin (finish_max_attempts)
+    uint64_t *usigs;               // [n_streams][finish_words(num_bins)]
+    uint64_t *first_sign;          // [n_streams] the densified signs[0], all 64 bits
+    uint8_t *flags;                // [n_streams] FINISH_DENSIFIED | FINISH_ALL_EMPTY | FINISH_UNFINISHED
+    uint32_t *targets;             // global form: [finish_workgroups()][num_bins] scratch; LDS form: unused
+};
+hipError_t launch_sketch_finish(const FinishArgs &args, hipStream_t stream);
 
 // Survivors of the read sketcher's count filter (read_survivors.hip, skl_reads_survivors): every valid window
 // of every (sample, k) stream in a range of window starts whose sign is below its bin's threshold.

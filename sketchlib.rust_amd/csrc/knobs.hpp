@@ -3,8 +3,8 @@
 #pragma once
 
 // Environment switches.  They are read ONCE, when a context is created (skl_ctx_create), never on
-// the launch path.  The product library READS thirteen of them (capi.cpp read_knobs: timing cadence, topology,
-// the knobs that force the banded / sliced / 32-row forms on small test inputs, the inverted query's band budget, the sketching calls' batch sizes and form threshold, the pair list's band); every "A/B only, results
+// the launch path.  The product library READS fifteen of them (capi.cpp read_knobs: timing cadence, topology,
+// the knobs that force the banded / sliced / 32-row forms on small test inputs, the inverted query's band budget, the sketching calls' batch sizes and form threshold, where and how far their streams are finished, the pair list's band); every "A/B only, results
 // identical" switch below keeps its default there and is read by the A/B build alone (-DSKL_AB), as are kernel
 // selection, tile shapes and the timing-only ablations.
 struct Knobs {
@@ -15,6 +15,8 @@ struct Knobs {
     long long sketch_batch_words = 0; // SKL_SKETCH_BATCH_WORDS: packed words (16 bases each) from which skl_sketch_signs closes an upload batch of whole samples (0: 8 Mi; tests force it low)
     long long aa_batch_sign_bytes = 0; // SKL_AA_BATCH_SIGN_BYTES: bytes of signs from which skl_sketch_signs_aa closes a batch of whole samples (0: 256 MiB; tests force it low)
     long long aa_long_min = 0;        // SKL_AA_LONG_MIN: residues from which a sample takes the staged form of skl_sketch_signs_aa (0: 8 192; tests force 1: every sample staged)
+    long long finish_max_attempts = 0; // SKL_FINISH_MAX_ATTEMPTS: probe cap per bin of the device-side densification (0: 2 048, finish_plan.hpp; tests force it low: capped streams are finished by the host)
+    bool sketch_finish_host = false;  // SKL_SKETCH_FINISH=host: skl_sketch_finish / skl_sketch_usigs_* download the signs and densify + transpose on host threads (A/B timing, escape hatch; the same bytes)
     long long pairs_band = 0;         // SKL_PAIRS_BAND: listed pairs per upload band of skl_*_dists_pairs (0: 64 Mi; tests force it low)
     int k_slices = 0;                 // SKL_K_SLICES: chunk slices per k of k-sliced core/acc launches (0: chosen per launch)
     int xcds = 0;                       // SKL_XCDS: XCDs the tile order assumes (0: from the device's CU count: 256 CUs = 8, a 32-CU partition = 1)
