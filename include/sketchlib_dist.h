@@ -435,6 +435,21 @@ int skl_sketch_usigs_packed(skl_ctx *ctx, const uint32_t *packed, const uint64_t
                             const uint64_t *offsets, const uint64_t *offset_begin, size_t n_samples,
                             const size_t *kmers, size_t nk, uint64_t num_bins, int rc, uint64_t *out_usigs,
                             uint64_t *out_first_sign, uint8_t *out_flags);
+/* The u16 form of skl_sketch_finish, an inverted index's rows (`.skq`): densify_bin, then `sign as u16` per bin, for ANY
+ * num_bins from 1 to 2^32 - 1 (an index has exactly sketch_size bins: 10, 1 000, ...).  The same kernel with another emit:
+ * emptiness is decided on all 64 bits (a valid sign whose low 16 bits are 0xFFFF is not empty) and the resolve runs on
+ * indices.  out_bins: [n_streams][num_bins]; out_flags as skl_sketch_finish (an all-empty stream: a zeroed row and
+ * SKL_FINISH_EMPTY; a stream past the probe cap: finished on the host, the same bytes, SKL_FINISH_UNFINISHED set).
+ * Batches, SKL_SKETCH_FINISH=host and SKL_FINISH_MAX_ATTEMPTS as there.  Host pointers. */
+int skl_sketch_finish_u16(skl_ctx *ctx, const uint64_t *signs, size_t n_streams, uint64_t num_bins, uint16_t *out_bins,
+                          uint8_t *out_flags);
+/* skl_sketch_signs_packed at ONE k-mer length with the u16 finish behind each batch's bin-minimum launch, on the same
+ * stream: 2 * num_bins bytes and a flag byte come home per sample instead of 8 * num_bins.  out_bins: [n_samples][num_bins];
+ * out_flags: [n_samples].  A sample without a valid k-mer comes back SKL_FINISH_EMPTY (a zeroed row); the error is the
+ * caller's to raise. */
+int skl_sketch_bins_u16_packed(skl_ctx *ctx, const uint32_t *packed, const uint64_t *code_begin,
+                               const uint64_t *offsets, const uint64_t *offset_begin, size_t n_samples,
+                               size_t kmer, uint64_t num_bins, int rc, uint16_t *out_bins, uint8_t *out_flags);
 /* skl_sketch_signs_aa with every stream finished on the device, batch by batch as that call cuts them; outputs as
  * skl_sketch_usigs_packed. */
 int skl_sketch_usigs_aa(skl_ctx *ctx, const uint8_t *residues, const uint64_t *res_begin, size_t n_samples,

@@ -121,6 +121,8 @@ _SIG = [
     ("skl_sketch_aa_shape", C.c_int, [C.c_int, C.c_size_t]),
     ("skl_sketch_finish", C.c_int, [_P, _P, C.c_size_t, C.c_uint64, _P, _P, _P]),
     ("skl_sketch_usigs_packed", C.c_int, [_P, _P, _P, _P, _P, C.c_size_t, _P, C.c_size_t, C.c_uint64, C.c_int, _P, _P, _P]),
+    ("skl_sketch_finish_u16", C.c_int, [_P, _P, C.c_size_t, C.c_uint64, _P, _P]),
+    ("skl_sketch_bins_u16_packed", C.c_int, [_P, _P, _P, _P, _P, C.c_size_t, C.c_size_t, C.c_uint64, C.c_int, _P, _P]),
     ("skl_sketch_usigs_aa", C.c_int, [_P, _P, _P, C.c_size_t, _P, C.c_size_t, C.c_uint64, C.c_int, C.c_int, _P, _P, _P]),
     ("skl_reads_create", C.c_int, [_P, _P, _P, _P, _P, C.c_size_t, _P, C.c_size_t, C.c_uint64, C.c_int, C.POINTER(_P)]),
     ("skl_reads_survivors", C.c_int, [_P, _P, _P, _P, C.c_uint64, _P, _P]),
@@ -810,6 +812,35 @@ def sketch_usigs_packed(ctx, packed, code_begin, offsets, offset_begin, kmers, n
                                           kmers.ctypes.data, kmers.size, num_bins, int(rc), usigs.ctypes.data, first.ctypes.data,
                                           flags.ctypes.data))
     return usigs, first, flags
+
+
+def sketch_finish_u16(ctx, signs, num_bins=None):
+    """skl_sketch_finish_u16: densify_bin + `sign as u16` of [..., num_bins] uint64 bin minima on the device, any num_bins ->
+    (bins [..., num_bins] uint16, flags [...] uint8: FINISH_* bits)."""
+    signs = np.ascontiguousarray(signs, dtype=np.uint64)
+    num_bins = signs.shape[-1] if num_bins is None else int(num_bins)
+    lead = signs.shape[:-1]
+    n = int(np.prod(lead, dtype=np.int64))
+    bins = np.zeros(lead + (num_bins,), dtype=np.uint16)
+    flags = np.zeros(lead, dtype=np.uint8)
+    _check(load().skl_sketch_finish_u16(ctx._h, signs.ctypes.data, n, num_bins, bins.ctypes.data, flags.ctypes.data))
+    return bins, flags
+
+
+def sketch_bins_u16_packed(ctx, packed, code_begin, offsets, offset_begin, kmer, num_bins, rc=True):
+    """skl_sketch_bins_u16_packed: sketch_signs_packed at one k-mer length with the u16 finish behind it ->
+    (bins [n, num_bins] uint16, flags [n] uint8) as sketch_finish_u16."""
+    packed = np.ascontiguousarray(packed, dtype=np.uint32)
+    code_begin = np.ascontiguousarray(code_begin, dtype=np.uint64)
+    offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+    offset_begin = np.ascontiguousarray(offset_begin, dtype=np.uint64)
+    n = code_begin.size - 1
+    bins = np.zeros((n, num_bins), dtype=np.uint16)
+    flags = np.zeros(n, dtype=np.uint8)
+    _check(load().skl_sketch_bins_u16_packed(ctx._h, packed.ctypes.data if packed.size else None, code_begin.ctypes.data,
+                                             offsets.ctypes.data if offsets.size else None, offset_begin.ctypes.data, n,
+                                             int(kmer), num_bins, int(rc), bins.ctypes.data, flags.ctypes.data))
+    return bins, flags
 
 
 def sketch_usigs_aa(ctx, residues, res_begin, kmers, num_bins, level=1, concat_end_rule=False):

@@ -138,7 +138,7 @@ static int sketch_signs_impl(skl_ctx *ctx, const uint8_t *codes, const uint32_t 
     const size_t small_words = 4 * (n_samples + 1) + n_offs + 9 * nk + 8;   // u64 each (the k-mer lengths: two per word)
     SKL_TRY(ctx_scratch(ctx, small_words * sizeof(uint64_t), &d_small, SCRATCH_SKETCH_SMALL));
     FinishDev fin_dev;
-    if (fin) SKL_TRY(finish_reserve(ctx, n_samples * nk, num_bins, &fin_dev));
+    if (fin) SKL_TRY(finish_reserve(ctx, n_samples * nk, num_bins, &fin_dev, fin->bins_u16 != nullptr));
     std::vector<uint64_t> small;
     small.reserve(small_words);
     auto put = [&](const uint64_t *v, size_t count) {
@@ -270,7 +270,7 @@ static int sketch_signs_impl(skl_ctx *ctx, const uint8_t *codes, const uint32_t 
     HIP_TRY(hipStreamSynchronize(ctx->aux_stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     if (fin) {   // (the call's signs are all still on the device)
-        ctx->last_kernel += std::string(" + ") + finish_kernel_name(ctx, num_bins);
+        ctx->last_kernel += std::string(" + ") + finish_kernel_name(ctx, num_bins, fin->bins_u16 != nullptr);
         SKL_TRY(finish_fallback((const uint64_t *)d_signs, n_samples * nk, num_bins, *fin, 0));
     }
     // The sketching buffers belong to the context so that a run of sketch calls does not allocate per call -- but beyond 1 GiB
@@ -325,6 +325,27 @@ extern "C" int skl_sketch_usigs_packed(skl_ctx *ctx, const uint32_t *packed, con
     SKL_TRY(sketch_signs_impl(ctx, nullptr, packed, code_begin, offsets, offset_begin, n_samples, kmers, nk, num_bins, rc, signs.get()));
     finish_on_host(signs.get(), n_samples * nk, num_bins, dst, false);
     ctx->last_kernel += std::string(" + ") + finish_kernel_name(ctx, num_bins);
+    return SKL_OK;
+}
+
+// An inverted index's rows: one k-mer length, exactly num_bins bins (any count), the u16 finish behind each batch's bin
+// minima on the same stream -- 2 num_bins bytes and a flag byte come home per sample.
+extern "C" int skl_sketch_bins_u16_packed(skl_ctx *ctx, const uint32_t *packed, const uint64_t *code_begin,
+                                          const uint64_t *offsets, const uint64_t *offset_begin, size_t n_samples,
+                                          size_t kmer, uint64_t num_bins, int rc, uint16_t *out_bins, uint8_t *out_flags)
+{
+    SKL_TRY(ctx_bind(ctx));
+    if (!out_bins || !out_flags) return fail(SKL_ERR_INVALID_ARG, "null argument");
+    if (!packed && code_begin && n_samples && code_begin[n_samples]) return fail(SKL_ERR_INVALID_ARG, "null argument");
+    SKL_TRY(finish_check_bins_u16(num_bins));
+    const FinishDest dst{nullptr, nullptr, out_flags, out_bins};
+    if (!ctx->knobs.sketch_finish_host) {
+        return sketch_signs_impl(ctx, nullptr, packed, code_begin, offsets, offset_begin, n_samples, &kmer, 1, num_bins, rc, nullptr, &dst);
+    }
+    std::unique_ptr<uint64_t[]> signs(new uint64_t[std::max<size_t>(n_samples * num_bins, 1)]);   // (not zero-filled: the call writes every word)
+    SKL_TRY(sketch_signs_impl(ctx, nullptr, packed, code_begin, offsets, offset_begin, n_samples, &kmer, 1, num_bins, rc, signs.get()));
+    finish_on_host(signs.get(), n_samples, num_bins, dst, false);
+    ctx->last_kernel += std::string(" + ") + finish_kernel_name(ctx, num_bins, true);
     return SKL_OK;
 }
 

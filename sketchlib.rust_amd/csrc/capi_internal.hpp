@@ -194,19 +194,23 @@ SKL_INTERNAL int dense_band(skl_ctx *ctx, const skl_sketches *rows, const skl_sk
                             void *dst_dev);
 
 // ---- finishing streams of bin minima on the device (capi_finish.cpp; sketch_finish.hip, finish_plan.hpp) ----
-// where a call's finished streams go on the host: [streams][finish_words(num_bins)], [streams] (may be null), [streams]
+// where a call's finished streams go on the host: [streams][finish_words(num_bins)], [streams] (may be null), [streams];
+// bins_u16 set: the u16 form instead -- rows [streams][num_bins] and the flags, usigs / first_sign unused
 struct FinishDest {
     uint64_t *usigs, *first_sign;
     uint8_t *flags;
+    uint16_t *bins_u16 = nullptr;
 };
 // ... and where the kernel leaves them on the device (SCRATCH_SKETCH_FINISHED), with the global form's target arrays
 struct FinishDev {
     uint64_t *usigs = nullptr, *first_sign = nullptr;
     uint8_t *flags = nullptr;
     uint32_t *targets = nullptr;
+    uint16_t *bins_u16 = nullptr;   // u16 form: the rows (usigs / first_sign null)
 };
 SKL_INTERNAL int finish_check_bins(uint64_t num_bins);   // a multiple of 64 that a u32 indexes, or SKL_ERR_INVALID_ARG
-SKL_INTERNAL int finish_reserve(skl_ctx *ctx, uint64_t streams, uint64_t num_bins, FinishDev *dev);
+SKL_INTERNAL int finish_check_bins_u16(uint64_t num_bins);   // the u16 form: 1 to 2^32 - 1
+SKL_INTERNAL int finish_reserve(skl_ctx *ctx, uint64_t streams, uint64_t num_bins, FinishDev *dev, bool u16 = false);
 // streams [0, n_streams) of d_signs into dev's streams [at, at + n_streams), on the context's stream
 SKL_INTERNAL int finish_launch(skl_ctx *ctx, const uint64_t *d_signs, uint64_t n_streams, uint64_t num_bins, const FinishDev &dev, uint64_t at);
 // dev's streams [at, at + n_streams) to dst's [dst_at, ...), queued on `stream`
@@ -217,4 +221,4 @@ SKL_INTERNAL int finish_download(const FinishDev &dev, uint64_t at, uint64_t n_s
 SKL_INTERNAL int finish_fallback(const uint64_t *d_signs, uint64_t n_streams, uint64_t num_bins, const FinishDest &dst, uint64_t dst_at);
 // every stream (or only those flagged FINISH_UNFINISHED) of host signs [n_streams][num_bins] on host threads
 SKL_INTERNAL void finish_on_host(const uint64_t *signs, uint64_t n_streams, uint64_t num_bins, const FinishDest &dst, bool only_unfinished);
-SKL_INTERNAL const char *finish_kernel_name(const skl_ctx *ctx, uint64_t num_bins);   // what skl_ctx_last_kernel() says of the finish
+SKL_INTERNAL const char *finish_kernel_name(const skl_ctx *ctx, uint64_t num_bins, bool u16 = false);   // what skl_ctx_last_kernel() says of the finish

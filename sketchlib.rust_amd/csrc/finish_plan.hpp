@@ -73,6 +73,23 @@ inline uint64_t finish_workgroups(uint64_t n_streams, uint64_t num_bins)
 inline uint64_t finish_lds_bytes(uint64_t num_bins) { return finish_lds_form(num_bins) ? num_bins * sizeof(uint32_t) + num_bins / 8 : 0; }
 inline uint64_t finish_words(uint64_t num_bins) { return num_bins / 64 * FINISH_PLANES; }   // u64 words of a finished stream
 
+// The u16 form (an inverted index's row: exactly num_bins bins, `sign as u16` each) takes any num_bins from 1 to 2^32 - 1.
+// Its workgroups are WHOLE WAVES: the kernel strides its chunk loops by n_waves = blockDim.x >> 6, and a workgroup of fewer
+// than 64 threads (finish_threads(10) would be 10) has n_waves == 0 -- a `c += n_waves` loop would never end.  Rounding up to
+// 64 makes that impossible: the result is a multiple of 64 and at least 64 for every num_bins >= 1.  At multiples of 64 the
+// values are finish_threads' / finish_lds_bytes'.
+inline uint32_t finish_threads_u16(uint64_t num_bins)
+{
+    if (!finish_lds_form(num_bins)) return FINISH_WG_GLOBAL;
+    const uint64_t whole_waves = (num_bins + 63) / 64 * 64;
+    return (uint32_t)(whole_waves < FINISH_WG_LDS ? (whole_waves ? whole_waves : 64) : FINISH_WG_LDS);
+}
+// targets [num_bins] u32, then the "holds a value" bits, a u32 per 32 bins (the last one partly used)
+inline uint64_t finish_lds_bytes_u16(uint64_t num_bins)
+{
+    return finish_lds_form(num_bins) ? num_bins * sizeof(uint32_t) + (num_bins + 31) / 32 * sizeof(uint32_t) : 0;
+}
+
 // sketch/mod.rs:225-231, in wrapping u64
 SKL_FINISH_HD inline uint64_t finish_universal_hash(uint64_t s, uint64_t t)
 {
@@ -151,6 +168,16 @@ inline uint8_t finish_stream_host(const uint64_t *signs, uint64_t num_bins, uint
         finish_transpose(sg, usigs);
     }
     if (first_sign) *first_sign = sg[0];
+    return flag;
+}
+
+// One stream on the host in the u16 form, as the kernel leaves it: densified, `sign as u16` per bin (any num_bins); returns
+// the flag.  An all-empty stream gives a zeroed row.
+inline uint8_t finish_stream_host_u16(const uint64_t *signs, uint64_t num_bins, uint16_t *out_u16)
+{
+    std::vector<uint64_t> sg(signs, signs + num_bins);
+    const uint8_t flag = finish_densify_two_step(sg);
+    for (uint64_t i = 0; i < num_bins; ++i) out_u16[i] = (flag & FINISH_ALL_EMPTY) ? (uint16_t)0 : (uint16_t)sg[i];
     return flag;
 }
 

@@ -613,8 +613,9 @@ int run_sketch(int argc, char **argv, int first, bool verbose, bool quiet)
 }
 
 // ---- `sketchlib inverted query` (src/cli.rs:380-412, src/lib.rs:605-680) ----
-// Queries are sketched on host threads the way the index was built (Inverted::sketch_queries, inverted.rs:118-140),
-// then matched against every indexed sample on the GPU (skl_inverted_query, csrc/inv_query.hip), one band of
+// Queries (assemblies or read sets, --min-count / --min-qual as in `sketch`) are sketched the way the index was built
+// (Inverted::sketch_queries, inverted.rs:118-140) -- on host threads, or with --gpu on the device --device names
+// (sketch_inverted_gpu) -- then matched against every indexed sample on the GPU (skl_inverted_query, csrc/inv_query.hip), one band of
 // queries at a time: band i + 1 computes while band i is formatted on --threads threads and written.  Rows come in
 // input order (the reference's come in whatever order its threads finish).
 int run_inverted_query(int argc, char **argv, int first, bool verbose, bool quiet)
@@ -626,6 +627,9 @@ int run_inverted_query(int argc, char **argv, int first, bool verbose, bool quie
     std::string mode_name = "match-count";
     size_t threads = 1;
     int device = 0;
+    bool gpu_sketch = false;
+    uint16_t min_count = 5;   // DEFAULT_MINCOUNT / DEFAULT_MINQUAL, cli.rs:12-15 (read sets only)
+    uint8_t min_qual = 20;
     for (int i = first; i < argc; ++i) {
         const std::string arg = argv[i];
         auto value = [&](const std::string &flag) -> std::string {
@@ -644,7 +648,9 @@ int run_inverted_query(int argc, char **argv, int first, bool verbose, bool quie
             else usage_error("invalid value '" + mode_name + "' for '--query-type <QUERY_TYPE>'\n  [possible values: match-count, all-bins, any-bins]");
         }
         else if (arg == "--threads") threads = std::max<size_t>(1, parse_usize("--threads <THREADS>", value(arg)));
-        else if (arg == "--min-count" || arg == "--min-qual") (void)value(arg);   // reads input only (out of scope)
+        else if (arg == "--min-count") min_count = (uint16_t)parse_bounded("--min-count <MIN_COUNT>", value(arg), 0xFFFF);
+        else if (arg == "--min-qual") min_qual = (uint8_t)parse_bounded("--min-qual <MIN_QUAL>", value(arg), 0xFF);
+        else if (arg == "--gpu") gpu_sketch = true;   // sketch the queries on the device too (the one --device names)
         else if (arg == "--device") device = (int)parse_usize("--device <D>", value(arg));
         else if (arg.size() > 1 && arg[0] == '-') usage_error("unexpected argument '" + arg + "' found");
         else if (!ski) ski = arg;
@@ -680,8 +686,15 @@ int run_inverted_query(int argc, char **argv, int first, bool verbose, bool quie
     log.info("Sketching input queries");
     const size_t nq = inputs.size();
     std::vector<uint16_t> query_bins(nq * S);
+    std::unique_ptr<Device> dev_owner;
     try {
-        std::atomic<size_t> next{0};
+        if (gpu_sketch) {
+            dev_owner = dev_starting.get();   // ("no CPU path" without a device: no fallback to the host loop)
+            const std::vector<std::vector<uint16_t>> rows =
+                sketch_inverted_gpu(*dev_owner, inputs, inv.kmer_size, S, inv.rc, threads, min_count, min_qual);
+            for (size_t i = 0; i < nq; ++i) std::copy(rows[i].begin(), rows[i].end(), query_bins.begin() + i * S);
+        }
+        std::atomic<size_t> next{gpu_sketch ? nq : 0};   // (nothing left for the host loop then)
         std::exception_ptr err;
         std::mutex mu;
         auto work = [&] {
@@ -689,7 +702,7 @@ int run_inverted_query(int argc, char **argv, int first, bool verbose, bool quie
                 for (;;) {
                     const size_t i = next.fetch_add(1);
                     if (i >= nq) break;
-                    const std::vector<uint16_t> q = sketch_sample_inverted(inputs[i], inv.kmer_size, S, inv.rc);
+                    const std::vector<uint16_t> q = sketch_sample_inverted(inputs[i], inv.kmer_size, S, inv.rc, min_count, min_qual);
                     std::copy(q.begin(), q.end(), query_bins.begin() + i * S);
                 }
             } catch (...) {
@@ -721,7 +734,7 @@ int run_inverted_query(int argc, char **argv, int first, bool verbose, bool quie
         if (!text.empty()) sink->finish(sink->begin(text.data(), text.size()), text.data(), text.size());
     };
 
-    const std::unique_ptr<Device> dev_owner = dev_starting.get();
+    if (!dev_owner) dev_owner = dev_starting.get();
     Device &dev = *dev_owner;
     skl_inverted *ix = nullptr;
     if (skl_inverted_create(dev.ctx(), index_bins.data(), n, S, &ix) != SKL_OK) throw std::runtime_error(skl_last_error());
@@ -823,6 +836,9 @@ int run_inverted(int argc, char **argv, int first, bool verbose, bool quiet)
         bool write_skq_flag = false, single_strand = false;
         uint64_t sketch_size = 1000;   // DEFAULT_SKETCHSIZE, cli.rs:17
         size_t kmer = 21, threads = 1; // DEFAULT_KMER, cli.rs:13
+        int gpu = -1;                  // --gpu / --device D: sketch on that device (sketch_inverted_gpu)
+        uint16_t min_count = 5;        // DEFAULT_MINCOUNT / DEFAULT_MINQUAL, cli.rs:12-15 (read sets only)
+        uint8_t min_qual = 20;
         for (int i = first + 1; i < argc; ++i) {
             const std::string arg = argv[i];
             if (arg == "-v" || arg == "--verbose") verbose = true;
@@ -836,7 +852,10 @@ int run_inverted(int argc, char **argv, int first, bool verbose, bool quiet)
             else if (arg == "-k" || arg == "--kmer-length") kmer = parse_usize("--kmer-length <KMER_LENGTH>", next_value(i, arg));
             else if (arg == "--single-strand") single_strand = true;
             else if (arg == "--threads") threads = std::max<size_t>(1, parse_usize("--threads <THREADS>", next_value(i, arg)));
-            else if (arg == "--min-count" || arg == "--min-qual") (void)next_value(i, arg);
+            else if (arg == "--min-count") min_count = (uint16_t)parse_bounded("--min-count <MIN_COUNT>", next_value(i, arg), 0xFFFF);
+            else if (arg == "--min-qual") min_qual = (uint8_t)parse_bounded("--min-qual <MIN_QUAL>", next_value(i, arg), 0xFF);
+            else if (arg == "--gpu") gpu = 0;
+            else if (arg == "--device") gpu = (int)parse_usize("--device <D>", next_value(i, arg));
             else if (arg.size() > 1 && arg[0] == '-') usage_error("unexpected argument '" + arg + "' found");
             else seq_files.push_back(arg);
         }
@@ -857,6 +876,10 @@ int run_inverted(int argc, char **argv, int first, bool verbose, bool quiet)
                 return 2;
             }
         }
+        const bool timing = std::getenv("SKL_CLI_TIMING") != nullptr;
+        const auto t_start = std::chrono::steady_clock::now();
+        auto since_start = [&] { return std::chrono::duration<double>(std::chrono::steady_clock::now() - t_start).count(); };
+        double t_parse = 0, t_pack = 0, t_device = 0;   // (the CPU path parses and hashes sample by sample: all of it under parse)
         std::optional<std::vector<std::string>> labels;
         std::vector<size_t> order(inputs.size());
         for (size_t i = 0; i < order.size(); ++i) order[i] = i;
@@ -868,7 +891,17 @@ int run_inverted(int argc, char **argv, int first, bool verbose, bool quiet)
             log.info("Creating sketches");
             std::vector<std::vector<uint16_t>> sketches(inputs.size());
             std::vector<std::string> names(inputs.size());
-            {
+            const double t_sketch0 = since_start();
+            if (gpu >= 0) {
+                log.info("Sketching on GPU " + std::to_string(gpu));
+                Device dev(gpu);   // ("no CPU path" without a device: no fallback to the host loop)
+                std::vector<std::vector<uint16_t>> rows =
+                    sketch_inverted_gpu(dev, inputs, kmer, sketch_size, !single_strand, threads, min_count, min_qual, &t_parse, &t_pack, &t_device);
+                for (size_t i = 0; i < inputs.size(); ++i) {
+                    sketches[order[i]] = std::move(rows[i]);
+                    names[order[i]] = inputs[i].first;
+                }
+            } else {
                 std::atomic<size_t> next{0};
                 std::exception_ptr err;
                 std::mutex mu;
@@ -877,7 +910,7 @@ int run_inverted(int argc, char **argv, int first, bool verbose, bool quiet)
                         for (;;) {
                             const size_t i = next.fetch_add(1);
                             if (i >= inputs.size()) break;
-                            sketches[order[i]] = sketch_sample_inverted(inputs[i], kmer, sketch_size, !single_strand);
+                            sketches[order[i]] = sketch_sample_inverted(inputs[i], kmer, sketch_size, !single_strand, min_count, min_qual);
                             names[order[i]] = inputs[i].first;
                         }
                     } catch (...) {
@@ -890,13 +923,19 @@ int run_inverted(int argc, char **argv, int first, bool verbose, bool quiet)
                 work();
                 for (auto &t : pool) t.join();
                 if (err) std::rethrow_exception(err);
+                t_parse = since_start() - t_sketch0;
             }
+            const double t_sketched = since_start();
+            double t_write = 0;
             if (write_skq_flag) {
                 log.info("Writing bins for use with precluster as " + *output + ".skq");
                 write_skq(*output + ".skq", sketches);
+                t_write = since_start() - t_sketched;
             }
             log.info("Inverting sketch order");
+            const double t_invert0 = since_start();
             Inverted inv = Inverted::from_sketches(sketches, names, kmer, !single_strand);
+            const double t_invert = since_start() - t_invert0;
             inv.labels = labels;
             if (metadata_file) {   // parse_metadata_info, src/io.rs:118-137; lib.rs:557-568
                 std::ifstream mf(*metadata_file);
@@ -920,7 +959,13 @@ int run_inverted(int argc, char **argv, int first, bool verbose, bool quiet)
                 }
                 inv.metadata = md;
             }
+            const double t_save0 = since_start();
             inv.save(*output);
+            t_write += since_start() - t_save0;
+            if (timing) {
+                std::fprintf(stderr, "TIMING inverted build: parse=%.3fs pack=%.3fs device=%.3fs invert=%.3fs write=%.3fs total=%.3fs\n",
+                             t_parse, t_pack, t_device, t_invert, t_write, since_start());
+            }
         } catch (const std::exception &e) {
             throw Panic(e.what());
         }
@@ -1089,7 +1134,8 @@ int main(int argc, char **argv)
         std::cout << "Usage: sketchlib [OPTIONS] <COMMAND>\n\nCommands:\n"
                      "  sketch  Create sketches from input data (DNA assemblies and read sets, amino-acid sequences; CPU, or GPU with --gpu)\n"
                      "  dist    Calculate pairwise distances using sketches (GPU)\n"
-                     "  inverted build|query|precluster  Inverted index of single-k sketches; match queries against it (GPU);\n"
+                     "  inverted build|query|precluster  Inverted index of single-k sketches of DNA assemblies and read sets (CPU, or GPU\n"
+                     "                                   with --gpu); match queries against it (GPU; --gpu sketches the queries there too);\n"
                      "                                   kNN restricted to its candidates (GPU)\n";
         return sub >= argc ? 2 : 0;
     }

@@ -63,8 +63,18 @@ class Inverted {
 };
 
 // Inverted::sketch_files_inverted for one single-entry sample (inverted.rs:303-395):
-// get_signs_no_densify over exactly `sketch_size` bins, densify_bin, `as u16`.
-std::vector<uint16_t> sketch_sample_inverted(const InputFastx &input, size_t k, uint64_t sketch_size, bool rc);
+// get_signs_no_densify over exactly `sketch_size` bins, densify_bin, `as u16`.  A read set (FASTQ; load_sample) goes
+// through the k-mer count filter as in `sketch`; min_count / min_qual apply to read sets only (defaults 5 / 20).
+std::vector<uint16_t> sketch_sample_inverted(const InputFastx &input, size_t k, uint64_t sketch_size, bool rc,
+                                             uint16_t min_count = 5, uint8_t min_qual = 20);
+// The same for a list of samples with hashing, bin minima, densification and the u16 rows on the device (sketch_gpu.cpp:
+// skl_sketch_bins_u16_packed; read sets under a count filter: skl_reads_survivors + skl_sketch_finish_u16).  Rows in input
+// order, byte for byte sketch_sample_inverted's; the first failing sample in input order raises the CPU path's error.
+// SKL_CLI_TIMING: *t_parse / *t_pack / *t_device (seconds) if asked for.
+std::vector<std::vector<uint16_t>> sketch_inverted_gpu(Device &dev, const std::vector<InputFastx> &inputs, size_t k,
+                                                       uint64_t sketch_size, bool rc, size_t threads, uint16_t min_count = 5,
+                                                       uint8_t min_qual = 20, double *t_parse = nullptr, double *t_pack = nullptr,
+                                                       double *t_device = nullptr);
 
 void write_skq(const std::string &path, const std::vector<std::vector<uint16_t>> &sketches);
 // [n_samples * sketch_size] u16; throws if the file does not hold exactly that many.

@@ -435,15 +435,23 @@ void check_read_signs(bool any_window, const std::vector<uint64_t> &signs, const
     }
 }
 
-std::vector<uint16_t> sketch_sample_inverted(const InputFastx &input, size_t k, uint64_t sketch_size, bool rc)
+std::vector<uint16_t> sketch_sample_inverted(const InputFastx &input, size_t k, uint64_t sketch_size, bool rc,
+                                             uint16_t min_count, uint8_t min_qual)
 {
     Sequence seq;
-    for (const auto &file : input.second) add_fasta(file, seq);
+    load_sample(input, min_qual, seq);
     uint64_t total = 0;
     for (uint64_t c : seq.acgt) total += c;
     if (total == 0) throw std::runtime_error(input.first + " has no valid sequence");
     std::vector<uint64_t> signs((size_t)sketch_size, UINT64_MAX);   // exactly sketch_size bins, inverted.rs:352-357
-    bin_minima(seq, k, rc, signs);
+    if (seq.reads) {   // every window through the count filter, in stream order (inverted.rs:348-361, as sketch_sample)
+        const uint64_t bin_size = (SIGN_MOD + sketch_size - 1) / sketch_size;
+        KmerFilter filter(min_count);
+        const bool any = for_each_window(seq, k, rc, [&](size_t, uint64_t sign) { offer_sign(signs.data(), bin_size, filter, sign); });
+        check_read_signs(any, signs, input.first, k, min_count);
+    } else {
+        bin_minima(seq, k, rc, signs);
+    }
     densify_bin(signs);
     std::vector<uint16_t> out(signs.size());
     for (size_t i = 0; i < signs.size(); ++i) out[i] = (uint16_t)signs[i];   // `*h as u16`, inverted.rs:380

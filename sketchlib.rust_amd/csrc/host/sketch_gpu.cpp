@@ -3,6 +3,9 @@
 // land in the `.skd` image as they come back; file writers on the host.  Read sets
 // with a count filter (min_count >= 2) hash on the device too (skl_reads_survivors), in chunks of window
 // starts, and the host replays the survivors through the filter and finishes their signs itself.
+// `inverted build --gpu` / `inverted query --gpu` (sketch_inverted_gpu, at the end): the same parsing, packing and batches for
+// an index's rows -- one k-mer length, exactly sketch_size bins, u16 -- through skl_sketch_bins_u16_packed, and read sets under
+// a count filter through the survivors path above with skl_sketch_finish_u16 behind it.
 #include <algorithm>
 #include <atomic>
 #include <chrono>
@@ -17,6 +20,7 @@
 
 #include "aahash.hpp"
 #include "distances.hpp"
+#include "inverted.hpp"
 #include "read_filter.hpp"
 #include "sketch.hpp"
 #include "sketchlib_dist.h"
@@ -502,6 +506,132 @@ MultiSketch sketch_files_gpu(Device &dev, const std::string &output_prefix, cons
         }
     }
     return m;
+}
+
+// `inverted build --gpu` / `inverted query --gpu`: the rows of an inverted index -- one k-mer length, exactly sketch_size bins,
+// `sign as u16` -- with hashing, bin minima, densification and the u16 emit on the device.  Parsing and
+// packing on host threads, batches as in sketch_files_gpu.  Every sample's error is kept and the first in input order is
+// raised at the end, which is what the CPU path reports on one thread.
+std::vector<std::vector<uint16_t>> sketch_inverted_gpu(Device &dev, const std::vector<InputFastx> &inputs, size_t k,
+                                                       uint64_t sketch_size, bool rc, size_t threads, uint16_t min_count,
+                                                       uint8_t min_qual, double *t_parse_out, double *t_pack_out, double *t_device_out)
+{
+    const size_t n = inputs.size();
+    const uint64_t S = sketch_size;
+    const auto t_start = std::chrono::steady_clock::now();
+    auto since = [&] { return std::chrono::duration<double>(std::chrono::steady_clock::now() - t_start).count(); };
+    double t_pack = 0, t_device = 0;
+
+    // 1. parse (threads)
+    std::vector<Sequence> seqs(n);
+    std::vector<std::string> error(n);
+    parallel_for(n, threads, [&](size_t i) {
+        try {
+            load_sample(inputs[i], min_qual, seqs[i]);
+            uint64_t total = 0;
+            for (uint64_t c : seqs[i].acgt) total += c;
+            if (total == 0) throw std::runtime_error(inputs[i].first + " has no valid sequence");
+        } catch (const std::exception &e) {
+            error[i] = e.what();
+            if (error[i].empty()) error[i] = "unreadable input";
+        }
+    });
+    const double t_parse = since();
+    std::vector<std::vector<uint16_t>> out(n);
+    // read sets under a count filter go their own way; assemblies (and read sets without one) take the bin-minimum kernel and
+    // the u16 finish behind it
+    std::vector<size_t> plain, filtered;
+    for (size_t i = 0; i < n; ++i) {
+        if (error[i].empty()) (seqs[i].reads && min_count >= 2 ? filtered : plain).push_back(i);
+    }
+
+    // 2. hash + bin minima + densify + u16 on the device, in batches of at most ~4 G bases and 1 GiB of signs on the device
+    constexpr uint64_t BATCH_CODES = 4ull << 30, BATCH_SIGN_BYTES = 1ull << 30;
+    for (size_t b0 = 0; b0 < plain.size();) {
+        const double p0 = since();
+        size_t b1 = b0;
+        uint64_t codes_in_batch = 0;
+        while (b1 < plain.size() && (b1 == b0 || (codes_in_batch + seqs[plain[b1]].codes.size() <= BATCH_CODES &&
+                                                  (b1 - b0 + 1) * S * sizeof(uint64_t) <= BATCH_SIGN_BYTES))) {
+            codes_in_batch += seqs[plain[b1]].codes.size();
+            ++b1;
+        }
+        const size_t nb = b1 - b0;
+        std::vector<uint64_t> code_begin(nb + 1, 0), word_begin(nb + 1, 0), offset_begin(nb + 1, 0), offsets;
+        for (size_t i = 0; i < nb; ++i) {
+            const Sequence &s = seqs[plain[b0 + i]];
+            code_begin[i + 1] = code_begin[i] + s.codes.size();
+            word_begin[i + 1] = word_begin[i] + (s.codes.size() + 15) / 16;
+            offsets.insert(offsets.end(), s.offsets.begin(), s.offsets.end());
+            offset_begin[i + 1] = offsets.size();
+        }
+        std::unique_ptr<uint32_t[]> packed(new uint32_t[std::max<uint64_t>(word_begin[nb], 1)]);   // not zero-filled
+        parallel_for(nb, threads, [&](size_t i) { pack_codes(seqs[plain[b0 + i]].codes, packed.get() + word_begin[i]); });
+        std::vector<uint16_t> rows(nb * S);
+        std::vector<uint8_t> flags(nb, 0);
+        const double d0 = since();
+        t_pack += d0 - p0;
+        if (skl_sketch_bins_u16_packed(dev.ctx(), packed.get(), code_begin.data(), offsets.data(), offset_begin.data(), nb, k, S,
+                                       rc ? 1 : 0, rows.data(), flags.data()) != SKL_OK) {
+            throw std::runtime_error(skl_last_error());
+        }
+        t_device += since() - d0;
+        for (size_t i = 0; i < nb; ++i) {
+            const size_t at = plain[b0 + i];
+            if (flags[i] & SKL_FINISH_EMPTY) {
+                error[at] = "K-mer larger than smallest valid sequence";   // as the CPU path
+            } else {
+                out[at].assign(rows.begin() + i * S, rows.begin() + (i + 1) * S);
+            }
+            Sequence().codes.swap(seqs[at].codes);   // release
+        }
+        b0 = b1;
+    }
+
+    // 2'. read sets with a count filter: survivors on the device, the filter replayed on the host (one k, sketch_size bins),
+    // then the u16 finish of their signs on the device.  A batch holds at most 64 streams (one 24 MiB filter each) and ~1 G bases.
+    const std::vector<size_t> kmers{k};
+    ReadsTiming rt;
+    for (size_t b0 = 0; b0 < filtered.size();) {
+        const double d0 = since();
+        size_t b1 = b0;
+        uint64_t codes_in_batch = 0;
+        while (b1 < filtered.size() &&
+               (b1 == b0 || (b1 - b0 + 1 <= 64 && codes_in_batch + seqs[filtered[b1]].codes.size() <= (1ull << 30)))) {
+            codes_in_batch += seqs[filtered[b1]].codes.size();
+            ++b1;
+        }
+        const std::vector<size_t> idx(filtered.begin() + b0, filtered.begin() + b1);
+        std::vector<uint64_t> signs;
+        std::vector<char> any_window;
+        reads_signs_gpu(dev, seqs, idx, kmers, S, rc, min_count, threads, signs, any_window, rt);
+        for (size_t i = 0; i < idx.size(); ++i) {
+            try {
+                check_read_signs(any_window[i] != 0, std::vector<uint64_t>(signs.begin() + i * S, signs.begin() + (i + 1) * S),
+                                 inputs[idx[i]].first, k, min_count);
+            } catch (const std::exception &e) {
+                error[idx[i]] = e.what();
+            }
+        }
+        std::vector<uint16_t> rows(idx.size() * S);
+        std::vector<uint8_t> flags(idx.size(), 0);
+        if (skl_sketch_finish_u16(dev.ctx(), signs.data(), idx.size(), S, rows.data(), flags.data()) != SKL_OK) {
+            throw std::runtime_error(skl_last_error());
+        }
+        for (size_t i = 0; i < idx.size(); ++i) {
+            if (error[idx[i]].empty()) out[idx[i]].assign(rows.begin() + i * S, rows.begin() + (i + 1) * S);
+            Sequence().codes.swap(seqs[idx[i]].codes);   // release
+        }
+        t_device += since() - d0;
+        b0 = b1;
+    }
+    for (const auto &e : error) {
+        if (!e.empty()) throw std::runtime_error(e);
+    }
+    if (t_parse_out) *t_parse_out = t_parse;
+    if (t_pack_out) *t_pack_out = t_pack;
+    if (t_device_out) *t_device_out = t_device;
+    return out;
 }
 
 }  // namespace skl_host

@@ -407,14 +407,18 @@ hipError_t launch_aa_sketch_signs(const AaSketchArgs &args, hipStream_t stream);
 struct FinishArgs {
     const uint64_t *signs;         // [n_streams][num_bins] bin minima, u64::MAX for an empty bin
     uint64_t n_streams;
-    uint32_t num_bins;             // a multiple of 64
+    uint32_t num_bins;             // a multiple of 64 (plane form); any count >= 1 (u16 form)
     uint32_t max_attempts;         // probe cap per bin (finish_max_attempts)
     uint64_t *usigs;               // [n_streams][finish_words(num_bins)]
     uint64_t *first_sign;          // [n_streams] the densified signs[0], all 64 bits
     uint8_t *flags;                // [n_streams] FINISH_DENSIFIED | FINISH_ALL_EMPTY | FINISH_UNFINISHED
     uint32_t *targets;             // global form: [finish_workgroups()][num_bins] scratch; LDS form: unused
+    uint16_t *bins_u16;            // u16 form only: [n_streams][num_bins], `sign as u16` of the densified bins
 };
 hipError_t launch_sketch_finish(const FinishArgs &args, hipStream_t stream);
+// The u16 form of the same kernel (an inverted index's rows): num_bins is ANY count from 1 to 2^32 - 1; writes bins_u16 and
+// flags, not usigs / first_sign.
+hipError_t launch_sketch_finish_u16(const FinishArgs &args, hipStream_t stream);
 
 // Survivors of the read sketcher's count filter (read_survivors.hip, skl_reads_survivors): every valid window
 // of every (sample, k) stream in a range of window starts whose sign is below its bin's threshold.
