@@ -25,6 +25,9 @@
  * LIMITS (one place; each is checked and reported with SKL_ERR_INVALID_ARG / SKL_ERR_OOM, never silently):
  *   - samples per slab: < 2^31; the library keeps TWO copies of every slab in HBM (row layout + lane layout,
  *     2 x n x nk x sketchsize64 x 112 B): ~7 M genomes per 288 GB GPU at sketchsize64 = 32, nk = 5.
+ *   - skl_sketches_select / skl_sketches_concat return a NEW slab and leave their inputs resident: source and result are both
+ *     in HBM (their row slabs, and the lane slab of each once a call has used it as the column side) until the caller
+ *     destroys one.  Dropping 10 % of a 18 GB slab therefore needs 16 GB more for as long as the old slab lives.
  *   - sketchsize64: < 2^25.  Up to 1 023 (65 472 bins) a k-mer length's counts live in u16 fields; larger sketches
  *     (the reference's "100000-1000000 for SNP level resolution", lib.rs:41-42) take the same kernel, walked in
  *     segments of 1 016 chunks; their core/accessory distances go through a bin-match count scratch of at most
@@ -155,6 +158,19 @@ int skl_sketches_create(skl_ctx *ctx, const uint64_t *bins, int on_device, size_
 int skl_sketches_set_completeness(skl_sketches *s, const double *completeness_host);
 int skl_sketches_destroy(skl_sketches *s);
 size_t skl_sketches_n_samples(const skl_sketches *s);
+/* New slabs from resident ones, without a trip through host memory.  Both return a NEW handle with its own
+ * generation id (what early-break decisions are kept under) and never touch their inputs, which stay valid and are the
+ * caller's to destroy; the rows are copied slab to slab on the context's stream, and the call returns when they are in
+ * place.  A completeness vector follows its samples and is installed in the result the way
+ * skl_sketches_set_completeness installs one (everything derived from it is recomputed for the result).
+ * select: samples ids[0 .. n_ids) of `s`, in that order; repeats are allowed (remove_genomes' keep list,
+ * multisketch.rs:305-348; a subset; a reordering).  n_ids == 0 or an id >= the slab's sample count is
+ * SKL_ERR_INVALID_ARG, found before anything is allocated or launched. */
+int skl_sketches_select(skl_ctx *ctx, const skl_sketches *s, const uint32_t *ids_host, size_t n_ids, skl_sketches **out);
+/* concat: a's samples, then b's (merge_sketches, multisketch.rs:247-267; `append`).  Different k-mer lists or
+ * sketchsize64: SKL_ERR_INCOMPATIBLE (is_compatible_with, multisketch.rs:222-226); a completeness vector on one side
+ * only: SKL_ERR_INVALID_ARG. */
+int skl_sketches_concat(skl_ctx *ctx, const skl_sketches *a, const skl_sketches *b, skl_sketches **out);
 
 /* set_k (src/distances/mod.rs:25-37): kmer == 0 means Option::None -> CoreAcc. */
 int skl_set_k(const skl_sketches *s, size_t kmer, int ani, double completeness_cutoff,

@@ -86,6 +86,8 @@ _SIG = [
     ("skl_sketches_set_completeness", C.c_int, [_P, _P]),
     ("skl_sketches_destroy", C.c_int, [_P]),
     ("skl_sketches_n_samples", C.c_size_t, [_P]),
+    ("skl_sketches_select", C.c_int, [_P, _P, _P, C.c_size_t, C.POINTER(_P)]),
+    ("skl_sketches_concat", C.c_int, [_P, _P, _P, C.POINTER(_P)]),
     ("skl_set_k", C.c_int, [_P, C.c_size_t, C.c_int, C.c_double, C.POINTER(DistParams)]),
     ("skl_self_dists_all", C.c_int, [_P, _P, C.POINTER(DistParams), _P, C.c_int]),
     ("skl_self_dists_rows", C.c_int, [_P, _P, C.POINTER(DistParams), C.c_size_t, C.c_size_t, _P,
@@ -371,6 +373,25 @@ class Sketches:
         assert comp.size == self.n
         _check(load().skl_sketches_set_completeness(self._h, comp.ctypes.data))
 
+    @classmethod
+    def _adopt(cls, ctx, handle, n, kmers, sketchsize64):
+        """A Sketches around a handle the library made (select / concat)."""
+        self = cls.__new__(cls)
+        self.ctx = ctx
+        self.n = int(n)
+        self.kmers = np.ascontiguousarray(kmers, dtype=np.uintp)
+        self.nk = len(self.kmers)
+        self.ss64 = int(sketchsize64)
+        self._h = handle
+        return self
+
+    def select(self, ids):
+        """skl_sketches_select: a NEW slab of samples ids[0], ids[1], .. (repeats allowed); this one is untouched."""
+        ids = np.ascontiguousarray(ids, dtype=np.uint32).reshape(-1)
+        h = _P()
+        _check(load().skl_sketches_select(self.ctx._h, self._h, ids.ctypes.data, ids.size, C.byref(h)))
+        return Sketches._adopt(self.ctx, h, ids.size, self.kmers, self.ss64)
+
     def set_k(self, kmer=None, ani=False, cutoff=0.64):
         """distances::set_k (mod.rs:25-37)."""
         p = DistParams()
@@ -388,6 +409,13 @@ class Sketches:
             self.close()
         except Exception:
             pass
+
+
+def concat(a, b):
+    """skl_sketches_concat: a NEW slab of a's samples, then b's; both inputs are untouched."""
+    h = _P()
+    _check(load().skl_sketches_concat(a.ctx._h, a._h, b._h, C.byref(h)))
+    return Sketches._adopt(a.ctx, h, a.n + b.n, a.kmers, a.ss64)
 
 
 def params(dist_type=COREACC, k_idx=0, ani=False, cutoff=0.64):

@@ -684,17 +684,14 @@ static int ensure_dtab(const skl_sketches *cs, int jout, size_t k_idx, float **o
     return SKL_OK;
 }
 
-extern "C" int skl_sketches_create(skl_ctx *ctx, const uint64_t *bins, int on_device,
-                                   size_t n_samples, size_t nk, const size_t *kmers,
-                                   size_t sketchsize64, skl_sketches **out)
+// A slab of n_samples rows with nothing in them yet: registered, its pad rows zeroed (queued on the context's stream) and its
+// k-mer table uploaded.  Rows [0, n_samples) are the caller's to fill on that stream (skl_sketches_create: a copy;
+// capi_slab.cpp: a gather or two device copies); on an error the caller destroys *out.
+int slab_alloc(skl_ctx *ctx, size_t n_samples, size_t nk, const size_t *kmers, size_t sketchsize64, skl_sketches **out)
 {
-    SKL_TRY(ctx_bind(ctx));
-    if (!out) return fail(SKL_ERR_INVALID_ARG, "out is null");
-    *out = nullptr;
     if (nk == 0 || sketchsize64 == 0 || !kmers) {
         return fail(SKL_ERR_INVALID_ARG, "need at least one k-mer length and a non-zero sketch size");
     }
-    if (n_samples && !bins) return fail(SKL_ERR_INVALID_ARG, "bins is null");
     if (n_samples >= (1ull << 31) || sketchsize64 >= (1ull << 25) || nk >= (1ull << 16)) {
         return fail(SKL_ERR_INVALID_ARG, "dimensions out of range");
     }
@@ -718,27 +715,46 @@ extern "C" int skl_sketches_create(skl_ctx *ctx, const uint64_t *bins, int on_de
         return fail(e == hipErrorOutOfMemory ? SKL_ERR_OOM : SKL_ERR_HIP, "hipMalloc(slab %zu B): %s",
                     total * sizeof(uint64_t), hipGetErrorString(e));
     }
-    int rc = SKL_OK;
     do {
         e = hipMemsetAsync(s->d_rows + n_samples * words, 0, A_PAD_ROWS * words * sizeof(uint64_t),
                            ctx->stream);
         if (e != hipSuccess) break;
-        if (n_samples) {
-            e = hipMemcpyAsync(s->d_rows, bins, n_samples * words * sizeof(uint64_t),
-                               on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice,
-                               ctx->stream);
-            if (e != hipSuccess) break;
-        }
         std::vector<double> kf(nk);
         for (size_t i = 0; i < nk; ++i) kf[i] = (double)kmers[i];
         e = hipMalloc((void **)&s->d_kf, nk * sizeof(double));
         if (e != hipSuccess) break;
         e = hipMemcpy(s->d_kf, kf.data(), nk * sizeof(double), hipMemcpyHostToDevice);
-        if (e != hipSuccess) break;
-        e = hipStreamSynchronize(ctx->stream);
     } while (0);
     if (e != hipSuccess) {
-        rc = fail(SKL_ERR_HIP, "slab upload: %s", hipGetErrorString(e));
+        const int rc = fail(SKL_ERR_HIP, "slab upload: %s", hipGetErrorString(e));
+        skl_sketches_destroy(s);
+        return rc;
+    }
+    *out = s;
+    return SKL_OK;
+}
+
+extern "C" int skl_sketches_create(skl_ctx *ctx, const uint64_t *bins, int on_device,
+                                   size_t n_samples, size_t nk, const size_t *kmers,
+                                   size_t sketchsize64, skl_sketches **out)
+{
+    SKL_TRY(ctx_bind(ctx));
+    if (!out) return fail(SKL_ERR_INVALID_ARG, "out is null");
+    *out = nullptr;
+    if (nk == 0 || sketchsize64 == 0 || !kmers) {
+        return fail(SKL_ERR_INVALID_ARG, "need at least one k-mer length and a non-zero sketch size");
+    }
+    if (n_samples && !bins) return fail(SKL_ERR_INVALID_ARG, "bins is null");
+    skl_sketches *s = nullptr;
+    SKL_TRY(slab_alloc(ctx, n_samples, nk, kmers, sketchsize64, &s));
+    hipError_t e = hipSuccess;
+    if (n_samples) {
+        e = hipMemcpyAsync(s->d_rows, bins, n_samples * s->sample_words() * sizeof(uint64_t),
+                           on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, ctx->stream);
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    if (e != hipSuccess) {
+        const int rc = fail(SKL_ERR_HIP, "slab upload: %s", hipGetErrorString(e));
         skl_sketches_destroy(s);
         return rc;
     }

@@ -161,6 +161,9 @@ struct DevBuf {
 using skl::BAND_BYTES;   // (knn_plan.hpp: the kNN band heights read it too)
 
 SKL_INTERNAL int ctx_bind(skl_ctx *ctx);
+// a registered slab whose rows [0, n_samples) are still to be written on the context's stream (capi.cpp; the pad rows are
+// queued to zero, nothing is waited for); skl_sketches_create and the slab operations of capi_slab.cpp fill it
+SKL_INTERNAL int slab_alloc(skl_ctx *ctx, size_t n_samples, size_t nk, const size_t *kmers, size_t sketchsize64, skl_sketches **out);
 // which glibc_log.hpp form reproduces this host's libm log(): probed once per process against
 // std::log; SKL_LOG_FMA / SKL_LOG_SSE2, or -1 when neither does (the FMA form is then used and a
 // warning printed once)

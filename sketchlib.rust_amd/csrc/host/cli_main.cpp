@@ -23,6 +23,7 @@
 #include <string>
 #include <vector>
 
+#include "dbmaint.hpp"
 #include "distances.hpp"
 #include "inverted.hpp"
 #include "sketchlib_dist.h"
@@ -612,6 +613,216 @@ int run_sketch(int argc, char **argv, int first, bool verbose, bool quiet)
     return 0;
 }
 
+// ---- `sketchlib merge | append | delete | info` (src/cli.rs:240-322, src/lib.rs:454-483 and 793-947) ----
+// merge, delete and info are file operations (dbmaint.cpp): no device context is made.
+int run_merge(int argc, char **argv, int first)
+{
+    g_usage = "sketchlib merge -o <OUTPUT> <DB1> <DB2>";
+    std::vector<std::string> dbs;
+    std::optional<std::string> output;
+    for (int i = first; i < argc; ++i) {
+        const std::string arg = argv[i];
+        if (arg == "-h" || arg == "--help") {
+            std::cout << "Merge two sketch files (.skm and .skd pair)\n\nUsage: " << g_usage << "\n\n"
+                         "Arguments:\n  <DB1>  The first .skd (sketch data) file\n  <DB2>  The second .skd (sketch data) file\n\n"
+                         "Options:\n  -o <OUTPUT>  Output filename for the merged sketch\n  -h, --help   Print help\n";
+            std::exit(0);
+        }
+        else if (arg == "-v" || arg == "--verbose" || arg == "--quiet") continue;
+        else if (arg == "-o") {
+            if (i + 1 >= argc) usage_error("a value is required for '-o <OUTPUT>' but none was supplied");
+            output = argv[++i];
+        }
+        else if (arg.size() > 2 && arg[0] == '-' && arg[1] == 'o') output = arg.substr(2);
+        else if (arg.size() > 1 && arg[0] == '-') usage_error("unexpected argument '" + arg + "' found");
+        else dbs.push_back(arg);
+    }
+    if (dbs.size() < 2) usage_error(std::string("the following required arguments were not provided:\n  ") + (dbs.empty() ? "<DB1>\n  <DB2>" : "<DB2>"));
+    if (dbs.size() > 2) usage_error("unexpected argument '" + dbs[2] + "' found");
+    if (!output) usage_error("the following required arguments were not provided:\n  -o <OUTPUT>");
+    db_merge(dbs[0], dbs[1], *output);
+    return 0;
+}
+
+int run_delete(int argc, char **argv, int first)
+{
+    g_usage = "sketchlib delete <DB> <SAMPLES> <OUTPUT_FILE>";
+    std::vector<std::string> pos;
+    for (int i = first; i < argc; ++i) {
+        const std::string arg = argv[i];
+        if (arg == "-h" || arg == "--help") {
+            std::cout << "Delete genome(s) from a database (input: one id per line)\n\nUsage: " << g_usage << "\n\n"
+                         "Arguments:\n  <DB>           Sketching database\n  <SAMPLES>      Input file with IDs to delete (one ID per line)\n"
+                         "  <OUTPUT_FILE>  Output prefix of the database without them\n\nOptions:\n  -h, --help  Print help\n";
+            std::exit(0);
+        }
+        else if (arg == "-v" || arg == "--verbose" || arg == "--quiet") continue;
+        else if (arg.size() > 1 && arg[0] == '-') usage_error("unexpected argument '" + arg + "' found");
+        else pos.push_back(arg);
+    }
+    static const char *const names[] = {"<DB>", "<SAMPLES>", "<OUTPUT_FILE>"};
+    if (pos.size() < 3) {
+        std::string msg = "the following required arguments were not provided:";
+        for (size_t i = pos.size(); i < 3; ++i) msg += std::string("\n  ") + names[i];
+        usage_error(msg);
+    }
+    if (pos.size() > 3) usage_error("unexpected argument '" + pos[3] + "' found");
+    db_delete(pos[0], pos[1], pos[2]);
+    return 0;
+}
+
+int run_info(int argc, char **argv, int first)
+{
+    g_usage = "sketchlib info [OPTIONS] <SKM_FILE>";
+    std::optional<std::string> file;
+    bool sample_info = false;
+    for (int i = first; i < argc; ++i) {
+        const std::string arg = argv[i];
+        if (arg == "-h" || arg == "--help") {
+            std::cout << "Print information about a .skm or .ski file\n\nUsage: " << g_usage << "\n\n"
+                         "Arguments:\n  <SKM_FILE>  Sketch metadata file (.skm) or inverted index (.ski) to describe\n\n"
+                         "Options:\n      --sample-info  Write out the information for every sample contained\n  -h, --help         Print help\n";
+            std::exit(0);
+        }
+        else if (arg == "-v" || arg == "--verbose" || arg == "--quiet") continue;
+        else if (arg == "--sample-info") sample_info = true;
+        else if (arg.size() > 1 && arg[0] == '-') usage_error("unexpected argument '" + arg + "' found");
+        else if (!file) file = arg;
+        else usage_error("unexpected argument '" + arg + "' found");
+    }
+    if (!file) usage_error("the following required arguments were not provided:\n  <SKM_FILE>");
+    db_info(*file, sample_info, std::cout);
+    std::cout.flush();
+    return 0;
+}
+
+// `append`: the new samples are sketched the way the database was (its k-mer lengths, sketch size and sequence type; the
+// `sketch` code path, on the host or with --gpu on the device) into <out>, the database's blocks follow them, and the
+// metadata is the new samples' with the database's merged in behind (lib.rs:857-875).
+int run_append(int argc, char **argv, int first, bool verbose, bool quiet)
+{
+    g_usage = "sketchlib append [OPTIONS] -o <OUTPUT> <DB> <SEQ_FILES|-f <FILE_LIST>>";
+    std::optional<std::string> db, file_list, output;
+    std::vector<std::string> seq_files;
+    bool single_strand = false, concat_fasta = false;
+    uint16_t min_count = 5;   // DEFAULT_MINCOUNT / DEFAULT_MINQUAL, cli.rs:12-15 (read sets only)
+    uint8_t min_qual = 20;
+    size_t threads = 1;
+    int gpu = -1;
+    std::optional<int> level;
+    for (int i = first; i < argc; ++i) {
+        const std::string arg = argv[i];
+        auto value = [&](const std::string &flag) -> std::string {
+            if (i + 1 >= argc) usage_error("a value is required for '" + flag + "' but none was supplied");
+            return argv[++i];
+        };
+        if (arg == "-h" || arg == "--help") {
+            std::cout <<
+                "Append new genomes to be sketched to an existing sketch database\n\nUsage: " << g_usage << "\n\n"
+                "The new samples come FIRST in the output, the samples of <DB> after them.\n\n"
+                "Options:\n"
+                "  -f <FILE_LIST>               File listing sample names and their files (name<TAB>file[<TAB>file])\n"
+                "  -o <OUTPUT>                  Output prefix (.skm / .skd); must differ from <DB>\n"
+                "      --single-strand          Ignore the reverse complement\n"
+                "      --min-count <MIN_COUNT>  Read sets: minimum k-mer count [default: 5]\n"
+                "      --min-qual <MIN_QUAL>    Read sets: minimum quality byte of a base [default: 20]\n"
+                "      --concat-fasta           aa: every FASTA record is a sample of its own\n"
+                "      --level <LEVEL>          aa: must be the database's aaHash level [default: the database's]\n"
+                "      --threads <THREADS>      Number of CPU threads [default: 1]\n"
+                "      --gpu                    Hash on the GPU (device 0)\n"
+                "      --device <D>             The same on device D\n"
+                "  -h, --help                   Print help\n";
+            std::exit(0);
+        }
+        else if (arg == "-v" || arg == "--verbose") verbose = true;
+        else if (arg == "--quiet") quiet = true;
+        else if (arg == "-f") file_list = value("-f <FILE_LIST>");
+        else if (arg == "-o") output = value("-o <OUTPUT>");
+        else if (arg == "--single-strand") single_strand = true;
+        else if (arg == "--concat-fasta") concat_fasta = true;
+        else if (arg == "--min-count") min_count = (uint16_t)parse_bounded("--min-count <MIN_COUNT>", value(arg), 0xFFFF);
+        else if (arg == "--min-qual") min_qual = (uint8_t)parse_bounded("--min-qual <MIN_QUAL>", value(arg), 0xFF);
+        else if (arg == "--threads") threads = std::max<size_t>(1, parse_usize("--threads <THREADS>", value(arg)));
+        else if (arg == "--gpu") gpu = 0;
+        else if (arg == "--device") gpu = (int)parse_usize("--device <D>", value(arg));
+        else if (arg == "--level") {
+            const std::string v = value(arg);
+            if (v != "level1" && v != "level2" && v != "level3") usage_error("invalid value '" + v + "' for '--level <LEVEL>'\n  [possible values: level1, level2, level3]");
+            level = v.back() - '0';
+        }
+        else if (arg.size() > 1 && arg[0] == '-') usage_error("unexpected argument '" + arg + "' found");
+        else if (!db) db = arg;
+        else seq_files.push_back(arg);
+    }
+    if (!db) usage_error("the following required arguments were not provided:\n  <DB>");
+    if (!output) usage_error("the following required arguments were not provided:\n  -o <OUTPUT>");
+    if (seq_files.empty() == !file_list.has_value()) {
+        usage_error("exactly one of <SEQ_FILES>... or -f <FILE_LIST> must be given");
+    }
+    const Logger log{verbose && !quiet, !quiet};
+    const std::string db_name = strip_sketch_extension(*db);
+    if (strip_sketch_extension(*output) == db_name) {
+        throw std::runtime_error("the output " + *output + " is the database itself: append writes a new database");
+    }
+    log.info("Getting input files");
+    const std::vector<InputFastx> inputs = file_list ? read_rfile(*file_list) : read_input_fastas(seq_files);
+    log.info("Parsed " + std::to_string(inputs.size()) + " samples in input list");
+    MultiSketch db_metadata = MultiSketch::load_metadata(db_name);   // `?` in the reference: Error, exit 1
+    {   // append_compatibility, multisketch.rs:229-244: before anything is sketched
+        std::vector<std::string> duplicates;
+        for (const auto &in : inputs) {
+            if (db_metadata.has_sample(in.first)) duplicates.push_back(in.first);
+        }
+        if (!duplicates.empty()) {
+            std::cout << "Duplicates found: " << rust_debug(duplicates) << std::endl;
+            throw Panic("Databases are not compatible for merging.");
+        }
+    }
+    log.info("Passed concat check");
+    SeqType seq;
+    const std::string &hash_type = db_metadata.hash_type();
+    if (hash_type.rfind("AA:Level", 0) == 0 && hash_type.size() == 9 && hash_type[8] >= '1' && hash_type[8] <= '3') {
+        seq.aa = true;
+        seq.level = hash_type[8] - '0';
+        if (level && *level != seq.level) {
+            throw std::runtime_error("--level level" + std::to_string(*level) + " is not the level of the database (" +
+                                     hash_type_debug(hash_type) + "): its samples and the new ones would not be comparable");
+        }
+    } else if (hash_type != "DNA") {
+        std::cerr << "error: this build sketches dna and aa (" << db_name << ".skm has sequence type " << hash_type_debug(hash_type) << ")\n";
+        return 2;
+    }
+    if (concat_fasta && !seq.aa) throw Panic("--concat-fasta currently only supported with --seq-type aa");   // lib.rs:825-827
+    seq.concat_fasta = concat_fasta;
+    const std::vector<size_t> &kmers = db_metadata.kmer_lengths();
+    log.info("Running sketching: sketch_size:" + std::to_string(db_metadata.sketch_size) + " threads:" + std::to_string(threads));
+    MultiSketch fresh;
+    try {
+        if (gpu >= 0) {
+            log.info("Hashing on GPU " + std::to_string(gpu));
+            Device dev(gpu);   // (no device: an error, never the host loop)
+            fresh = sketch_files_gpu(dev, *output, inputs, kmers, db_metadata.sketch_size, !single_strand, threads, min_count, min_qual, seq);
+        } else {
+            fresh = sketch_files(*output, inputs, kmers, db_metadata.sketch_size, !single_strand, threads, min_count, min_qual, seq);
+        }
+    } catch (const std::exception &e) {
+        throw Panic(e.what());   // the reference panics on unreadable / empty input
+    }
+    log.info("Merging and saving sketch data to " + *output + ".skd");
+    append_file(db_name + ".skd", *output + ".skd", false);
+    try {
+        fresh.merge_sketches(db_metadata);
+    } catch (const std::exception &e) {
+        throw Panic(e.what());
+    }
+    try {
+        fresh.save_metadata(*output);
+    } catch (const std::exception &) {
+        throw Panic("Could not save metadata to " + *output);
+    }
+    return 0;
+}
+
 // ---- `sketchlib inverted query` (src/cli.rs:380-412, src/lib.rs:605-680) ----
 // Queries (assemblies or read sets, --min-count / --min-qual as in `sketch`) are sketched the way the index was built
 // (Inverted::sketch_queries, inverted.rs:118-140) -- on host threads, or with --gpu on the device --device names
@@ -1136,7 +1347,12 @@ int main(int argc, char **argv)
                      "  dist    Calculate pairwise distances using sketches (GPU)\n"
                      "  inverted build|query|precluster  Inverted index of single-k sketches of DNA assemblies and read sets (CPU, or GPU\n"
                      "                                   with --gpu); match queries against it (GPU; --gpu sketches the queries there too);\n"
-                     "                                   kNN restricted to its candidates (GPU)\n";
+                     "                                   kNN restricted to its candidates (GPU)\n"
+                     "  merge   Merge two sketch databases (.skm and .skd pair) into a new one (files only)\n"
+                     "  append  Sketch new samples the way a database was sketched and write both as a new database, the new\n"
+                     "          samples first (CPU, or GPU with --gpu)\n"
+                     "  delete  Write a database without the samples listed in a file (files only)\n"
+                     "  info    Print information about a .skm or .ski file (files only)\n";
         return sub >= argc ? 2 : 0;
     }
     if (strcmp(argv[sub], "sketch") == 0) {
@@ -1176,9 +1392,32 @@ int main(int argc, char **argv)
             return 1;
         }
     }
+    const bool is_merge = strcmp(argv[sub], "merge") == 0, is_append = strcmp(argv[sub], "append") == 0;
+    const bool is_delete = strcmp(argv[sub], "delete") == 0, is_info = strcmp(argv[sub], "info") == 0;
+    if (is_merge || is_append || is_delete || is_info) {
+        bool verbose = false, quiet = false;
+        for (int i = 1; i < sub; ++i) {
+            if (strcmp(argv[i], "--quiet") == 0) quiet = true;
+            else verbose = true;
+        }
+        try {
+            if (is_merge) return run_merge(argc, argv, sub + 1);
+            if (is_delete) return run_delete(argc, argv, sub + 1);
+            if (is_info) return run_info(argc, argv, sub + 1);
+            return run_append(argc, argv, sub + 1, verbose, quiet);
+        } catch (const Panic &p) {
+            std::cout.flush();
+            std::cerr << "thread 'main' panicked:\n" << p.what() << "\n";
+            return 101;
+        } catch (const std::exception &e) {
+            std::cerr << "Error: " << e.what() << "\n";
+            return 1;
+        }
+    }
     if (strcmp(argv[sub], "dist") != 0) {
         std::cerr << "error: unrecognized subcommand '" << argv[sub]
-                  << "' (this build provides `sketch` (DNA assemblies and read sets), `dist` (GPU) and `inverted build|query|precluster`)\n";
+                  << "' (this build provides `sketch` (DNA assemblies and read sets), `dist` (GPU) and `inverted build|query|precluster`"
+                     ", and the database commands `merge`, `append`, `delete` and `info`)\n";
         return 2;
     }
     DistArgs args = parse_dist(argc, argv, sub + 1);

@@ -444,4 +444,61 @@ bool MultiSketch::is_compatible_with(const MultiSketch &o) const
     return kmer_lengths_ == o.kmer_lengths_ && sketch_size == o.sketch_size && hash_type_ == o.hash_type_;
 }
 
+void MultiSketch::merge_sketches(const MultiSketch &o)
+{
+    std::unordered_map<std::string, size_t> held = name_map();
+    const size_t offset = sketch_metadata_.size();
+    for (size_t i = 0; i < o.sketch_metadata_.size(); ++i) {
+        SketchMeta sm = o.sketch_metadata_[i];
+        if (held.count(sm.name)) throw std::runtime_error(sm.name + " appears in both databases. Cannot merge sketches.");
+        const size_t new_index = (size_t)sm.index.value_or(i) + offset;
+        sm.index = new_index;
+        held.emplace(sm.name, new_index);
+        name_map_order_.emplace_back(sm.name, new_index);
+        sketch_metadata_.push_back(std::move(sm));
+    }
+    name_lookup_ = std::make_shared<LazyNameMap>();   // (built again on the next lookup)
+}
+
+std::vector<size_t> MultiSketch::remove_samples(const std::vector<std::string> &ids, std::vector<std::string> *missing)
+{
+    const size_t n = sketch_metadata_.size();
+    std::vector<bool> drop_block(n, false);
+    std::set<std::string> drop_names;
+    for (const auto &id : ids) {
+        const auto it = name_map().find(id);
+        if (it == name_map().end()) {
+            if (missing && std::find(missing->begin(), missing->end(), id) == missing->end()) missing->push_back(id);
+            continue;
+        }
+        drop_block[it->second] = true;
+        drop_names.insert(id);
+    }
+    if (missing && !missing->empty()) return {};
+    constexpr size_t GONE = (size_t)-1;
+    std::vector<size_t> kept, new_pos(n, GONE);
+    for (size_t b = 0; b < n; ++b) {
+        if (!drop_block[b]) {
+            new_pos[b] = kept.size();
+            kept.push_back(b);
+        }
+    }
+    std::vector<SketchMeta> meta;
+    for (size_t i = 0; i < n; ++i) {
+        SketchMeta &sm = sketch_metadata_[i];
+        const size_t block = (size_t)sm.index.value_or(i);
+        if (drop_names.count(sm.name) || new_pos[block] == GONE) continue;
+        sm.index = new_pos[block];
+        meta.push_back(std::move(sm));
+    }
+    std::vector<std::pair<std::string, size_t>> order;
+    for (auto &kv : name_map_order_) {
+        if (!drop_names.count(kv.first) && new_pos[kv.second] != GONE) order.emplace_back(std::move(kv.first), new_pos[kv.second]);
+    }
+    sketch_metadata_ = std::move(meta);
+    name_map_order_ = std::move(order);
+    name_lookup_ = std::make_shared<LazyNameMap>();
+    return kept;
+}
+
 }  // namespace skl_host

@@ -85,6 +85,15 @@ class MultiSketch {
     std::optional<size_t> get_sample_index(const std::string &name) const;  // :148-164
     const uint64_t *get_sketch_slice(size_t sketch_idx, size_t k_idx) const;  // :213-219
     bool is_compatible_with(const MultiSketch &other) const;      // :222-226
+    // merge_sketches (:247-267): `other`'s samples after these, their index moved up by the number of samples held here; every
+    // other field stays.  A name held already: std::runtime_error "<name> appears in both databases. Cannot merge sketches."
+    void merge_sketches(const MultiSketch &other);
+    // remove_metadata + the keep list of remove_genomes (:270-348) in one step: drops the samples named in `ids` and returns
+    // the blocks of the .skd that stay, ascending.  Unlike the reference, which keeps the old `index` values (stale unless
+    // only trailing samples go), `index` and the name map are renumbered to the blocks' new positions.  Ids that name no
+    // sample: nothing is changed and they come back in *missing (in the order given, once each).
+    std::vector<size_t> remove_samples(const std::vector<std::string> &ids, std::vector<std::string> *missing);
+    bool has_sample(const std::string &name) const { return name_map().count(name) != 0; }   // name_map.contains_key
     const BinVec &bins() const { return sketch_bins_; }
     void set_bins(const std::vector<uint64_t> &bins) { sketch_bins_.assign(bins.begin(), bins.end()); }
     size_t sample_stride() const { return sample_stride_; }

@@ -631,4 +631,16 @@ struct InvQueryArgs {
 hipError_t launch_inv_planes(const InvPlanesArgs &a, hipStream_t stream);
 hipError_t launch_inv_query(const InvQueryArgs &a, hipStream_t stream);
 
+// skl_sketches_select (slab_ops.hip): whole sample rows of a row slab gathered by index into another row slab.
+// dst row r = src row ids[r]; a row is row_vec 16-byte words (nk * sketchsize64 * 112 B is always a multiple of 16).
+// The caller guarantees ids[r] < rows of src and room for n_ids rows in dst; n_cu sizes the grid.
+struct SlabGatherArgs {
+    const uint4 *src;
+    uint4 *dst;
+    const uint32_t *ids;   // [n_ids], device memory
+    uint64_t n_ids;
+    uint64_t row_vec;
+};
+hipError_t launch_slab_gather(const SlabGatherArgs &a, int n_cu, hipStream_t stream);
+
 }  // namespace skl
