@@ -381,6 +381,19 @@ int skl_inverted_query(skl_ctx *ctx, const skl_inverted *ix, const uint16_t *que
                        void *out);
 size_t skl_inverted_band_queries(skl_ctx *ctx, const skl_inverted *ix, int mode);
 
+/* The best hits of every query (the reference's identification query, SketchlibData::query / get_probs,
+ * src/lib.rs:1019-1109: match counts -> d / (2 S - d), a stable ascending sort, reverse(), the first nouts), selected on
+ * the device behind the counts: hit r of a query is the indexed sample with the r-th largest key
+ * (count << 32) | index compared as u64 -- counts descend and at equal count the HIGHER .ski index comes first, which
+ * is what that sort-and-reverse gives.  out_ids / out_counts: u32 [n_queries][top], host pointers; with
+ * n_eff = min(top, n_samples), entries [n_eff, top) of a row are id 0xFFFFFFFF, count 0 (an empty index: every entry).
+ * Queries run in the bands of SKL_INVQ_MATCH_COUNT (skl_inverted_band_queries); a band's counts stay on the device
+ * and n_queries x top x 8 bytes come back.  The hits of a query live in the workgroup's LDS: top is 1 to
+ * SKL_INVQ_TOP_MAX, anything else is SKL_ERR_INVALID_ARG (not a slower path). */
+#define SKL_INVQ_TOP_MAX 1024
+int skl_inverted_query_top(skl_ctx *ctx, const skl_inverted *ix, const uint16_t *query_bins, size_t n_queries, size_t top,
+                           uint32_t *out_ids, uint32_t *out_counts);
+
 /* GPU sketching: bin minima of `canonical ntHash % SIGN_MOD` over every
  * valid k-mer of DNA samples -- Sketch::get_signs_no_densify (src/sketch/mod.rs:156-176) over
  * NtHashIterator (src/hashing/nthash_iterator.rs:325-523), all samples and k-mer lengths of a

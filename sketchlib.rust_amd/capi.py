@@ -117,6 +117,7 @@ _SIG = [
     ("skl_inverted_destroy", C.c_int, [_P]),
     ("skl_inverted_query", C.c_int, [_P, _P, _P, C.c_size_t, C.c_int, _P]),
     ("skl_inverted_band_queries", C.c_size_t, [_P, _P, C.c_int]),
+    ("skl_inverted_query_top", C.c_int, [_P, _P, _P, C.c_size_t, C.c_size_t, _P, _P]),
     ("skl_sketch_signs", C.c_int, [_P, _P, _P, _P, _P, C.c_size_t, _P, C.c_size_t, C.c_uint64, C.c_int, _P]),
     ("skl_sketch_signs_packed", C.c_int, [_P, _P, _P, _P, _P, C.c_size_t, _P, C.c_size_t, C.c_uint64, C.c_int, _P]),
     ("skl_sketch_signs_aa", C.c_int, [_P, _P, _P, C.c_size_t, _P, C.c_size_t, C.c_uint64, C.c_int, C.c_int, _P]),
@@ -675,6 +676,7 @@ def self_dists_knn_shared_bins(ctx, s, p, knn, skq):
 
 
 INVQ_MATCH_COUNT, INVQ_ANY_BINS, INVQ_ALL_BINS = 0, 1, 2
+INVQ_TOP_MAX = 1024   # SKL_INVQ_TOP_MAX: hits per query of Inverted.top
 
 
 class Inverted:
@@ -707,6 +709,19 @@ class Inverted:
         _check(load().skl_inverted_query(self.ctx._h, self._h, queries.ctypes.data if queries.size else None, nq,
                                          int(mode), out.ctypes.data if out.size else None))
         return out
+
+    def top(self, queries, top):
+        """The `top` best hits of every query, selected on the device (src/lib.rs:1019-1109): (ids, counts), two uint32
+        arrays [n_queries, top] ordered by the key (count << 32) | index descending -- at equal count the higher .ski index
+        first; entries past min(top, n) are id 0xFFFFFFFF, count 0.  top: 1 to INVQ_TOP_MAX."""
+        queries = np.ascontiguousarray(queries, dtype=np.uint16)
+        assert queries.ndim == 2 and queries.shape[1] == self.sketch_size
+        nq, top = queries.shape[0], int(top)
+        shape = (nq, top) if 0 < top <= INVQ_TOP_MAX else (0, 0)   # (the library refuses the rest)
+        ids, counts = np.zeros(shape, dtype=np.uint32), np.zeros(shape, dtype=np.uint32)
+        _check(load().skl_inverted_query_top(self.ctx._h, self._h, queries.ctypes.data if queries.size else None, nq, top,
+                                             ids.ctypes.data if ids.size else None, counts.ctypes.data if counts.size else None))
+        return ids, counts
 
     def close(self):
         if self._h:

@@ -371,6 +371,7 @@ Knobs read_knobs()
     k.sliced_max_pairs = env_int("SKL_SLICED_MAX_PAIRS", -1);
     k.knn_band_rows = std::max(0ll, env_int("SKL_KNN_BAND_ROWS", 0));
     k.invq_band_bytes = std::max(0ll, env_int("SKL_INVQ_BAND_BYTES", 0));
+    k.invq_top_digit_bits = std::max(0ll, env_int("SKL_INVQ_TOP_DIGIT_BITS", 0));
     {
         const long long w = env_int("SKL_SKETCH_BATCH_WORDS", 0);   // 0 or unset: 8 Mi; any other value: at least 1
         k.sketch_batch_words = w == 0 ? 0 : std::max(1ll, w);

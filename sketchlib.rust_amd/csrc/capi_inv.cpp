@@ -1,6 +1,6 @@
 // capi_inv.cpp -- the entry points of include/sketchlib_dist.h for `inverted query`: a device-resident
-// index of u16 index sketches (skl_inverted) and the query against it (src/inverted.rs:229-269).
-// Kernels: inv_query.hip.
+// index of u16 index sketches (skl_inverted), the query against it (src/inverted.rs:229-269) and its best hits
+// (src/lib.rs:1019-1109).  Kernels: inv_query.hip, inv_top.hip.
 #include "capi_internal.hpp"
 
 #include <algorithm>
@@ -153,6 +153,74 @@ extern "C" int skl_inverted_query(skl_ctx *ctx, const skl_inverted *ix, const ui
         a.n_words64 = n_words64;
         HIP_TRY(launch_inv_query(a, ctx->stream));
         HIP_TRY(hipMemcpyAsync((char *)out + q0 * out_row, d_out.p, nq * out_row, hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(hipStreamSynchronize(ctx->stream));
+    }
+    return SKL_OK;
+}
+
+// The best hits of every query: the counts band of match-count mode stays on the device, inv_top.hip selects behind it on
+// the same stream, and top ids + top counts per query come back.
+extern "C" int skl_inverted_query_top(skl_ctx *ctx, const skl_inverted *ix, const uint16_t *query_bins, size_t n_queries,
+                                      size_t top, uint32_t *out_ids, uint32_t *out_counts)
+{
+    const RoctxRange range_("skl:inverted query top");
+    SKL_TRY(ctx_bind(ctx));
+    if (!ix) return fail(SKL_ERR_INVALID_ARG, "null index");
+    if (top == 0 || top > SKL_INVQ_TOP_MAX) {
+        return fail(SKL_ERR_INVALID_ARG, "top = %zu: 1 to %d hits per query (SKL_INVQ_TOP_MAX)", top, SKL_INVQ_TOP_MAX);
+    }
+    static_assert(SKL_INVQ_TOP_MAX == INV_TOP_MAX, "the public limit is the plan's");
+    if (ix->device != ctx->device) return fail(SKL_ERR_INVALID_ARG, "index and context are on different devices");
+    if (n_queries == 0) return SKL_OK;
+    if (!query_bins || !out_ids || !out_counts) return fail(SKL_ERR_INVALID_ARG, "null argument");
+    const size_t n = ix->n, S = ix->sketch_size, W = ix->words;
+    if (n == 0) {
+        std::fill(out_ids, out_ids + n_queries * top, INV_TOP_PAD_ID);
+        std::fill(out_counts, out_counts + n_queries * top, 0u);
+        return SKL_OK;
+    }
+    const size_t band = std::min(n_queries, skl_inverted_band_queries(ctx, ix, SKL_INVQ_MATCH_COUNT));
+    const size_t band_pad = (band + IQ_QTILE - 1) / IQ_QTILE * IQ_QTILE;
+    DevBuf d_qplanes, d_counts, d_hits;
+    HIP_TRY(hipMalloc(&d_qplanes.p, W * band_pad * 16 * sizeof(uint32_t)));
+    HIP_TRY(hipMalloc(&d_counts.p, band * n * sizeof(uint32_t)));
+    HIP_TRY(hipMalloc(&d_hits.p, 2 * band * top * sizeof(uint32_t)));   // the band's ids, then its counts
+    InvTopArgs t;
+    memset(&t, 0, sizeof t);
+    t.counts = (const uint32_t *)d_counts.p;
+    t.n = (uint32_t)n;
+    t.top = (uint32_t)top;
+    t.n_eff = inv_top_n_eff(t.top, t.n);
+    t.digit_bits = inv_top_digit_bits(ctx->knobs.invq_top_digit_bits);
+    t.digits = inv_top_digits((uint32_t)S, t.digit_bits);
+    t.list_len = inv_top_list_len(t.n_eff);
+    for (size_t q0 = 0; q0 < n_queries; q0 += band) {
+        const size_t nq = std::min(band, n_queries - q0);
+        const size_t nq_pad = (nq + IQ_QTILE - 1) / IQ_QTILE * IQ_QTILE;
+        HIP_TRY(hipMemsetAsync(d_qplanes.p, 0, W * nq_pad * 16 * sizeof(uint32_t), ctx->stream));
+        SKL_TRY(upload_planes(ctx, query_bins + q0 * S, nq, S, W, 16, 16ull * nq_pad, 1, (uint32_t *)d_qplanes.p));
+        InvQueryArgs a;
+        memset(&a, 0, sizeof a);
+        a.ref_planes = ix->d_planes;
+        a.q_planes = (const uint32_t *)d_qplanes.p;
+        a.n = (uint32_t)n;
+        a.nq = (uint32_t)nq;
+        a.nq_pad = (uint32_t)nq_pad;
+        a.words = (uint32_t)W;
+        a.sketch_size = (uint32_t)S;
+        a.tail_mask = tail_mask(S);
+        a.mode = INVQ_COUNTS;
+        a.counts = (uint32_t *)d_counts.p;
+        HIP_TRY(launch_inv_query(a, ctx->stream));
+        t.nq = (uint32_t)nq;
+        t.ids = (uint32_t *)d_hits.p;
+        t.hit_counts = t.ids + nq * top;
+        std::pair<hipEvent_t, hipEvent_t> *ev = timing_slot(ctx);   // (the selection alone, bracketed like the pair kernels: skl_ctx_kernel_ms)
+        if (ev) HIP_TRY(hipEventRecord(ev->first, ctx->stream));
+        HIP_TRY(launch_inv_top(t, ctx->stream));
+        if (ev) HIP_TRY(hipEventRecord(ev->second, ctx->stream));
+        HIP_TRY(hipMemcpyAsync(out_ids + q0 * top, t.ids, nq * top * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(hipMemcpyAsync(out_counts + q0 * top, t.hit_counts, nq * top * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
         HIP_TRY(hipStreamSynchronize(ctx->stream));
     }
     return SKL_OK;

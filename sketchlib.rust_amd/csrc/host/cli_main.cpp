@@ -829,6 +829,9 @@ int run_append(int argc, char **argv, int first, bool verbose, bool quiet)
 // (sketch_inverted_gpu) -- then matched against every indexed sample on the GPU (skl_inverted_query, csrc/inv_query.hip), one band of
 // queries at a time: band i + 1 computes while band i is formatted on --threads threads and written.  Rows come in
 // input order (the reference's come in whatever order its threads finish).
+// --top N (match-count only): the N best hits of every query instead of every count -- the reference's identification
+// query (SketchlibData::query / get_probs, src/lib.rs:1019-1109), selected on the device (skl_inverted_query_top,
+// csrc/inv_top.hip) -- in long form, one line per hit with d / (2 S - d) and the index's label and metadata.
 int run_inverted_query(int argc, char **argv, int first, bool verbose, bool quiet)
 {
     g_usage = "sketchlib inverted query [OPTIONS] <SKI> <SEQ_FILES|-f <FILE_LIST>>";
@@ -841,6 +844,8 @@ int run_inverted_query(int argc, char **argv, int first, bool verbose, bool quie
     bool gpu_sketch = false;
     uint16_t min_count = 5;   // DEFAULT_MINCOUNT / DEFAULT_MINQUAL, cli.rs:12-15 (read sets only)
     uint8_t min_qual = 20;
+    size_t top = 0;           // --top N: 0 = every count (the default)
+    bool query_type_given = false;
     for (int i = first; i < argc; ++i) {
         const std::string arg = argv[i];
         auto value = [&](const std::string &flag) -> std::string {
@@ -851,7 +856,15 @@ int run_inverted_query(int argc, char **argv, int first, bool verbose, bool quie
         else if (arg == "--quiet") quiet = true;
         else if (arg == "-f") file_list = value("-f <FILE_LIST>");
         else if (arg == "-o") output = value("-o <OUTPUT>");
+        else if (arg == "--top") {
+            const std::string v = value("--top <N>");
+            top = parse_usize("--top <N>", v);
+            if (top == 0 || top > SKL_INVQ_TOP_MAX || v.size() > 20) {   // the hits of a query are held in the kernel's LDS list
+                usage_error("invalid value '" + v + "' for '--top <N>': " + v + " is not in 1..=" + std::to_string(SKL_INVQ_TOP_MAX));
+            }
+        }
         else if (arg == "--query-type") {
+            query_type_given = true;
             mode_name = value("--query-type <QUERY_TYPE>");
             if (mode_name == "match-count") mode = SKL_INVQ_MATCH_COUNT;
             else if (mode_name == "all-bins") mode = SKL_INVQ_ALL_BINS;
@@ -866,6 +879,9 @@ int run_inverted_query(int argc, char **argv, int first, bool verbose, bool quie
         else if (arg.size() > 1 && arg[0] == '-') usage_error("unexpected argument '" + arg + "' found");
         else if (!ski) ski = arg;
         else seq_files.push_back(arg);
+    }
+    if (top && query_type_given && mode != SKL_INVQ_MATCH_COUNT) {
+        usage_error("the argument '--top <N>' cannot be used with '--query-type <QUERY_TYPE>'");
     }
     if (!ski) usage_error("the following required arguments were not provided:\n  <SKI>");
     if (seq_files.empty() == !file_list.has_value()) {
@@ -955,7 +971,9 @@ int run_inverted_query(int argc, char **argv, int first, bool verbose, bool quie
     log.info("Running queries in mode: " + mode_name);
     {
         std::string header = "Query";
-        if (mode == SKL_INVQ_MATCH_COUNT) {
+        if (top) {
+            header += "\tSample\tMatches\tJaccard\tLabel\tMetadata";
+        } else if (mode == SKL_INVQ_MATCH_COUNT) {
             for (const auto &name : inv.sample_names) header += "\t" + name;
         } else {
             header += "\tMatches";
@@ -964,14 +982,16 @@ int run_inverted_query(int argc, char **argv, int first, bool verbose, bool quie
     }
     // bands of queries: 256 MB of results on the host at a time (at least one query)
     const size_t words64 = (n + 63) / 64;
-    const size_t row_bytes = std::max<size_t>(1, mode == SKL_INVQ_MATCH_COUNT ? n * sizeof(uint32_t) : words64 * sizeof(uint64_t));
+    // (--top: a band's ids [rows][top], then its counts [rows][top])
+    const size_t row_bytes = std::max<size_t>(1, top ? top * 2 * sizeof(uint32_t) : mode == SKL_INVQ_MATCH_COUNT ? n * sizeof(uint32_t) : words64 * sizeof(uint64_t));
     const size_t band = std::max<size_t>(1, std::min<size_t>(nq, (256ull << 20) / row_bytes));
     auto compute = [&](size_t q0) {
         const size_t rows = std::min(band, nq - q0);
         std::vector<uint64_t> buf((rows * row_bytes + 7) / 8);
-        if (skl_inverted_query(dev.ctx(), ix, query_bins.data() + q0 * S, rows, mode, buf.data()) != SKL_OK) {
-            throw std::runtime_error(skl_last_error());
-        }
+        uint32_t *hits = reinterpret_cast<uint32_t *>(buf.data());
+        const int rc = top ? skl_inverted_query_top(dev.ctx(), ix, query_bins.data() + q0 * S, rows, top, hits, hits + rows * top)
+                           : skl_inverted_query(dev.ctx(), ix, query_bins.data() + q0 * S, rows, mode, buf.data());
+        if (rc != SKL_OK) throw std::runtime_error(skl_last_error());
         return buf;
     };
     double t_query = 0, t_write = 0;
@@ -990,6 +1010,28 @@ int run_inverted_query(int argc, char **argv, int first, bool verbose, bool quie
             std::string &o = pieces[piece];
             char num[16];
             for (size_t r = rows * piece / n_pieces; r < rows * (piece + 1) / n_pieces; ++r) {
+                if (top) {   // one line per hit, best first; fewer than `top` lines when the index is smaller
+                    const uint32_t *ids = reinterpret_cast<const uint32_t *>(buf.data()) + r * top, *cnt = ids + rows * top;
+                    char jac[40];
+                    for (size_t h = 0; h < std::min(top, n); ++h) {
+                        const uint32_t s = ids[h], c = cnt[h];
+                        o += inputs[q0 + r].first;
+                        o += '\t';
+                        o += inv.sample_names[s];
+                        num[0] = '\t';
+                        o.append(num, std::to_chars(num + 1, num + sizeof num, c).ptr);
+                        o += '\t';
+                        // lib.rs:1049: d / (2 S - d) in f64, shortest digits that read back as the same value
+                        const double j = (double)c / (2.0 * (double)S - (double)c);
+                        o.append(jac, std::to_chars(jac, jac + sizeof jac, j, std::chars_format::fixed).ptr);
+                        o += '\t';
+                        if (inv.labels) o += (*inv.labels)[s];
+                        o += '\t';
+                        if (inv.metadata) o += (*inv.metadata)[s];
+                        o += '\n';
+                    }
+                    continue;
+                }
                 o += inputs[q0 + r].first;
                 if (mode == SKL_INVQ_MATCH_COUNT) {
                     const uint32_t *c = reinterpret_cast<const uint32_t *>(buf.data()) + r * n;

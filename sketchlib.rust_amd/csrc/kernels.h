@@ -13,6 +13,7 @@
 #include "aa_plan.hpp"      // the amino-acid sketching call's work plan and locators
 #include "finish_plan.hpp"  // device-side densify + transpose: launch rules, flag bits, the shared target rule
 #include "work_map.hpp"     // which workgroup computes what: TILE_PREFIX_INLINE, the fields below it reads and plans
+#include "inv_top_plan.hpp" // best hits of an inverted query: digits, list length, LDS bytes, the descending walk
 
 namespace skl {
 
@@ -630,6 +631,16 @@ struct InvQueryArgs {
 };
 hipError_t launch_inv_planes(const InvPlanesArgs &a, hipStream_t stream);
 hipError_t launch_inv_query(const InvQueryArgs &a, hipStream_t stream);
+// inv_top.hip: per query the n_eff = min(top, n) largest keys (count << 32) | index of a counts band, descending; every
+// number below but the pointers comes from inv_top_plan.hpp
+struct InvTopArgs {
+    const uint32_t *counts;       // [nq][n]: inv_query_kernel's INVQ_COUNTS output (16-byte aligned base)
+    uint32_t n, nq, top, n_eff;
+    uint32_t digit_bits, digits;  // inv_top_digit_bits(knob), inv_top_digits(sketch_size, digit_bits)
+    uint32_t list_len;            // inv_top_list_len(n_eff)
+    uint32_t *ids, *hit_counts;   // [nq][top]; entries past n_eff: INV_TOP_PAD_ID, 0
+};
+hipError_t launch_inv_top(const InvTopArgs &a, hipStream_t stream);
 
 // skl_sketches_select (slab_ops.hip): whole sample rows of a row slab gathered by index into another row slab.
 // dst row r = src row ids[r]; a row is row_vec 16-byte words (nk * sketchsize64 * 112 B is always a multiple of 16).

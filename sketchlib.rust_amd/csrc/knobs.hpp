@@ -3,8 +3,8 @@
 #pragma once
 
 // Environment switches.  They are read ONCE, when a context is created (skl_ctx_create), never on
-// the launch path.  The product library READS fifteen of them (capi.cpp read_knobs: timing cadence, topology,
-// the knobs that force the banded / sliced / 32-row forms on small test inputs, the inverted query's band budget, the sketching calls' batch sizes and form threshold, where and how far their streams are finished, the pair list's band); every "A/B only, results
+// the launch path.  The product library READS sixteen of them (capi.cpp read_knobs: timing cadence, topology,
+// the knobs that force the banded / sliced / 32-row forms on small test inputs, the inverted query's band budget and the digit width of its best-hit selection, the sketching calls' batch sizes and form threshold, where and how far their streams are finished, the pair list's band); every "A/B only, results
 // identical" switch below keeps its default there and is read by the A/B build alone (-DSKL_AB), as are kernel
 // selection, tile shapes and the timing-only ablations.
 struct Knobs {
@@ -12,6 +12,7 @@ struct Knobs {
     long long sliced_max_pairs = -1;  // SKL_SLICED_MAX_PAIRS: core/acc launches below this run k-sliced (-1: default)
     long long knn_band_rows = 0;      // SKL_KNN_BAND_ROWS: force the band height of the kNN drivers (tests)
     long long invq_band_bytes = 0;    // SKL_INVQ_BAND_BYTES: device memory per query band of skl_inverted_query (0: 1 GiB; tests force it low)
+    long long invq_top_digit_bits = 0; // SKL_INVQ_TOP_DIGIT_BITS: bits per digit of skl_inverted_query_top's radix select (1..11; 0: 11, inv_top_plan.hpp; tests force several passes at small sketch sizes)
     long long sketch_batch_words = 0; // SKL_SKETCH_BATCH_WORDS: packed words (16 bases each) from which skl_sketch_signs closes an upload batch of whole samples (0: 8 Mi; tests force it low)
     long long aa_batch_sign_bytes = 0; // SKL_AA_BATCH_SIGN_BYTES: bytes of signs from which skl_sketch_signs_aa closes a batch of whole samples (0: 256 MiB; tests force it low)
     long long aa_long_min = 0;        // SKL_AA_LONG_MIN: residues from which a sample takes the staged form of skl_sketch_signs_aa (0: 8 192; tests force 1: every sample staged)
