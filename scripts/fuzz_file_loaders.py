@@ -7,10 +7,10 @@ fed to `sketchlib inverted precluster --count`, `skl_dbtool info` and (the .skm,
 exit (sanitizer report, signal, time-out) is printed.
 
 Build the two sanitised binaries first (from sketchlib.rust_amd/csrc):
-  g++ -O1 -g -std=c++17 -fsanitize=address,undefined -fno-sanitize-recover=undefined host/*.cpp -I../../include \
+  g++ -O1 -g -std=c++17 -fsanitize=address,undefined -fno-sanitize-recover=undefined host/*.cpp host/cli/*.cpp -I../../include \
       -L_build -lsketchlib_dist_hip -lpthread -lz -o /tmp/sketchlib_asan
   g++ -O1 -g -std=c++17 -fsanitize=address,undefined -fno-sanitize-recover=undefined tools/dbtool_main.cpp \
-      $(ls host/*.cpp | grep -v -e cli_main -e distances.cpp -e sketch_gpu) -lpthread -lz -o /tmp/dbtool_asan
+      $(ls host/*.cpp | grep -v -e distances.cpp -e sketch_gpu) -lpthread -lz -o /tmp/dbtool_asan
 usage: fuzz_file_loaders.py [seed] [rounds]     (run from the repository root)
 Round 1 of this found: an indefinite-length CBOR string read past the end of the input, a string
 length that overflowed the bounds check, bitmaps naming samples beyond n_samples (out-of-bounds

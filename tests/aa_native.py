@@ -10,9 +10,9 @@ from conftest import ROOT
 
 SRC = os.path.join(ROOT, "tests", "native", "aa_check.cpp")
 HOST = os.path.join(ROOT, "sketchlib.rust_amd", "csrc", "host")
-# the host layer without the CLI and the two files that call the GPU library (the Makefile's HOST_LIB_SRC)
+# the host layer (the CLI lies in host/cli/) without the two files that call the GPU library (the Makefile's HOST_LIB_SRC)
 HOST_SRC = sorted(f for f in glob.glob(os.path.join(HOST, "*.cpp"))
-                  if os.path.basename(f) not in ("cli_main.cpp", "distances.cpp", "sketch_gpu.cpp"))
+                  if os.path.basename(f) not in ("distances.cpp", "sketch_gpu.cpp"))
 _DIR = tempfile.TemporaryDirectory(prefix="aa_check_")
 
 

@@ -136,9 +136,22 @@ def test_unmatched_host_log_is_reported_through_ctx_flags():
             assert v in ("0", "1") and f == "0"
     # the product library has no such switch
     assert b"SKL_FORCE_LOG_VARIANT" not in open(pkg.library_path(), "rb").read()
-    # and the CLI warns once when a completeness correction meets the flag
-    cli = open(os.path.join(ROOT, "sketchlib.rust_amd", "csrc", "host", "cli_main.cpp")).read()
-    assert cli.count("SKL_CTX_FLAG_LOG_UNMATCHED)) log.warn(LOG_UNMATCHED_WARNING)") == 2
+    # and the CLI warns once when a completeness correction meets the flag.  The form checked: ONE shared helper, defined
+    # once (host/cli/common.cpp: the flag test and the warning), called from exactly the two command files whose commands
+    # take a completeness correction -- dist.cpp (`dist`) and inverted.cpp (`inverted precluster`), once each, under the
+    # condition that a completeness file was given -- and the flag and the warning text are used nowhere else.
+    cli_dir = os.path.join(ROOT, "sketchlib.rust_amd", "csrc", "host", "cli")
+    cli = {f: open(os.path.join(cli_dir, f)).read() for f in sorted(os.listdir(cli_dir))}
+    assert cli["common.cpp"].count("if (skl_ctx_flags(ctx) & SKL_CTX_FLAG_LOG_UNMATCHED) log.warn(LOG_UNMATCHED_WARNING);") == 1
+    assert {f: s.count("SKL_CTX_FLAG_LOG_UNMATCHED") for f, s in cli.items() if "SKL_CTX_FLAG_LOG_UNMATCHED" in s} == \
+        {"common.cpp": 1, "common.hpp": 1}            # (the header: a comment)
+    assert {f: s.count("log.warn(LOG_UNMATCHED_WARNING)") for f, s in cli.items() if "log.warn(LOG_UNMATCHED_WARNING)" in s} == {"common.cpp": 1}
+    calls = {f: s.count("warn_if_log_unmatched(") for f, s in cli.items() if "warn_if_log_unmatched(" in s}
+    assert calls == {"common.hpp": 1, "common.cpp": 1, "dist.cpp": 1, "inverted.cpp": 1}, calls
+    assert "if (ref_comp || query_comp) warn_if_log_unmatched(log, dev[0].ctx());" in cli["dist.cpp"]
+    assert "if (comp) warn_if_log_unmatched(log, dev.ctx());" in cli["inverted.cpp"]
+    precluster = cli["inverted.cpp"].split("int run_inverted_precluster(")[1]
+    assert "warn_if_log_unmatched(" in precluster
 
 
 def _kernel_metadata(lib_path):
