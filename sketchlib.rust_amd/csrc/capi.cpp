@@ -363,8 +363,8 @@ static long long env_int(const char *name, long long dflt)
 Knobs read_knobs()
 {
     Knobs k;
-    // The product library reads ELEVEN switches: the timing cadence, the device topology the tile order assumes, and the knobs
-    // with which the tests force the banded / sliced / 32-row forms (and the inverted query's bands, the sketching call's upload batches, where and how far its streams are finished, the pair list's bands) on inputs small enough for the oracle.  Everything that
+    // The product library reads SEVENTEEN switches: the timing cadence, the device topology the tile order assumes, and the knobs
+    // with which the tests force the banded / sliced / 32-row / striped forms (and the inverted query's bands, the sketching call's upload batches, where and how far its streams are finished, the pair list's bands) on inputs small enough for the oracle.  Everything that
     // exists only to time one form against another ("A/B only, results identical") is read by the A/B build alone (-DSKL_AB),
     // where scripts/ab_sweep.py, scripts/forced_switch_suites.sh and the tests marked `ab_library` find it.
     k.timing_every = std::max(0ll, env_int("SKL_TIMING_EVERY", 0));
@@ -389,6 +389,7 @@ Knobs read_knobs()
     k.tile32_min = env_int("SKL_TILE32_MIN", 8ll << 20);
     k.group_span = (int)std::min(64ll, std::max(1ll, env_int("SKL_GROUP_SPAN", 2)));
     k.xcds = (int)std::min(8ll, std::max(0ll, env_int("SKL_XCDS", 0)));
+    k.eb_stripes = (int)std::min(1ll, std::max(-1ll, env_int("SKL_EB_STRIPES", -1)));
 #ifdef SKL_AB
     k.k_slices = (int)env_int("SKL_K_SLICES", 0);
     k.round_priority = env_int("SKL_ROUND_PRIORITY", 1) != 0;
@@ -1234,6 +1235,7 @@ static int run_counts_epilogue(skl_ctx *ctx, const skl_sketches *rows, const skl
     e.lean = L.lean ? 1u : 0u;
     e.comp_lean = L.comp_lean ? 1u : 0u;
     e.lds_rows = L.lds_rows ? 1u : 0u;
+    e.striped = L.striped ? 1u : 0u;
     e.ytab = rows->d_ytab;
     e.tolerance = g.tolerance;
     e.kf = rows->d_kf;
@@ -1250,6 +1252,7 @@ static int run_counts_epilogue(skl_ctx *ctx, const skl_sketches *rows, const skl
     {
         if (coreacc_epilogue_is_lean(e)) ctx->last_kernel += e.cnt_u16 ? " [lean epilogue]" : " [lean epilogue, sliced counts]";
         if (coreacc_epilogue_stages_rows(e)) ctx->last_kernel += " [row slices staged in LDS]";
+        if (coreacc_epilogue_is_striped(e)) ctx->last_kernel += " [column stripes folded onto the XCDs]";
         HIP_TRY(launch_coreacc_epilogue_r6(e, epi_stream));
     }
     if (slot.overlapped) HIP_TRY(hipEventRecord(ctx->eb_events[2 + slot.buf], epi_stream));

@@ -15,6 +15,7 @@
 #include <string>
 #include <vector>
 
+#include "eb_stripes.hpp"
 #include "knobs.hpp"
 
 namespace skl {
@@ -180,6 +181,41 @@ inline CountsBasics counts_basics(const DenseCall &c, uint64_t pairs)
     return b;
 }
 
+// XCDs the device presents as one: an MI355X XCD has 32 CUs, so an unpartitioned (SPX) part shows 256 CUs = 8 XCDs, a CPX
+// partition 32 CUs = 1.  The tile order deals workgroups to XCDs by blockIdx mod that number; SKL_XCDS forces it (tests).
+inline uint32_t plan_xcd_shift(int n_cu, int knob_xcds)
+{
+    int x = knob_xcds > 0 ? knob_xcds : n_cu / 32;
+    uint32_t shift = 0;
+    while (shift < 3u && (2 << shift) <= x) ++shift;
+    return shift;
+}
+
+// STRIPED EPILOGUE ORDER (eb_stripes.hpp): the early break's epilogue walks a SMALL launch in column stripes folded onto the
+// XCDs, so that an XCD is asked for its two stripes' column slices only and serves its completions from its own L2 -- in
+// the flat order every XCD is asked for every column slice of a length (cfg 2: 7 MB against a 4 MB L2).  Taken where the lean
+// kernel takes the launch with its rows staged (`lds_rows`: from 3 % of the sampled pairs still in the running), the order
+// is not the blocked one, there is more than one XCD, the two stripes' slices of one length are within STRIPES_L2_BYTES and
+// the heaviest XCD holds at most STRIPES_MAX_IMBALANCE x the mean number of pairs.  SKL_EB_STRIPES=0 / 1: never / wherever the
+// lean kernel stages its rows (tests).
+// Measured (profiles/r08_cfg2_epilogue_stripes.md; Set U, 4 096 bins, 4.8 % still in the running, ms per call flat -> striped):
+//   the bytes    n = 1 000 / 2 000 / 3 000 / 4 000 / 5 000 / 8 000 = 0.9 / 1.8 / 2.75 / 3.7 / 4.6 / 7.3 MB of slices per XCD and length:
+//                0.0997 -> 0.0935, 0.328 -> 0.292, 0.692 -> 0.591, 1.186 -> 1.033, 1.84 -> 1.59, 4.6 -> 4.2: the order pays past the 4 MB
+//                of an L2 too (an XCD still reads an eighth of the distinct bytes); 8 MiB is the largest size measured, and from
+//                48 Mi pairs the blocked order takes over anyway
+//   the balance  n = 2 000 / 1 900 / 1 800 / 1 500 = 1.05 / 1.16 / 1.29 / 1.86 x the mean: -11 %, -8 %, -6 %, +5 %: taken up to 1.3
+constexpr uint64_t STRIPES_L2_BYTES = 8ull << 20;
+constexpr double STRIPES_MAX_IMBALANCE = 1.3;
+inline bool counts_striped(const DenseCall &c, const CountsBasics &b, bool lean, bool lds_rows, uint64_t r0, uint64_t r1)
+{
+    if (c.knobs.eb_stripes == 0 || !b.early || b.blocked || !b.lean_like || !lean || !lds_rows) return false;
+    if (c.ss64 * 224ull > 16384ull) return false;   // (the two rows do not fit the LDS the launch may ask for: nothing is staged)
+    if (c.knobs.eb_stripes > 0) return true;
+    const uint32_t xs = plan_xcd_shift(c.n_cu, c.knobs.xcds);
+    return xs > 0u && eb_stripe_slice_bytes(c.n_cols, xs, c.ss64) <= STRIPES_L2_BYTES &&
+           eb_stripe_imbalance(c.self_mode, c.n_cols, r0, r1, xs) <= STRIPES_MAX_IMBALANCE;
+}
+
 // Rows [r0, r1) cut into n_bands bands of (nearly) equal pair count: cuts[0] = r0 < ... < cuts.back() = r1, every band at
 // least one row (so there may be fewer bands than asked for).
 inline std::vector<uint64_t> cut_row_bands(const DenseCall &c, uint64_t n_bands)
@@ -276,6 +312,7 @@ struct CountsLaunch {
     // the early break's epilogue
     bool blocked = false;                  // order: in blocks kept on one XCD each (false: flat)
     bool lean = true, ahead = true, lds_rows = false, comp_lean = false;
+    bool striped = false;                  // order: column stripes folded onto the XCDs (counts_striped)
     // A/B build: the plain k-sliced launch may finish its pairs itself (the executor still asks the kernel whether it takes the
     // launch) / round 5's epilogue is asked for
     bool fuse_epilogue = false, epilogue_r5 = false;
@@ -339,20 +376,11 @@ inline CountsLaunch plan_counts_launch(const DenseCall &c, uint64_t r0, uint64_t
     L.ahead = c.knobs.eb_ahead;
     L.lean = c.knobs.eb_lean;
     L.comp_lean = c.has_comp && c.comp_unit;
+    L.striped = counts_striped(c, b, L.lean, L.lds_rows, r0, r1);
     L.fuse_epilogue = b.sliced && !b.early && L.k_slices == 1u && !L.two_planes && c.knobs.fuse_epilogue && c.forced_kernel == 0 &&
                       c.ss64 <= PLAN_MAX_U16_CHUNKS;
     L.epilogue_r5 = c.knobs.epilogue_r5 && !b.mixed && !(b.early && (c.has_comp || c.ss64 > PLAN_MAX_U16_CHUNKS));
     return L;
-}
-
-// XCDs the device presents as one: an MI355X XCD has 32 CUs, so an unpartitioned (SPX) part shows 256 CUs = 8 XCDs, a CPX
-// partition 32 CUs = 1.  The tile order deals workgroups to XCDs by blockIdx mod that number; SKL_XCDS forces it (tests).
-inline uint32_t plan_xcd_shift(int n_cu, int knob_xcds)
-{
-    int x = knob_xcds > 0 ? knob_xcds : n_cu / 32;
-    uint32_t shift = 0;
-    while (shift < 3u && (2 << shift) <= x) ++shift;
-    return shift;
 }
 
 // ONE LAUNCH OF THE PAIR KERNEL: its tile shape and form.  Product library: the chunk-split kernel (pair_kslice.hip: 16 x 128

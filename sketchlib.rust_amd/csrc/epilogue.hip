@@ -28,6 +28,7 @@
 //
 // Order of the file: constants, helpers, the two dense kernels, the kNN bands' kernel, the sampling kernel, launchers.
 #include "device_common.hpp"
+#include "eb_stripes.hpp"
 
 #include <algorithm>
 
@@ -171,6 +172,12 @@ __device__ __forceinline__ uint32_t eb_same_bins(const uint64_t *rows_ref, const
 // row later and every completion is a 7 KB gather from HBM.  Here the block's 256 column slices (1.8 MB at 4 096 bins) stay in
 // that XCD's 4 MB L2 while the block's rows pass.  Lanes without a pair shadow pair 0 and store nothing; a workgroup without
 // a pair leaves (workgroup-uniform).
+//
+// STRIPED ORDER (small launches the lean kernel takes with its rows staged; eb_stripes.hpp): the columns in 2 X stripes, XCD x
+// owns stripes x and 2 X - 1 - x and is asked for their slices alone -- in the flat order every XCD is asked for every column
+// slice of a length, 7 MB against a 4 MB L2 at cfg 2.  A workgroup = two rows x one 64-column block of each of its XCD's
+// stripes; (i, j) are known from the start.  Lanes without a pair shadow pair 0 and store nothing (a wave of them completes
+// nothing); a workgroup without a pair leaves before it stages anything.
 struct EbPairLoc {
     uint32_t i = 0, j = 0;      // the pair, where have_ij
     uint64_t p;                 // its index in the launch's counts and output
@@ -200,6 +207,21 @@ struct EbPairLoc {
             in_range = j < g.nB_cols && (!g.self_mode || j > i);
             have_ij = true;
             p = in_range ? (g.self_mode ? square_to_condensed_dev(i, j, g.n_total) : (uint64_t)i * g.nB_cols + j) - g.out_base : 0ull;
+        } else if (g.striped) {
+            const EbStripeWg w = eb_stripe_wg(g, blockIdx.x + g.wg_base);   // (wg_base: a multiple of the XCDs)
+            if (w.none) {
+                leaves = true;
+                return;
+            }
+            in_range = eb_stripe_pair(g, w, threadIdx.x, i, j);
+            have_ij = true;
+            p = in_range ? (g.self_mode ? square_to_condensed_dev(i, j, g.n_total) : (uint64_t)i * g.nB_cols + j) - g.out_base : 0ull;
+            if (!in_range) {   // (a lane without a pair is never looked up by its (i, j): kept inside both slabs all the same)
+                i = w.i0;
+                j = min(j, g.nB_cols - 1u);
+            }
+            i_wg = w.i0;
+            have_wg = true;
         } else {
             const uint64_t p_raw = ((uint64_t)blockIdx.x + g.wg_base) * blockDim.x + threadIdx.x;
             if (p_raw >= g.n_pairs && !stay) {
@@ -1066,6 +1088,13 @@ bool coreacc_epilogue_stages_rows(const EpilogueArgs &a)
     return eb_is_early(a) && a.block_ke == nullptr && a.ss64 * 224ull <= 16384ull && a.lds_rows != 0u;
 }
 
+// does that launch walk its pairs in the striped order (eb_stripes.hpp)?  Asked for, and the lean kernel stages its rows: the
+// flat order otherwise
+bool coreacc_epilogue_is_striped(const EpilogueArgs &a)
+{
+    return a.striped != 0u && a.blocked == 0u && coreacc_epilogue_is_lean(a) && coreacc_epilogue_stages_rows(a);
+}
+
 namespace {
 
 using EpilogueKernel = void (*)(const EpilogueArgs);
@@ -1104,6 +1133,11 @@ hipError_t launch_coreacc_epilogue_r6(const EpilogueArgs &args, hipStream_t stre
         const uint64_t n_xcd = 1ull << a.xcd_shift;
         const uint64_t per_xcd = ((uint64_t)a.blk_rb * a.blk_cb + n_xcd - 1) / n_xcd;
         blocks = (per_xcd * br) << a.xcd_shift;
+        if (blocks >= (1ull << 32)) return hipErrorInvalidValue;
+    }
+    a.striped = coreacc_epilogue_is_striped(a) ? 1u : 0u;
+    if (a.striped) {   // the same number of workgroups on every XCD: (row pair, 64-column block of a stripe) slots
+        blocks = plan_eb_stripes(a);
         if (blocks >= (1ull << 32)) return hipErrorInvalidValue;
     }
     const size_t lds = coreacc_epilogue_stages_rows(a) ? (size_t)a.ss64 * 224u : 0u;

@@ -236,6 +236,10 @@ struct EpilogueArgs {
     uint32_t blocked, row_end, xcd_shift, blk_rb, blk_cb;
     uint32_t blk_row_shift;     // log2 of the rows per block (out of 5 ... 12: 10)
     uint32_t blk_cb0, wg_base;  // (launcher) first column block that holds a pair; workgroup offset of this launch (a launch carries < 2^32 work-items)
+    // STRIPED ORDER (eb_stripes.hpp; small launches the lean kernel takes with its rows staged): the columns in 2 X stripes, XCD x
+    // owns stripes x and 2 X - 1 - x, a workgroup = two rows x one 64-column block of each.  striped: asked for by the host (the
+    // launcher drops it where the lean kernel does not stage rows); stripe_w / stripe_rp: set by the launcher
+    uint32_t striped, stripe_w, stripe_rp;
     uint32_t comp_lean;         // 1: both completeness vectors lie in (0, 1] (checked on the host): the lean form's integer tests hold under the correction
     uint32_t lean;              // 1: launches the lean form can take go to it (epilogue.hip coreacc_epilogue_lean_kernel)
     uint32_t ahead;             // 1: with the row slices in LDS, the first length not counted is completed with the column slices requested a trip ahead
@@ -253,6 +257,7 @@ hipError_t launch_coreacc_epilogue(const EpilogueArgs &args, hipStream_t stream)
 hipError_t launch_coreacc_epilogue_r6(const EpilogueArgs &args, hipStream_t stream);
 bool coreacc_epilogue_is_lean(const EpilogueArgs &args);   // will that launch take the lean kernel?
 bool coreacc_epilogue_stages_rows(const EpilogueArgs &args);   // ... and stage its row slices in LDS?
+bool coreacc_epilogue_is_striped(const EpilogueArgs &args);    // ... in the striped order (args.striped asks for it)?
 // EARLY BREAK in the one-evaluation core/accessory self kNN (capi_knn.cpp): a row band's view of the columns was counted at
 // its first `nk` k-mer lengths (k-major counts, counts[t * n_pairs + row * nB + c]); this launch turns them into the band's
 // (core, acc) records -- completing the pairs still in the running like coreacc_epilogue_kernel -- and does what the fused
