@@ -75,9 +75,86 @@ int main(int argc, char **argv)
         g.tail_resident = (shape == 325 ? 3u : 4u) * 256u / 8u;
         CK(hipMemset(dOut, 0, pairs * nk * 4 * 2));
     }
+    // KT_K=K: the launch counts the first K of the 5 k-mer lengths (an early-break launch; cfg 2: KT_K=2 KT_TAIL=4)
+    if (getenv("KT_K")) {
+        g.k_count = std::min(nk, std::max(1u, (uint32_t)atoi(getenv("KT_K"))));
+        g.cnt_k_stride = pairs;
+    }
+    // KT_COST=1: self-mode tiles dealt to the XCDs by cost, half tiles last (work_map.hpp)
+    if (getenv("KT_COST")) g.tile_cost_order = (uint32_t)atoi(getenv("KT_COST"));
+    // KT_SPAN=S: column groups numbered side by side (the library: 2); KT_INLINE=1: the prefix table in the kernel arguments (the library: 1)
+    if (getenv("KT_SPAN")) g.group_span = (uint32_t)atoi(getenv("KT_SPAN"));
+    if (getenv("KT_INLINE")) g.inline_prefix_ok = (uint32_t)atoi(getenv("KT_INLINE"));
     for (int i = 0; i < warm; ++i) CK(launch_pair_kernel_kslice(g, MODE_COUNTS, shape, true, ablate, ts, 0));
     CK(hipDeviceSynchronize());
     fprintf(stderr, "warm done\n");
+    // KT_ENDS=N: N traced launches back to back with the warm-up; per XCD (workgroup index mod 8) when its last workgroup ends,
+    // counted from the launch's first wave, and what its last 32 workgroups to end were.  One JSON line.
+    if (getenv("KT_ENDS")) {
+        const int reps = std::max(1, atoi(getenv("KT_ENDS")));
+        const int R_ = shape > 1000 ? shape / 100 : shape / 10;
+        PairArgs gp = g;
+        uint64_t n_wg = 0;
+        CK(plan_tiles(gp, R_, 128, ts, 0, &n_wg));
+        if (!plan_kslice_grid(gp, true, true, &n_wg)) { printf("no grid\n"); return 1; }
+        if (n_wg * WAVES_PER_WG * TW > trace_words) { printf("too many waves for the trace buffer\n"); return 1; }
+        struct Wg { double end; uint32_t slot; bool half; };
+        std::vector<uint64_t> tr(n_wg * WAVES_PER_WG * TW);
+        std::vector<std::vector<double>> ends(8);
+        std::vector<double> spread, span_us;
+        double last_half[8] = {}, last_slot_min[8] = {}, xcc_mismatch = 0;
+        for (int rep = 0; rep < reps; ++rep) {
+            CK(launch_pair_kernel_kslice(g, MODE_COUNTS, shape, true, ablate, ts, 0));
+            CK(hipMemcpy(tr.data(), dTrace, tr.size() * 8, hipMemcpyDeviceToHost));
+            uint64_t t0 = ~0ull;
+            for (size_t w = 0; w < n_wg * WAVES_PER_WG; ++w) if (tr[w * TW] != 0) t0 = std::min(t0, tr[w * TW]);
+            std::vector<std::vector<Wg>> per(8);
+            int xcc_of[8] = {-1, -1, -1, -1, -1, -1, -1, -1};
+            for (uint64_t b = 0; b < n_wg; ++b) {
+                uint64_t end = 0;
+                for (int w = 0; w < WAVES_PER_WG; ++w) end = std::max(end, tr[(b * WAVES_PER_WG + w) * TW + 3]);
+                if (end == 0) continue;   // no tile
+                const uint32_t xcd = (uint32_t)b & 7u;
+                const KsliceUnit u = kslice_unit(gp, (uint32_t)(b >> 3), true, true);
+                uint32_t jg = 0, at = 0;
+                const bool ok = gp.tile_cost_order ? lookup_tile_by_cost_at(gp, xcd, u.slot, jg, at) : lookup_tile_at(gp, xcd, u.slot, jg, at);
+                if (!ok) continue;
+                const bool half = tile_skips_block0(1u, gp.row_begin + at * R_, jg * 2u) || tile_skips_block1(jg * 2u, gp.n_jblocks);
+                per[xcd].push_back({(double)(end - t0) / 100.0, u.slot, half});
+                const int xcc = (int)((tr[b * WAVES_PER_WG * TW + 4] >> 32) & 0xF);
+                if (xcc_of[xcd] < 0) xcc_of[xcd] = xcc;
+                else if (xcc_of[xcd] != xcc) xcc_mismatch += 1;
+            }
+            double lo = 1e30, hi = 0;
+            for (int x = 0; x < 8; ++x) {
+                if (per[x].empty()) continue;
+                std::sort(per[x].begin(), per[x].end(), [](const Wg &a, const Wg &b) { return a.end < b.end; });
+                ends[x].push_back(per[x].back().end);
+                lo = std::min(lo, per[x].back().end);
+                hi = std::max(hi, per[x].back().end);
+                const size_t from = per[x].size() > 32 ? per[x].size() - 32 : 0;
+                uint32_t smin = ~0u;
+                for (size_t i = from; i < per[x].size(); ++i) {
+                    last_half[x] += per[x][i].half ? 1.0 : 0.0;
+                    smin = std::min(smin, per[x][i].slot);
+                }
+                last_slot_min[x] += smin;
+            }
+            spread.push_back(hi - lo);
+            span_us.push_back(hi);
+        }
+        auto med = [](std::vector<double> v) { std::sort(v.begin(), v.end()); return v.empty() ? 0.0 : v[v.size() / 2]; };
+        printf("{\"tool\": \"kslice_trace ends\", \"n\": %u, \"k_count\": %u, \"tail_slices\": %u, \"cost_order\": %u, \"launches\": %d, \"workgroups\": %llu, "
+               "\"tiles_per_xcd\": %u, \"last_end_us_median\": %.2f, \"xcd_end_spread_us_median\": %.2f, \"xcc_id_mismatches\": %.0f, \"xcd_end_us_median\": [",
+               n, g.k_count, g.tail_slices, gp.tile_cost_order, reps, (unsigned long long)n_wg, gp.tiles_per_xcd, med(span_us), med(spread), xcc_mismatch);
+        for (int x = 0; x < 8; ++x) printf("%s%.2f", x ? ", " : "", med(ends[x]));
+        printf("], \"half_tile_workgroups_among_last_32_mean\": [");
+        for (int x = 0; x < 8; ++x) printf("%s%.1f", x ? ", " : "", last_half[x] / reps);
+        printf("], \"lowest_tile_slot_among_last_32_mean\": [");
+        for (int x = 0; x < 8; ++x) printf("%s%.1f", x ? ", " : "", last_slot_min[x] / reps);
+        printf("]}\n");
+        return 0;
+    }
     hipEvent_t e0, e1;
     hipEventCreate(&e0); hipEventCreate(&e1);
     hipEventRecord(e0);

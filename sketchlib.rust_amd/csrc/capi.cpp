@@ -363,8 +363,8 @@ static long long env_int(const char *name, long long dflt)
 Knobs read_knobs()
 {
     Knobs k;
-    // The product library reads SEVENTEEN switches: the timing cadence, the device topology the tile order assumes, and the knobs
-    // with which the tests force the banded / sliced / 32-row / striped forms (and the inverted query's bands, the sketching call's upload batches, where and how far its streams are finished, the pair list's bands) on inputs small enough for the oracle.  Everything that
+    // The product library reads EIGHTEEN switches: the timing cadence, the device topology the tile order assumes, and the knobs
+    // with which the tests force the banded / sliced / 32-row / striped / cost-ordered forms (and the inverted query's bands, the sketching call's upload batches, where and how far its streams are finished, the pair list's bands) on inputs small enough for the oracle.  Everything that
     // exists only to time one form against another ("A/B only, results identical") is read by the A/B build alone (-DSKL_AB),
     // where scripts/ab_sweep.py, scripts/forced_switch_suites.sh and the tests marked `ab_library` find it.
     k.timing_every = std::max(0ll, env_int("SKL_TIMING_EVERY", 0));
@@ -390,6 +390,7 @@ Knobs read_knobs()
     k.group_span = (int)std::min(64ll, std::max(1ll, env_int("SKL_GROUP_SPAN", 2)));
     k.xcds = (int)std::min(8ll, std::max(0ll, env_int("SKL_XCDS", 0)));
     k.eb_stripes = (int)std::min(1ll, std::max(-1ll, env_int("SKL_EB_STRIPES", -1)));
+    k.tile_cost_order = (int)std::min(1ll, std::max(-1ll, env_int("SKL_TILE_COST_ORDER", -1)));
 #ifdef SKL_AB
     k.k_slices = (int)env_int("SKL_K_SLICES", 0);
     k.round_priority = env_int("SKL_ROUND_PRIORITY", 1) != 0;
@@ -469,6 +470,7 @@ static hipError_t dispatch_pair_kernel(skl_ctx *ctx, const PairArgs &args_in, in
     a.k_sliced = args.k_sliced != 0;
     a.mid_band = args.mid_band != 0;
     a.tail_slices = args.tail_slices;
+    a.xcd_interleave = args.xcd_interleave != 0;
     a.n_cu = ctx->n_cu;
     a.xcd_shift = args.xcd_shift;
     a.knobs = ctx->knobs;
@@ -485,6 +487,8 @@ static hipError_t dispatch_pair_kernel(skl_ctx *ctx, const PairArgs &args_in, in
     if (args.tail_slices > 1u) args.tail_resident = s.tail_resident;
     const bool kslice = s.try_kslice && kslice_supported(args, mode, s.sliced_launch);
     ctx->last_kernel = pair_kernel_name(s, kslice);
+    args.tile_cost_order = args_in.tile_cost_order != 0u && s.tile_cost_order && kslice ? 1u : 0u;   // (asked for by the dense calls' counts launches alone)
+    if (args.tile_cost_order) ctx->last_kernel += " [tiles dealt by cost, half tiles last]";
     if (kslice) return launch_pair_kernel_kslice(args, mode, s.shape, s.sliced_launch, s.ablate, ctx->tile_scratch, stream);
     return launch_pair_kernel_ksplit(args, mode, s.ksplit_rows, ctx->tile_scratch, stream);
 }
@@ -1170,6 +1174,7 @@ static int run_counts_epilogue(skl_ctx *ctx, const skl_sketches *rows, const skl
         g.slice_chunks = L.slice_chunks;
         g.mid_band = L.mid_band ? 1u : 0u;
     }
+    g.tile_cost_order = 1;   // (a request: plan_pair_shape decides)
     set_rows(&g, c, r0, r1, counts);
     SKL_TRY(ensure_ytab(rows));   // (before the pair launch: nothing may fail between it and the epilogue)
     // FUSED EPILOGUE (round 5): a plain k-sliced launch -- one workgroup per (tile, k-mer length), no chunk slices -- finishes
@@ -1296,6 +1301,7 @@ static int run_direct(skl_ctx *ctx, const skl_sketches *rows, const skl_sketches
 {
     PairArgs g;
     SKL_TRY(fill_args(rows, cols, p, c.mode, jout, &g));
+    g.tile_cost_order = 1;   // (a request: plan_pair_shape takes it for bin-match counts in self mode)
     set_rows(&g, c, r0, r1, dst_dev);
     return timed_pair_launch(ctx, g, c.mode);
 }

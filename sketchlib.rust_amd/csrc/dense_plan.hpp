@@ -396,6 +396,7 @@ struct PairLaunch {
     bool k_sliced = false;      // the caller asks for one workgroup per (tile, k-mer length)
     bool mid_band = false;      // the mid-band rule (plan_counts_launch)
     uint32_t tail_slices = 0;
+    bool xcd_interleave = false;   // the tiles are dealt to the XCDs in blocks of 32 (block-by-block early break)
     int n_cu = 256;
     uint32_t xcd_shift = 3;     // plan_xcd_shift()
     Knobs knobs;
@@ -411,11 +412,29 @@ struct PairShape {
     int ablate = 0;
     uint32_t wg_per_cu = 4, round_size = 0, tail_resident = 0;
     bool no_half_tiles = false;
+    bool tile_cost_order = false;       // self mode: every XCD takes a share of the full tiles, then of the half tiles (work_map.hpp)
     // what the name needs besides
     int mode = PLAN_MODE_COUNTS;
     bool big_sketch = false;
     uint32_t tail_slices = 0;
 };
+// TILES DEALT BY COST (work_map.hpp).  A self-mode launch of 16 x 128 tiles walks half tiles -- 31 of cfg 2's 287 -- and a contiguous
+// eighth of the tile numbering gives one XCD eight of them and another none: blocks of 64 columns walked per XCD 63 ... 72
+// against a mean of 67.9 at n = 1 000, 1.27 x the mean at n = 700.  In the cost order every XCD takes its share of the full
+// tiles and then its share of the half tiles (within one tile of each other in both), so that the XCDs carry the same cost and
+// each ends on its cheapest workgroups.  The form: k-sliced MODE_COUNTS in self mode, half tiles walked, more than one XCD, not
+// the XCD-interleaved order of block-by-block plans.  SKL_TILE_COST_ORDER = 0 / 1: never / wherever the form allows (tests);
+// by rule: launches of up to TILE_COST_MAX_PAIRS pairs -- a few rounds of workgroups, where the last round's make-up and the
+// XCDs' balance are a visible share of the launch (profiles/r09_cfg2_counts_order.md).
+constexpr uint64_t TILE_COST_MAX_PAIRS = 2ull << 20;
+inline bool tile_cost_order_rule(const PairLaunch &a, const PairShape &s, uint64_t pairs)
+{
+    const bool form = a.self_mode && a.mode == PLAN_MODE_COUNTS && s.sliced_launch && s.shape == 165 && !s.no_half_tiles && s.ablate == 0 &&
+                      a.xcd_shift > 0u && !a.xcd_interleave && s.try_kslice && !a.knobs.fuse_epilogue;
+    if (!form || a.knobs.tile_cost_order == 0) return false;
+    return a.knobs.tile_cost_order > 0 || pairs <= TILE_COST_MAX_PAIRS;
+}
+
 inline PairShape plan_pair_shape(const PairLaunch &a)
 {
     PairShape s;
@@ -459,6 +478,7 @@ inline PairShape plan_pair_shape(const PairLaunch &a)
         // kernel without the slices leaves plane 1 as it found it: zero)
         s.tail_resident = s.wg_per_cu * (uint32_t)a.n_cu / n_xcd;
     }
+    s.tile_cost_order = tile_cost_order_rule(a, s, pairs);
     return s;
 }
 

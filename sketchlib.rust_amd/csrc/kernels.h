@@ -96,6 +96,11 @@ struct PairArgs {
     uint32_t round_size;
     uint32_t mid_band;            // host-side request (dense_band): 32 x 128 tiles whatever the launch size
     uint32_t no_half_tiles;       // 1: walk both 64-column blocks of every tile (A/B timing of the half tiles; results identical)
+    // TILES DEALT BY COST (work_map.hpp; self-mode k-sliced MODE_COUNTS launches of 16 x 128 tiles, which walk half tiles): every
+    // XCD takes a share of the full tiles and then a share of the half tiles instead of one contiguous share of all of them.
+    // The shares are closed forms of the two tile counts, so the per-XCD start offsets are computed, not stored.
+    uint32_t tile_cost_order;     // host-side request; the launcher clears it where the form does not allow the order
+    uint32_t n_full_tiles;        // active tiles that walk both blocks (the others: n_active_tiles - n_full_tiles)
     // Symmetric self kNN (pair_kslice.hip: k-sliced MODE_JACCARD and all-k MODE_COREACC): besides
     // out, the record of (row i, column j >= t_col_begin) also goes to record
     // (j - t_col_begin) * t_stride + (i - row_begin) of out_t, i.e. as a candidate of row j.
@@ -162,7 +167,7 @@ struct PairArgs {
     double tolerance;             // ln(2 / (sketch_size * 64))   jaccard.rs:75
     double kf[MAX_FUSED_K];       // k-mer lengths as f64
 };
-static_assert(sizeof(PairArgs) == 528, "PairArgs is the pair kernels' argument: its layout is pinned");
+static_assert(sizeof(PairArgs) == 536,"PairArgs is the pair kernels' argument: its layout is pinned");
 
 // Device buffer the launchers may use for the tile-prefix table (owned by the context).
 struct TileScratch {

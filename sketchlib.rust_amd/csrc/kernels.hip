@@ -32,10 +32,16 @@ hipError_t plan_tiles(PairArgs &args, uint32_t rows_per_tile, uint32_t cols_per_
 {
     plan_tile_geometry(args, rows_per_tile, cols_per_group);
     std::vector<uint32_t> prefix(args.self_mode ? n_supergroups(args) + 1u : 0u);
-    if (!plan_tile_numbering(args, prefix.data(), grid_out)) return hipErrorInvalidValue;
+    if (args.tile_cost_order != 0u && !tile_cost_order_possible(args)) args.tile_cost_order = 0;
+    args.n_full_tiles = 0;
+    if (!(args.tile_cost_order != 0u ? plan_tile_numbering_by_cost(args, prefix.data(), grid_out) : plan_tile_numbering(args, prefix.data(), grid_out))) {
+        return hipErrorInvalidValue;
+    }
     if (args.self_mode) {
+        // (the table of the cost order is the full tiles': n_full_tiles tells the two apart, 0 = the order of all tiles)
         const uint64_t key[4] = {((uint64_t)args.row_begin << 32) | args.row_end, ((uint64_t)args.group_span << 32) | args.nB,
-                                 ((uint64_t)rows_per_tile << 32) | cols_per_group, args.n_active_tiles};
+                                 ((uint64_t)rows_per_tile << 32) | cols_per_group,
+                                 ((uint64_t)(args.tile_cost_order != 0u ? 1u + args.n_full_tiles : 0u) << 32) | args.n_active_tiles};
         if (prefix.size() > scratch.capacity) {
             if (scratch.d_prefix) (void)hipFree(scratch.d_prefix);          // (synchronises the device)
             if (scratch.h_staging) (void)hipHostFree(scratch.h_staging);

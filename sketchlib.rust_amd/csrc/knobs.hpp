@@ -3,8 +3,8 @@
 #pragma once
 
 // Environment switches.  They are read ONCE, when a context is created (skl_ctx_create), never on
-// the launch path.  The product library READS seventeen of them (capi.cpp read_knobs: timing cadence, topology,
-// the knobs that force the banded / sliced / 32-row forms and the striped epilogue order on small test inputs, the inverted query's band budget and the digit width of its best-hit selection, the sketching calls' batch sizes and form threshold, where and how far their streams are finished, the pair list's band); every "A/B only, results
+// the launch path.  The product library READS eighteen of them (capi.cpp read_knobs: timing cadence, topology,
+// the knobs that force the banded / sliced / 32-row forms and the striped epilogue order and the cost order of the tiles on small test inputs, the inverted query's band budget and the digit width of its best-hit selection, the sketching calls' batch sizes and form threshold, where and how far their streams are finished, the pair list's band); every "A/B only, results
 // identical" switch below keeps its default there and is read by the A/B build alone (-DSKL_AB), as are kernel
 // selection, tile shapes and the timing-only ablations.
 struct Knobs {
@@ -22,6 +22,7 @@ struct Knobs {
     int k_slices = 0;                 // SKL_K_SLICES: chunk slices per k of k-sliced core/acc launches (0: chosen per launch)
     int xcds = 0;                       // SKL_XCDS: XCDs the tile order assumes (0: from the device's CU count: 256 CUs = 8, a 32-CU partition = 1)
     int eb_stripes = -1;                // SKL_EB_STRIPES: the early break's epilogue walks the pairs in column stripes folded onto the XCDs (eb_stripes.hpp): -1 by rule (dense_plan.hpp counts_striped), 0 never, 1 wherever the lean kernel stages its rows (tests)
+    int tile_cost_order = -1;           // SKL_TILE_COST_ORDER: self-mode k-sliced counts launches deal their tiles to the XCDs by cost, half tiles last (work_map.hpp): -1 by rule (dense_plan.hpp tile_cost_order_rule), 0 never, 1 wherever the form allows (tests)
     int group_span = 2;                 // SKL_GROUP_SPAN: column groups whose tiles are numbered side by side (work_map.hpp lookup_tile_at)
     long long tile32_min = 8ll << 20;   // SKL_TILE32_MIN: pair x k evaluations from which launches use 32 x 128 tiles (-1: never, 0: always); 8 Mi since the k-sliced 32-row form holds 4 waves per SIMD (profiles/r03_ab_tile32_threshold.jsonl)
     bool mid_band = true;               // SKL_MID_BAND=0: no mid-band rule (32-row tiles + 2 slices of the last round at 0.5-1 x tile32_min evaluations; A/B only, results are identical)

@@ -166,7 +166,13 @@ __global__ __launch_bounds__(LANES *WAVES_PER_WG, OCC != 0 ? OCC : (TIGHT ? (R >
     uint32_t c_begin, c_end;   // chunk range of this workgroup
     slice_chunk_range(g, n_slices, slice, c_begin, c_end);
     uint32_t jg, at;  // column group (JL blocks of 64), row tile
-    if (!lookup_tile_at(g, xcd, slot, jg, at)) return;
+    // (tiles dealt by cost, half tiles last on every XCD: a run-time case of the lookup, in the one form whose launches ask for it)
+    constexpr bool COST_ORDER = KSL && MODE == MODE_COUNTS && R == 16 && JL == 2 && TIGHT && ABL == 0 && !FUSE;
+    if (COST_ORDER && g.tile_cost_order != 0u) {
+        if (!lookup_tile_by_cost_at(g, xcd, slot, jg, at)) return;
+    } else if (!lookup_tile_at(g, xcd, slot, jg, at)) {
+        return;
+    }
     if constexpr ((ABL & 8) != 0) {   // timing only: every workgroup computes tile (0, group 1): all operands cache-hot
         jg = 1;
         at = 0;
@@ -203,8 +209,8 @@ __global__ __launch_bounds__(LANES *WAVES_PER_WG, OCC != 0 ? OCC : (TIGHT ? (R >
 #else
     constexpr bool half_ok = HALF_TILES;
 #endif
-    const bool skip0 = half_ok && g.self_mode && a0 + 1u >= (jb0 + 1u) * 64u;
-    const bool skip1 = half_ok && jb0 + 1u >= g.n_jblocks;
+    const bool skip0 = half_ok && tile_skips_block0(g.self_mode, a0, jb0);   // (work_map.hpp: the cost order's classes are these two tests)
+    const bool skip1 = half_ok && tile_skips_block1(jb0, g.n_jblocks);
     // The walk is TEXTUALLY included once per case (pair_kslice_walk.inc; SKL_J0 / SKL_J1 = the column blocks
     // [J0, J1) it walks), not a lambda or a function template: wrapping it in either changes hipcc's register
     // allocation of the 32-row form (168 VGPRs + 144 B of spills per lane instead of 144 VGPRs).  No value of
@@ -365,6 +371,8 @@ hipError_t launch_pair_kernel_kslice(const PairArgs &args_in, int mode, int shap
     const int R = shape > 1000 ? shape / 100 : shape / 10;   // 165 / 325 (and 165x, 325x in the A/B build): 16 x 128 and 32 x 128 tiles
     const int JL = 2;
     uint64_t n_wg = 0;
+    // tiles dealt by cost: the k-sliced counts form of the 16 x 128 shape, which is the one that walks half tiles (COST_ORDER in the kernel)
+    if (!(shape == 165 && k_sliced && mode == MODE_COUNTS && ablate == 0 && args.fuse_counter == nullptr && args.no_half_tiles == 0u)) args.tile_cost_order = 0;
     const hipError_t pe = plan_tiles(args, (uint32_t)R, (uint32_t)JL * 64u, scratch, stream, &n_wg);
     if (pe != hipSuccess) return pe;
     if (n_wg == 0) return hipSuccess;

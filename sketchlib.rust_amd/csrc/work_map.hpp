@@ -3,7 +3,8 @@
 // fields: the ONE place the numbering is written.
 //
 //   tiles   workgroup index -> (XCD, slot) -> tile number -> (column group, row tile): plan_tile_geometry() and
-//           plan_tile_numbering() against lookup_tile_at();
+//           plan_tile_numbering() against lookup_tile_at(); dealt by cost (self mode, full tiles before half tiles on every
+//           XCD): plan_tile_numbering_by_cost() against lookup_tile_by_cost_at(), tile_slot_by_cost() the forward map;
 //   units   the chunk-split kernel's k-sliced grid, slot on an XCD -> (tile slot, k index, chunk slice) and the slice's chunk
 //           range: plan_kslice_grid() against kslice_unit() and slice_chunk_range().
 //
@@ -68,7 +69,9 @@ SKL_MAP_FN void plan_tile_geometry(G &g, uint32_t rows_per_tile, uint32_t cols_p
 // prefix[0 .. n_supergroups(g)] with the first tile number of each super-group (the caller uploads it and sets g.tile_prefix)
 // and copies it into the arguments when it is short enough and the launch allows it.  Workgroup b runs on XCD
 // b mod 2^xcd_shift and is slot b >> xcd_shift there; XCD x takes tiles [x * tiles_per_xcd, (x + 1) * tiles_per_xcd) of the
-// numbering -- every XCD the same number of (equal-cost) tiles -- or, interleaved, whole blocks of 32 tiles dealt in turns.
+// numbering -- every XCD the same number of tiles, which are equal-cost in cross mode and wherever no half tile is walked; self-mode
+// launches that walk half tiles are dealt by cost instead (plan_tile_numbering_by_cost below) -- or, interleaved, whole blocks of
+// 32 tiles dealt in turns.
 // Returns false when the launch has too many tiles; *grid_out = tiles_per_xcd << xcd_shift workgroups, 0 = nothing to do.
 template <class G>
 SKL_MAP_FN bool plan_tile_numbering(G &g, uint32_t *prefix, uint64_t *grid_out)
@@ -173,6 +176,236 @@ SKL_MAP_FN bool lookup_tile_at(const G &g, uint32_t xcd, uint32_t slot, uint32_t
     }
     tile_in_supergroup_self(g, lo, t - g.tile_prefix[lo], group, row_tile);
     return true;
+}
+
+// ---------------------------------------------------------------------------
+// tiles dealt by cost (self mode, 128-column groups: tile_cost_order)
+// ---------------------------------------------------------------------------
+//
+// In self mode the active tiles are NOT equal-cost where the kernel walks half tiles (pair_kslice.hip): a tile whose 64-column
+// block 0 lies on or below the diagonal, or whose block 1 lies past the launch's last column, walks one block and costs half.
+// Every column group ends in 64 / tile_rows such tiles, so contiguous shares of the numbering above differ by up to a ninth in
+// cost at 1 000 genomes, and the XCD that holds none of them ends last.  The second order numbers the two classes apart:
+//   full tiles   the super-group numbering above with every group's row tiles cut at its last full one (same prefix table);
+//   half tiles   group by group: the first group the band reaches, a run of groups with 64 / tile_rows each, the last group
+//                the band's end cuts, and the group whose columns end in block 0 (all of its tiles) -- closed form, no table.
+// XCD x takes the x-th share of the full numbering, then the x-th share of the half numbering: its slots run its full tiles
+// first and its half tiles last.  Shares differ by at most one tile per class -- the odd full tiles go to the first XCDs,
+// the odd half tiles to the last -- so the heaviest XCD is within one full tile of the mean.  tiles_per_xcd is the largest
+// share; a slot past an XCD's own share yields nothing.
+
+// The half-tile tests of a tile whose first row is a0 and first 64-column block jb0 (2 blocks per tile): the kernel's skip and
+// the classes below are the same two lines.
+SKL_MAP_FN bool tile_skips_block0(uint32_t self_mode, uint32_t a0, uint32_t jb0) { return self_mode && a0 + 1u >= (jb0 + 1u) * 64u; }
+SKL_MAP_FN bool tile_skips_block1(uint32_t jb0, uint32_t n_jblocks) { return jb0 + 1u >= n_jblocks; }
+
+// The launches the order is defined for
+template <class G>
+SKL_MAP_FN bool tile_cost_order_possible(const G &g)
+{
+    return g.self_mode && !g.xcd_interleave && g.group_cols == 128u && g.tile_rows != 0u && 64u % g.tile_rows == 0u;
+}
+
+// Column groups that can hold a full tile: all but a last group whose columns end in block 0
+template <class G>
+SKL_MAP_FN uint32_t n_full_groups(const G &g)
+{
+    return g.n_groups - (g.n_groups != 0u && tile_skips_block1((g.n_groups - 1u) * 2u, g.n_jblocks) ? 1u : 0u);
+}
+
+// Full row tiles of column group `group`: the first ones, those whose first row lies before the group's column 63
+template <class G>
+SKL_MAP_FN uint32_t group_full_row_tiles(const G &g, uint32_t group)
+{
+    if (tile_skips_block1(group * 2u, g.n_jblocks)) return 0u;
+    const uint64_t mid = (uint64_t)group * g.group_cols + 63u;
+    const uint32_t lim = mid < g.row_end ? (uint32_t)mid : g.row_end;
+    return lim > g.row_begin ? (lim - g.row_begin + g.tile_rows - 1u) / g.tile_rows : 0u;
+}
+
+// Tile u of super-group sg of the full numbering: tile_in_supergroup_self() with the groups' limits pulled in
+template <class G>
+SKL_MAP_FN void full_tile_in_supergroup(const G &g, uint32_t sg, uint32_t u, uint32_t &group, uint32_t &row_tile)
+{
+    const uint32_t first = sg * g.group_span;
+    const uint32_t gcount = map_min(g.group_span, n_full_groups(g) - first);
+    uint32_t lo_at = 0;
+    for (uint32_t gi = 0; gi + 1u < gcount; ++gi) {
+        const uint32_t width = gcount - gi;
+        const uint32_t n_gi = group_full_row_tiles(g, first + gi);
+        const uint32_t span = (n_gi - lo_at) * width;
+        if (u < span) {
+            row_tile = lo_at + u / width;
+            group = first + gi + (u - (u / width) * width);
+            return;
+        }
+        u -= span;
+        lo_at = n_gi;
+    }
+    row_tile = lo_at + u;
+    group = first + gcount - 1u;
+}
+
+// The runs of the half numbering: group ga (h_a tiles), groups ga + 1 ... ga + n_mid (`per` each), group gb (h_b), group
+// n_groups - 1 when its columns end in block 0 (whatever is left).  A group below ga has no tile, one above gb only full ones.
+struct HalfRuns {
+    uint32_t ga, h_a, n_mid, per, gb, h_b;
+};
+template <class G>
+SKL_MAP_FN HalfRuns half_tile_runs(const G &g)
+{
+    HalfRuns r = {0u, 0u, 0u, 64u / g.tile_rows, 0u, 0u};
+    const uint32_t ngf = n_full_groups(g);
+    r.ga = (g.row_begin + 1u) / g.group_cols;    // the first group with a column right of row_begin
+    if (ngf == 0u || g.row_end < 64u || r.ga >= ngf) return r;
+    r.gb = map_min(ngf - 1u, (g.row_end - 64u) / g.group_cols);   // the last group whose column 63 lies right of a row
+    if (r.gb < r.ga) return r;
+    r.h_a = group_row_tiles(g, r.ga) - group_full_row_tiles(g, r.ga);
+    if (r.gb > r.ga) {
+        r.n_mid = r.gb - r.ga - 1u;
+        r.h_b = group_row_tiles(g, r.gb) - group_full_row_tiles(g, r.gb);
+    }
+    return r;
+}
+
+// Inverse: half tile v
+template <class G>
+SKL_MAP_FN void half_tile_at(const G &g, uint32_t v, uint32_t &group, uint32_t &row_tile)
+{
+    const HalfRuns r = half_tile_runs(g);
+    const uint32_t mid = r.n_mid * r.per;
+    if (v < r.h_a) {
+        group = r.ga;
+    } else if (v - r.h_a < mid) {
+        const uint32_t q = (v - r.h_a) / r.per;
+        group = r.ga + 1u + q;
+        v = v - r.h_a - q * r.per;
+    } else if (v - r.h_a - mid < r.h_b) {
+        group = r.gb;
+        v = v - r.h_a - mid;
+    } else {
+        group = g.n_groups - 1u;
+        v = v - r.h_a - mid - r.h_b;
+    }
+    row_tile = group_full_row_tiles(g, group) + v;
+}
+
+// The share of XCD `xcd`: tiles [full_begin, + n_full) of the full numbering, then [half_begin, + n_half) of the half numbering
+struct CostShare {
+    uint32_t full_begin, n_full, half_begin, n_half;
+};
+template <class G>
+SKL_MAP_FN CostShare tile_cost_share(const G &g, uint32_t xcd)
+{
+    const uint32_t n_xcd = 1u << g.xcd_shift, n_half = g.n_active_tiles - g.n_full_tiles;
+    const uint32_t qf = g.n_full_tiles >> g.xcd_shift, rf = g.n_full_tiles & (n_xcd - 1u);
+    const uint32_t qh = n_half >> g.xcd_shift, plain = n_xcd - (n_half & (n_xcd - 1u));   // XCDs before those with one half tile more
+    CostShare s;
+    s.full_begin = xcd * qf + map_min(xcd, rf);
+    s.n_full = qf + (xcd < rf ? 1u : 0u);
+    s.half_begin = xcd * qh + (xcd > plain ? xcd - plain : 0u);
+    s.n_half = qh + (xcd >= plain ? 1u : 0u);
+    return s;
+}
+
+// Forward, step 2 in this order (tile_cost_order_possible() launches): as plan_tile_numbering(), the table being the full
+// numbering's; sets n_full_tiles too.
+template <class G>
+SKL_MAP_FN bool plan_tile_numbering_by_cost(G &g, uint32_t *prefix, uint64_t *grid_out)
+{
+    *grid_out = 0;
+    g.n_active_tiles = g.tiles_per_xcd = g.n_full_tiles = 0;
+    g.n_prefix_inline = 0;
+    const uint32_t ngf = n_full_groups(g), n_super = (ngf + g.group_span - 1u) / g.group_span;
+    uint64_t total = 0, full = 0;
+    for (uint32_t gi = 0; gi < g.n_groups; ++gi) total += group_row_tiles(g, gi);
+    for (uint32_t gi = 0; gi < ngf; ++gi) {
+        if (gi % g.group_span == 0) prefix[gi / g.group_span] = (uint32_t)full;
+        full += group_full_row_tiles(g, gi);
+    }
+    prefix[n_super] = (uint32_t)full;
+    if (total >= (1ull << 31)) return false;
+    if (g.inline_prefix_ok && n_super + 1u <= (uint32_t)TILE_PREFIX_INLINE) {
+        g.n_prefix_inline = n_super + 1u;
+        for (uint32_t x = 0; x <= n_super; ++x) g.tile_prefix_inline[x] = prefix[x];
+    }
+    g.n_active_tiles = (uint32_t)total;
+    g.n_full_tiles = (uint32_t)full;
+    for (uint32_t x = 0; x < (1u << g.xcd_shift); ++x) {
+        const CostShare s = tile_cost_share(g, x);
+        if (s.n_full + s.n_half > g.tiles_per_xcd) g.tiles_per_xcd = s.n_full + s.n_half;
+    }
+    *grid_out = (uint64_t)g.tiles_per_xcd << g.xcd_shift;
+    return true;
+}
+
+// Inverse in this order: lookup_tile_at()
+template <class G>
+SKL_MAP_FN bool lookup_tile_by_cost_at(const G &g, uint32_t xcd, uint32_t slot, uint32_t &group, uint32_t &row_tile)
+{
+    const CostShare s = tile_cost_share(g, xcd);
+    if (slot >= s.n_full + s.n_half) return false;
+    if (slot >= s.n_full) {
+        half_tile_at(g, s.half_begin + (slot - s.n_full), group, row_tile);
+        return true;
+    }
+    const uint32_t t = s.full_begin + slot;
+    const uint32_t n_super = (n_full_groups(g) + g.group_span - 1u) / g.group_span;
+    if (g.n_prefix_inline != 0u) {
+        uint32_t lo = 0, base = 0;
+        SKL_MAP_UNROLL
+        for (int x = 1; x < TILE_PREFIX_INLINE; ++x) {
+            if ((uint32_t)x < n_super && g.tile_prefix_inline[x] <= t) {
+                lo = (uint32_t)x;
+                base = g.tile_prefix_inline[x];
+            }
+        }
+        full_tile_in_supergroup(g, lo, t - base, group, row_tile);
+        return true;
+    }
+    uint32_t lo = 0, hi = n_super;
+    while (hi - lo > 1u) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (g.tile_prefix[mid] <= t) lo = mid; else hi = mid;
+    }
+    full_tile_in_supergroup(g, lo, t - g.tile_prefix[lo], group, row_tile);
+    return true;
+}
+
+// Forward in this order: the (XCD, slot) of active tile (group, row_tile) -- what the plan promises the decode above
+template <class G>
+SKL_MAP_FN void tile_slot_by_cost(const G &g, uint32_t group, uint32_t row_tile, uint32_t &xcd, uint32_t &slot)
+{
+    const uint32_t n_full_here = group_full_row_tiles(g, group);
+    const bool half = row_tile >= n_full_here;
+    uint32_t t;
+    if (half) {
+        const HalfRuns r = half_tile_runs(g);
+        const bool in_runs = group < n_full_groups(g);   // (then ga <= group <= gb: no other group has a half tile)
+        t = (!in_runs ? r.h_a + r.n_mid * r.per + r.h_b : group == r.ga ? 0u : r.h_a + (group - r.ga - 1u) * r.per) + (row_tile - n_full_here);
+    } else {
+        const uint32_t sg = group / g.group_span, first = sg * g.group_span;
+        const uint32_t gcount = map_min(g.group_span, n_full_groups(g) - first);
+        t = g.n_prefix_inline != 0u ? g.tile_prefix_inline[sg] : g.tile_prefix[sg];
+        uint32_t lo_at = 0;
+        for (uint32_t gi = 0; gi < gcount; ++gi) {   // the stretch of row tiles the groups from gi on share
+            const uint32_t width = gcount - gi, n_gi = group_full_row_tiles(g, first + gi);
+            if (row_tile < n_gi) {
+                t += (row_tile - lo_at) * width + (group - first - gi);
+                break;
+            }
+            t += (n_gi - lo_at) * width;
+            lo_at = n_gi;
+        }
+    }
+    for (xcd = 0;; ++xcd) {
+        const CostShare s = tile_cost_share(g, xcd);
+        const uint32_t begin = half ? s.half_begin : s.full_begin, count = half ? s.n_half : s.n_full;
+        if (t < begin + count) {
+            slot = (half ? s.n_full : 0u) + (t - begin);
+            return;
+        }
+    }
 }
 
 // ---------------------------------------------------------------------------
