@@ -1,4 +1,4 @@
-"""Early break of the core/accessory calls (capi.cpp dense_band): all-vs-all timings on Set U / Set R at several sizes, with the
+"""Early break of the core/accessory calls (capi_dense.cpp dense_band): all-vs-all timings on Set U / Set R at several sizes, with the
 library as loaded (SKL_LIBRARY=<A/B build> SKL_EARLY_BREAK=0 for the comparison).  One JSON line per case."""
 import os, sys, time, json
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))

@@ -1,6 +1,15 @@
 // capi_internal.hpp -- shared between the translation units that implement
-// include/sketchlib_dist.h (capi.cpp: contexts, slabs, dense calls; capi_knn.cpp: the kNN
-// drivers; capi_aux.cpp: candidate lists and sketching; capi_pairs.cpp: pair lists; capi_finish.cpp: finishing sketch streams).  Not part of the public boundary.
+// include/sketchlib_dist.h.  Not part of the public boundary.
+//   capi_ctx.cpp       errors, the handle registry, a context's life cycle, streams, scratch, launch timing, the clock sampler
+//   capi_knobs.cpp     the environment, read into `Knobs` (knobs.def, knobs.hpp) -- the one file that calls the C library's lookup
+//   capi_tables.cpp    the probe of the host libm's logarithm; upload of the ln J / distance tables (dist_tables.hpp)
+//   capi_sketches.cpp  slabs, parameter checks, the operand / epilogue fields of a launch
+//   capi_eb.cpp        the early break's sample and the decisions a context keeps
+//   capi_dense.cpp     one pair-kernel launch, the dense executors and entry points
+//   capi_knn.cpp       the kNN drivers;  capi_aux.cpp  candidate lists and sketching;  capi_pairs.cpp  pair lists
+//   capi_inv.cpp       inverted query;  capi_reads.cpp  read survivors;  capi_aa.cpp  amino-acid sketching
+//   capi_finish.cpp    finishing sketch streams on the device;  capi_slab.cpp  new slabs from resident ones
+// Everything declared here is SKL_INTERNAL (hidden): the library exports the functions of the public header and nothing else of the host layer.
 // How a dense call and each pair-kernel launch is shaped is decided in dense_plan.hpp (pure, no HIP), reached through kernels.h;
 // the early break's decision in eb_plan.hpp; how the kNN drivers cut and feed their bands in knn_plan.hpp (both pure, no HIP).
 #pragma once
@@ -10,6 +19,7 @@
 #include <hip/hip_runtime.h>
 
 #include <map>
+#include <mutex>
 #include <set>
 #include <string>
 #include <utility>
@@ -43,13 +53,17 @@ SKL_INTERNAL int fail(int code, const char *fmt, ...);
 
 struct skl_sketches;
 
+// the process environment as of now (capi_knobs.cpp): for skl_ctx_create, skl_ctx_reload_env and the A/B build's ctx_bind alone
 SKL_INTERNAL Knobs read_knobs();
+#ifdef SKL_AB
+SKL_INTERNAL int ab_forced_log_variant();   // SKL_FORCE_LOG_VARIANT, for the cached probe of host_log_variant() (-2: not forced)
+#endif
 
 // EARLY BREAK of the core/accessory calls, as decided for one (row slab, column slab) pair: how many k-mer lengths the pair
 // kernel counts before the epilogue completes the pairs still in the running -- for the whole pair space (`decision.lengths`;
 // what the kNN drivers take) and, when its blocks of (row >> shift_r, column >> shift_c) sample ids disagree, per block.
 // The rules -- when a decision is taken at all, the blocks, what the sampled histograms decide -- are eb_plan.hpp's (pure);
-// capi.cpp early_break_plan() samples and keeps the answer.  Kept by the CONTEXT, keyed by the slabs' generation ids (never
+// capi_eb.cpp early_break_plan() samples and keeps the answer.  Kept by the CONTEXT, keyed by the slabs' generation ids (never
 // reused), not written through the caller's const slab.
 struct EbPlan {
     uint64_t rows_gen = 0, cols_gen = 0;
@@ -161,17 +175,33 @@ struct DevBuf {
 using skl::BAND_BYTES;   // (knn_plan.hpp: the kNN band heights read it too)
 
 SKL_INTERNAL int ctx_bind(skl_ctx *ctx);
-// a registered slab whose rows [0, n_samples) are still to be written on the context's stream (capi.cpp; the pad rows are
+// the handle registry (capi_ctx.cpp): live slabs, and the lock that guards them and the live contexts
+SKL_INTERNAL extern std::mutex g_registry_mutex;
+SKL_INTERNAL extern std::set<const void *> g_live_sketches;
+SKL_INTERNAL void free_sketches_locked(skl_sketches *s);   // (capi_sketches.cpp; the registry lock held; a handle already gone: no-op)
+SKL_INTERNAL void free_plans(skl_ctx *ctx);                // the early-break decisions a context keeps (capi_eb.cpp)
+SKL_INTERNAL uint64_t next_generation();                   // a slab's / completeness vector's generation id, never reused (capi_sketches.cpp)
+// a registered slab whose rows [0, n_samples) are still to be written on the context's stream (capi_sketches.cpp; the pad rows are
 // queued to zero, nothing is waited for); skl_sketches_create and the slab operations of capi_slab.cpp fill it
 SKL_INTERNAL int slab_alloc(skl_ctx *ctx, size_t n_samples, size_t nk, const size_t *kmers, size_t sketchsize64, skl_sketches **out);
+// a slab's tables on the device, made on first use (capi_tables.cpp): ln J with min_alive; the single-k distance / ANI table
+SKL_INTERNAL int ensure_ytab(const skl_sketches *s);
+SKL_INTERNAL int ensure_dtab(const skl_sketches *s, int jout, size_t k_idx, float **out);
 // which glibc_log.hpp form reproduces this host's libm log(): probed once per process against
 // std::log; SKL_LOG_FMA / SKL_LOG_SSE2, or -1 when neither does (the FMA form is then used and a
 // warning printed once)
 SKL_INTERNAL int host_log_variant();
 // grow-only scratch slot `which` of the context, at least `bytes` large
 SKL_INTERNAL int ctx_scratch(skl_ctx *ctx, size_t bytes, void **out, ScratchSlot which);
-SKL_INTERNAL uint32_t ctx_xcd_shift(const skl_ctx *ctx);   // log2 of the XCDs the tile order deals workgroups to
-SKL_INTERNAL int forced_kernel(const skl_ctx *ctx);   // A/B build: SKL_KERNEL; product library: always 0
+// log2 of the XCDs the tile order deals workgroups to
+SKL_INTERNAL inline uint32_t ctx_xcd_shift(const skl_ctx *ctx) { return skl::plan_xcd_shift(ctx->n_cu, ctx->knobs.xcds); }
+// A/B build: SKL_KERNEL, and a forced tile shape or ablation counts as a forced kernel (no chunk slices, no mid-band rule);
+// product library: always 0
+SKL_INTERNAL inline int forced_kernel(const skl_ctx *ctx)
+{
+    if (ctx->knobs.kernel == 0 && (ctx->knobs.kslice_shape || ctx->knobs.kslice_ablate)) return 4;
+    return ctx->knobs.kernel;
+}
 // the pair kernel bracketed by HIP events on the context's stream (skl_ctx_kernel_ms)
 SKL_INTERNAL int timed_pair_launch(skl_ctx *ctx, const skl::PairArgs &args, int mode);
 // records [first, second) events around a launch of another kernel the same way; returns the
@@ -179,7 +209,7 @@ SKL_INTERNAL int timed_pair_launch(skl_ctx *ctx, const skl::PairArgs &args, int 
 SKL_INTERNAL std::pair<hipEvent_t, hipEvent_t> *timing_slot(skl_ctx *ctx);
 SKL_INTERNAL int check_params(const skl_sketches *a, const skl_sketches *b, const skl_dist_params *p);
 SKL_INTERNAL bool fused_coreacc_ok(const skl_sketches *s);
-// early break of the core/accessory calls (capi.cpp): the decision for this slab pair (sampled once, kept by the context);
+// early break of the core/accessory calls (capi_eb.cpp): the decision for this slab pair (sampled once, kept by the context);
 // *plan = null: not applicable (eb_plan.hpp eb_applicable: fewer than 3 or more than 8 k-mer lengths, a tiny pair space, switched off)
 SKL_INTERNAL int early_break_plan(skl_ctx *ctx, const skl_sketches *rows, const skl_sketches *cols, int self_mode, double cutoff,
                                   const EbPlan **plan);

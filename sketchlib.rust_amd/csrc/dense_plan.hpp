@@ -1,11 +1,11 @@
 // dense_plan.hpp -- HOW a dense distance call is launched, as data computed by pure functions.
 //
-// capi.cpp dense_band() fills a DenseCall from the slabs, the context and the early-break decision, asks plan_row_bands()
+// capi_dense.cpp dense_band() fills a DenseCall from the slabs, the context and the early-break decision, asks plan_row_bands()
 // where to cut the call and plan_counts_launch() what each band launches, and executes the answer.  Nothing here touches a
 // device: no HIP header, plain C++17 (tests/native/dense_plan_check.cpp builds it with the host compiler alone).
 // The row bands are planned from the whole call, each band's launch from the band's own rows.
-// Every launch of the pair kernel then asks plan_pair_shape() for its tile shape and form (capi.cpp dispatch_pair_kernel), and
-// a host-destined call is cut by plan_host_bands() (capi.cpp dense_rows).
+// Every launch of the pair kernel then asks plan_pair_shape() for its tile shape and form (capi_dense.cpp dispatch_pair_kernel), and
+// a host-destined call is cut by plan_host_bands() (capi_dense.cpp dense_rows).
 #pragma once
 
 #include <stddef.h>
@@ -20,7 +20,7 @@
 
 namespace skl {
 
-// = MODE_COUNTS / MODE_JACCARD / MODE_COREACC, KSLICE_MAX_U16_CHUNKS and KSLICE_SEG_CHUNKS of kernels.h (capi.cpp asserts they agree)
+// = MODE_COUNTS / MODE_JACCARD / MODE_COREACC, KSLICE_MAX_U16_CHUNKS and KSLICE_SEG_CHUNKS of kernels.h (capi_dense.cpp asserts they agree)
 constexpr int PLAN_MODE_COUNTS = 0, PLAN_MODE_JACCARD = 1, PLAN_MODE_COREACC = 2;
 constexpr uint32_t PLAN_MAX_U16_CHUNKS = 1023;   // sketches beyond it (65 535 bins): k-sliced forms only, u32 counts
 constexpr uint32_t PLAN_SEG_CHUNKS = 1016;       // ... walked in segments of this many chunks
@@ -399,10 +399,7 @@ struct PairLaunch {
     bool xcd_interleave = false;   // the tiles are dealt to the XCDs in blocks of 32 (block-by-block early break)
     int n_cu = 256;
     uint32_t xcd_shift = 3;     // plan_xcd_shift()
-    Knobs knobs;
-    // the A/B build (-DSKL_AB) and the forms its switches force; the product library leaves all of it as it is
-    bool ab_build = false;
-    int ab_kernel = 0, ab_kslice_shape = 0, ab_ksplit_rows = 0, ab_kslice_ablate = 0;   // SKL_KERNEL, SKL_KSLICE_SHAPE, SKL_KSPLIT_ROWS, SKL_KSLICE_ABLATE
+    Knobs knobs;                // (kernel, kslice_shape, ksplit_rows, kslice_ablate: the forms the A/B build's switches force; the product library never sets them)
 };
 struct PairShape {
     int shape = 165, ksplit_rows = 8;   // chunk-split kernel: tile shape; pair_ksplit.hip: rows per tile
@@ -457,12 +454,11 @@ inline PairShape plan_pair_shape(const PairLaunch &a)
         if (a.knobs.tile32_min >= 0 && pairs * k_walked >= (uint64_t)a.knobs.tile32_min) s.shape = 325;
         if (a.mid_band) s.shape = 325;   // the mid-band rule (plan_counts_launch): 32-row tiles with the last round cut in 2
     }
-    if (a.ab_build) {
-        if (a.ab_kslice_shape) s.shape = a.ab_kslice_shape;
-        if (a.ab_ksplit_rows) s.ksplit_rows = a.ab_ksplit_rows;
-        s.try_kslice = a.ab_kernel != 3;
-        s.ablate = a.ab_kslice_ablate;
-    }
+    // what the A/B build's switches force (all 0 in the product library: nothing changes)
+    if (a.knobs.kslice_shape) s.shape = a.knobs.kslice_shape;
+    if (a.knobs.ksplit_rows) s.ksplit_rows = a.knobs.ksplit_rows;
+    s.try_kslice = a.knobs.kernel != 3;
+    s.ablate = a.knobs.kslice_ablate;
     s.tile_rows = s.shape > 1000 ? s.shape / 100 : s.shape / 10;
     s.no_half_tiles = !a.knobs.half_tiles;
     // workgroups resident per CU: 4 for every shipped form (the A/B build's 3-wave all-k 32-row form: 3)

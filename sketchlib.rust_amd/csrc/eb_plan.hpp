@@ -1,6 +1,6 @@
 // eb_plan.hpp -- the EARLY BREAK's decision for one (row slab, column slab) pair, as data computed by pure functions.
 //
-// capi.cpp early_break_plan() asks eb_applicable(), cuts the pair space with eb_geometry(), runs the sampler on the device,
+// capi_eb.cpp early_break_plan() asks eb_applicable(), cuts the pair space with eb_geometry(), runs the sampler on the device,
 // hands its histograms to eb_decide() and keeps the answer (EbPlan, capi_internal.hpp).  Nothing here touches a device: no
 // device header, plain C++17 (tests/native/eb_plan_check.cpp builds it with the host compiler alone).
 #pragma once

@@ -266,7 +266,7 @@ inline KnnCallPlan plan_knn_call(const KnnCall &c)
     P.prune = c.knobs.knn_prune && c.knobs.knn_row_flags && !c.coreacc && !c.has_comp && c.ss64 <= (size_t)PLAN_MAX_U16_CHUNKS;
     P.prune_cols_at = c.cross() ? c.n_rows + 64 : 0;
     P.prune_bounds_bytes = (c.n_rows + 64 + (c.cross() ? n + 64 : 0)) * sizeof(uint32_t);
-    // EARLY BREAK (core/accessory keys; capi.cpp early_break_lengths): from the call's second band on -- every list then holds
+    // EARLY BREAK (core/accessory keys; capi_eb.cpp early_break_lengths): from the call's second band on -- every list then holds
     // knn candidates, so a pair that left the reference's loop early, (1, 1), marks nothing -- the band is COUNTED at its first
     // eb_lengths k-mer lengths (k-sliced counts launch) and coreacc_epilogue_knn_kernel writes the records, the marks and the
     // turned copy (pre-filled with (1, 1)), completing the pairs still in the running.  Same records as the fused kernel's.

@@ -547,9 +547,8 @@ static void shape()
     {   // the A/B build's forms.  3254 = round 2's k-sliced 32-row form, 3255 its all-k form: 3 waves per SIMD = 3 workgroups per CU
         // in THAT form, 4 in the other; 1651 / 1652 the 16-row forms
         PairLaunch a = launch_of(PLAN_MODE_COUNTS, true, 999, 1000, 5, true);
-        a.ab_kslice_shape = 3254;
-        CHECK_EQ(plan_pair_shape(a).shape, 165);             // not the A/B build: the switches are not read
-        a.ab_build = true;
+        CHECK_EQ(plan_pair_shape(a).shape, 165);             // the switches at their defaults, which the product library never leaves (tests/test_knobs_cpu.py)
+        a.knobs.kslice_shape = 3254;
         a.tail_slices = 4;
         PairShape s = plan_pair_shape(a);
         CHECK_EQ(s.shape, 3254);
@@ -558,26 +557,25 @@ static void shape()
         CHECK_EQ(s.round_size, 96);                          // 3 x 256 / 8
         CHECK_EQ(s.tail_resident, 96);
         CHECK_NAME(s, true, "skl::pair_kernel_kslice<R=32, JL=2, COUNTS, k-sliced, tight> (32x128 tiles, chunks split over 4 waves; 4 chunk slices per unit in the last round of workgroups)");
-        a.ab_kslice_shape = 3255;
+        a.knobs.kslice_shape = 3255;
         CHECK_EQ(plan_pair_shape(a).wg_per_cu, 4);           // sliced launch in the all-k shape
         PairLaunch f = launch_of(PLAN_MODE_COREACC, true, 999, 1000, 5, false);
-        f.ab_build = true;
-        f.ab_kslice_shape = 3255;
+        f.knobs.kslice_shape = 3255;
         s = plan_pair_shape(f);
         CHECK_EQ(s.wg_per_cu, 3);
         CHECK_EQ(s.round_size, 96);
         CHECK_EQ(s.tail_resident, 0);
         CHECK_NAME(s, true, "skl::pair_kernel_kslice<R=32, JL=2, COREACC, all k, tight> (32x128 tiles, chunks split over 4 waves)");
-        f.ab_kslice_shape = 3254;
+        f.knobs.kslice_shape = 3254;
         CHECK_EQ(plan_pair_shape(f).wg_per_cu, 4);
-        f.ab_kslice_shape = 1652;
+        f.knobs.kslice_shape = 1652;
         CHECK_EQ(plan_pair_shape(f).tile_rows, 16);
         CHECK_NAME(plan_pair_shape(f), true, "skl::pair_kernel_kslice<R=16, JL=2, COREACC, all k, tight> (16x128 tiles, chunks split over 4 waves)");
-        f.ab_kslice_shape = 0;
-        f.ab_kslice_ablate = 2;
+        f.knobs.kslice_shape = 0;
+        f.knobs.kslice_ablate = 2;
         CHECK_EQ(plan_pair_shape(f).ablate, 2);
-        f.ab_kernel = 3;                                     // SKL_KERNEL=ksplit: the chunk-split kernel is not asked
-        f.ab_ksplit_rows = 4;
+        f.knobs.kernel = 3;                                     // SKL_KERNEL=ksplit: the chunk-split kernel is not asked
+        f.knobs.ksplit_rows = 4;
         s = plan_pair_shape(f);
         CHECK(!s.try_kslice);
         CHECK_EQ(s.ksplit_rows, 4);

@@ -31,6 +31,25 @@ def test_header_symbols_all_exported(skl):
     assert sorted(skl.DECLARED_SYMBOLS) == declared
 
 
+def test_nothing_but_the_header_and_the_kernels_is_exported():
+    """The strong symbols of the dynamic table: the functions of the public header, the kernels and their launchers in namespace
+    skl:: (scripts/microbench/kslice_trace links against them), and nothing else of the host layer -- what the translation
+    units share among themselves is declared SKL_INTERNAL in capi_internal.hpp and stays hidden."""
+    import sketchlib.rust_amd as pkg
+
+    pkg.build_library()
+    declared = set(_declared_in_header())
+    toolchain = re.compile(r"__hip_cuid_[0-9a-f]+")          # one byte per HIP translation unit, emitted by hipcc: the only such symbols seen
+    for lib in (pkg.library_path(), pkg.build_ab_library()):
+        out = subprocess.check_output(["nm", "-D", "--defined-only", lib], text=True)
+        strong = [l.split() for l in out.splitlines() if len(l.split()) == 3 and l.split()[1] in "TDBRGS"]
+        text = {name for _a, kind, name in strong if kind == "T" and not name.startswith("_ZN3skl")}
+        assert text == declared, (lib, sorted(text ^ declared))
+        data = [name for _a, kind, name in strong if kind != "T" and not name.startswith("_ZN3skl") and not toolchain.fullmatch(name)]
+        assert not data, (lib, data)
+        assert "free_plans" not in out and "next_generation" not in out
+
+
 def test_product_library_has_no_ab_kernels_or_switches():
     """The forms kept for A/B timing (the round-2/3 forms of the chunk-split kernel's tile shapes) and the
     timing-only ablations, whose outputs are wrong by construction, exist only in the -DSKL_AB build; the
@@ -61,14 +80,32 @@ def test_product_library_has_no_ab_kernels_or_switches():
                    b"SKL_FUSE_EPILOGUE", b"SKL_FUSE_VARIANT", b"pair_kernel_lds", b"SKL_KSLICE_ABLATE", b"SKL_LDS_ABLATE", b"SKL_KERNEL", b"SKL_KSLICE_SHAPE",
                    b"SKL_LDS_SHAPE", b"SKL_FORCE_NA", b"SKL_PAIR_VARIANT", b"SKL_PERSIST"):
         assert needle not in blob, needle
-    # and no getenv on the launch path: what remains is read by read_knobs(), once per context
-    src = open(os.path.join(ROOT, "sketchlib.rust_amd", "csrc", "capi.cpp")).read()
-    lo, hi = src.index("static long long env_int"), src.index("int forced_kernel(const skl_ctx *ctx)")
-    assert "getenv(" not in src[:lo] + src[hi:]
-    assert src.count("read_knobs()") == 4      # definition, skl_ctx_create, skl_ctx_reload_env, the A/B build's refresh at every API entry
-    for f in ("capi_knn.cpp", "capi_aux.cpp", "pair_kslice.hip", "pair_ksplit.hip", "kernels.hip", "topk.hip"):
-        text = open(os.path.join(ROOT, "sketchlib.rust_amd", "csrc", f)).read()
-        assert "getenv" not in text and "env_int(" not in text, f
+    # and no getenv on the launch path: the environment is read in capi_knobs.cpp and nowhere else -- not in another
+    # translation unit of the C ABI, not in a kernel file, not in the switches' table or a plan header -- by read_knobs(), once per context
+    csrc = os.path.join(ROOT, "sketchlib.rust_amd", "csrc")
+    capi = sorted(f for f in os.listdir(csrc) if f.startswith("capi") and f.endswith(".cpp"))
+    assert "capi.cpp" not in capi and {"capi_ctx.cpp", "capi_knobs.cpp", "capi_tables.cpp", "capi_sketches.cpp", "capi_eb.cpp", "capi_dense.cpp"} <= set(capi)
+    plans = sorted(f for f in os.listdir(csrc) if f.endswith("_plan.hpp")) + ["work_map.hpp", "eb_stripes.hpp", "knobs.hpp", "knobs.def", "dist_tables.hpp", "capi_internal.hpp"]
+    assert len(plans) >= 12
+    src = {f: open(os.path.join(csrc, f)).read() for f in capi + plans + sorted(f for f in os.listdir(csrc) if f.endswith(".hip"))}
+    assert len(src) >= 40
+    assert src["capi_knobs.cpp"].count("getenv(") == 1
+    for f, text in src.items():
+        if f != "capi_knobs.cpp":
+            assert "getenv" not in text and "env_int(" not in text, f
+    # read_knobs(): its definition, skl_ctx_create, skl_ctx_reload_env, the A/B build's refresh at every API entry
+    calls = {f: text.count("read_knobs(") for f, text in src.items() if f.endswith(".cpp") and "read_knobs(" in text}
+    assert calls == {"capi_knobs.cpp": 1, "capi_ctx.cpp": 3}, calls
+    ctx = src["capi_ctx.cpp"]
+    for fn in ("int ctx_bind(skl_ctx *ctx)", 'extern "C" int skl_ctx_create(', 'extern "C" int skl_ctx_reload_env('):
+        body = ctx[ctx.index(fn):]
+        assert "ctx->knobs = read_knobs();" in body[:body.index("\n}\n")], fn
+    # ... and the reader behind it (knobs.hpp knobs_from) is reached from capi_knobs.cpp alone: read_knobs() and the A/B build's
+    # once-per-process SKL_FORCE_LOG_VARIANT inside the cached probe of the host's logarithm
+    uses = {f: text.count("knobs_from(") for f, text in src.items() if f.endswith((".cpp", ".hip")) and "knobs_from(" in text}
+    assert uses == {"capi_knobs.cpp": 2}, uses
+    assert sum(text.count("ab_forced_log_variant()") for f, text in src.items() if f.endswith(".cpp")) == 2
+    assert src["capi_tables.cpp"].count("ab_forced_log_variant()") == 1 and "static const int variant = [] {" in src["capi_tables.cpp"]
 
 
 def test_library_has_gfx950_code_object():

@@ -1,4 +1,4 @@
-"""The early break of the core/accessory calls (capi.cpp dense_band, kernels.hip coreacc_epilogue_kernel): the reference's loop
+"""The early break of the core/accessory calls (capi_dense.cpp dense_band, kernels.hip coreacc_epilogue_kernel): the reference's loop
 over the k-mer lengths leaves at the first one whose Jaccard index is 0 (jaccard.rs:89-91) and a fit over fewer than three
 lengths is (1, 1) (jaccard.rs:117), so the pair kernel counts only the first three or four lengths for every pair and the
 epilogue completes the pairs that are still in the running.  Same (core, acc), bit for bit, as counting every length --

@@ -1,4 +1,4 @@
-"""Round 6 of the early break (capi.cpp early_break_plan, epilogue.hip): the regimes round 5 left untested or declined.
+"""Round 6 of the early break (capi_eb.cpp early_break_plan, epilogue.hip): the regimes round 5 left untested or declined.
 
 * sketchsize64 256 ... 1023: expected_samebits = maxnbits >> 14 >= 1 (jaccard.rs:26-31), so a pair leaves the reference's
   loop when it shares NO MORE bins than chance -- 1, 2 or 3 of them -- not when it shares none.  Random sketches (Poisson(1-4)

@@ -172,7 +172,7 @@ def test_every_pair_written_when_kernels_alternate(skl, gpu_ctx, monkeypatch, ea
 
 def test_host_output_in_several_bands_equals_device_output(skl, gpu_ctx):
     """A host destination is filled in bands of 512 MB through two device buffers, band i's copy issued behind band i + 1's
-    kernels (csrc/capi.cpp dense_rows): 1.6 GB of (core, acc) records = 4 bands (self mode), 0.72 GB of single-k
+    kernels (csrc/capi_dense.cpp dense_rows): 1.6 GB of (core, acc) records = 4 bands (self mode), 0.72 GB of single-k
     distances = 2 bands (cross mode), and a row range that starts mid-matrix, against the same call left on the device."""
     import torch
 

@@ -1,4 +1,4 @@
-"""The fused core/accessory epilogue of k-sliced launches (pair_kslice.hip, FUSE; capi.cpp dense_band) -- A/B BUILD ONLY.
+"""The fused core/accessory epilogue of k-sliced launches (pair_kslice.hip, FUSE; capi_dense.cpp dense_band) -- A/B BUILD ONLY.
 
 Launches of roughly 900 ... 8 000 genomes run one workgroup per (tile, k-mer length) and hand their bin-match counts to a
 second kernel.  Round 5 built the one-launch form the round-4 verdict asked for: every workgroup stores its counts
