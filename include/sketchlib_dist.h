@@ -199,6 +199,37 @@ int skl_cross_dists_rows(skl_ctx *ctx, const skl_sketches *ref, const skl_sketch
                          const skl_dist_params *p, size_t ref_begin, size_t ref_end, float *out,
                          int out_on_device);
 
+/* ---- all pairs within a distance cap (no reference counterpart): the dense listing with lines removed ----
+ * What network building, threshold clustering and dereplication ask of a pair space: every pair closer than a cap, however
+ * many a sample has.  The calls evaluate rows [row_begin, row_end) exactly as skl_self_dists_rows / skl_cross_dists_rows do
+ * (same row-range rules: an empty range, or fewer than two samples, is SKL_OK with *n_found = 0; completeness vectors and
+ * completeness_cutoff apply unchanged) and keep the pairs that pass, compacted on the device (csrc/within.hip).
+ * ORDER: the dense call's own -- ascending condensed index (i < j) for the self call, ascending i_ref * n_query + j_query for
+ * the cross call -- so the result is the dense listing with lines removed and never depends on scheduling.
+ * RECORD r: out_i[r], out_j[r] = the pair's samples, indices into the whole slab(s), not into the row range (self: i < j;
+ * cross: reference, query); out_d[r * ncols ...) = the f32 values the dense call stores, ncols = 2 (core, acc) or 1.
+ * PREDICATE, on those f32 values (v0, v1):
+ *     distance in the first column (core; single-k Jaccard distance):  v0 <= (float)max_first
+ *     ANI (p->ani):                                                    v0 >= (float)(1.0 - (double)max_first)
+ *                                     -- the cap is a distance in every mode; the bound is formed in double and rounded once
+ *     core/accessory, additionally:                                    v1 <= (float)max_second
+ *                                     -- max_second = INFINITY: the second column is not tested; ignored when ncols == 1
+ * A NaN in a tested column never passes.  max_first or max_second NaN, or max_first < 0: SKL_ERR_INVALID_ARG.
+ * CAPACITY: *n_found is always the number of pairs that pass.  Records [0, min(*n_found, capacity)) are written -- the first
+ * ones in order -- and nothing beyond them is touched; the status is SKL_OK either way and the caller compares *n_found with
+ * capacity.  capacity == 0 is the COUNT-ONLY form: the outputs may be NULL and the scatter pass is not launched.  capacity > 0
+ * with a NULL output is SKL_ERR_INVALID_ARG.  The context keeps nothing between calls.
+ * `out_on_device` != 0: out_i / out_j / out_d are device pointers.  Either way the call returns with the stream idle and the
+ * records in place (it has *n_found to hand back).  The row range is evaluated in bands of the host-destined dense calls'
+ * scratch budget (512 MiB; each band fewer than 2^32 pairs), a band's records appended behind the previous band's: a
+ * whole-matrix call over a million samples needs no 4 TB buffer. */
+int skl_self_dists_within(skl_ctx *ctx, const skl_sketches *s, const skl_dist_params *p, size_t row_begin, size_t row_end,
+                          double max_first, double max_second, uint32_t *out_i, uint32_t *out_j, float *out_d, uint64_t capacity,
+                          int out_on_device, uint64_t *n_found);
+int skl_cross_dists_within(skl_ctx *ctx, const skl_sketches *ref, const skl_sketches *query, const skl_dist_params *p,
+                           size_t ref_begin, size_t ref_end, double max_first, double max_second, uint32_t *out_i,
+                           uint32_t *out_j, float *out_d, uint64_t capacity, int out_on_device, uint64_t *n_found);
+
 /* ---- sparse k-nearest-neighbour distances ----
  * Output rows hold `knn` items sorted ascending by key, where key = d0 for Jaccard / core for
  * CoreAcc, or 1-ANI for ANI (mod.rs:173-176).  out_d1 is written for CoreAcc only and may be NULL

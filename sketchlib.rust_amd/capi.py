@@ -95,6 +95,10 @@ _SIG = [
     ("skl_cross_dists_all", C.c_int, [_P, _P, _P, C.POINTER(DistParams), _P, C.c_int]),
     ("skl_cross_dists_rows", C.c_int, [_P, _P, _P, C.POINTER(DistParams), C.c_size_t, C.c_size_t,
                                        _P, C.c_int]),
+    ("skl_self_dists_within", C.c_int, [_P, _P, C.POINTER(DistParams), C.c_size_t, C.c_size_t, C.c_double, C.c_double, _P, _P, _P,
+                                        C.c_uint64, C.c_int, C.POINTER(C.c_uint64)]),
+    ("skl_cross_dists_within", C.c_int, [_P, _P, _P, C.POINTER(DistParams), C.c_size_t, C.c_size_t, C.c_double, C.c_double, _P, _P, _P,
+                                         C.c_uint64, C.c_int, C.POINTER(C.c_uint64)]),
     ("skl_self_dists_knn", C.c_int, [_P, _P, C.POINTER(DistParams), C.c_size_t, _P, _P, _P,
                                      C.c_int]),
     ("skl_self_dists_knn_rows", C.c_int, [_P, _P, C.POINTER(DistParams), C.c_size_t, C.c_size_t,
@@ -471,6 +475,61 @@ def cross_dists_rows(ctx, r, q, p, r0, r1, out=None):
     addr, dev = _ptr(out)
     _check(load().skl_cross_dists_rows(ctx._h, r._h, q._h, C.byref(p), r0, r1, addr, dev))
     return out
+
+
+# ---- all pairs within a distance cap ----
+
+WITHIN_CHUNK = 2048        # WITHIN_CHUNK of csrc/within_plan.hpp: pair positions a workgroup of the filter owns
+WITHIN_SCAN_STEP = 1024    # WITHIN_SCAN_STEP: chunk counts the scan takes per step
+
+
+def dists_within_into(ctx, s, p, max_dist, max_acc=np.inf, r0=0, r1=None, out=None, capacity=0, query=None):
+    """skl_self_dists_within (query=None) / skl_cross_dists_within as they are: rows [r0, r1), `out` = (i, j, d) numpy arrays or
+    device tensors taking `capacity` records (None with capacity 0: count only) -> n_found, which may exceed capacity."""
+    r1 = (s.n) if r1 is None else r1
+    oi, oj, od = out if out is not None else (None, None, None)
+    (ai, dev), (aj, dev_j), (ad, dev_d) = _ptr(oi), _ptr(oj), _ptr(od)
+    if not dev == dev_j == dev_d:
+        raise ValueError("the three outputs must live on the same side")
+    found = C.c_uint64(0)
+    if query is None:
+        _check(load().skl_self_dists_within(ctx._h, s._h, C.byref(p), r0, r1, max_dist, max_acc, ai, aj, ad, capacity, dev, C.byref(found)))
+    else:
+        _check(load().skl_cross_dists_within(ctx._h, s._h, query._h, C.byref(p), r0, r1, max_dist, max_acc, ai, aj, ad, capacity, dev,
+                                             C.byref(found)))
+    return int(found.value)
+
+
+def count_within(ctx, s, p, max_dist, max_acc=np.inf, r0=0, r1=None, query=None):
+    """How many pairs of rows [r0, r1) lie within the cap (the count-only form: nothing is scattered or copied)."""
+    return dists_within_into(ctx, s, p, max_dist, max_acc, r0, r1, query=query)
+
+
+def _dists_within(ctx, s, p, max_dist, max_acc, r0, r1, capacity, query):
+    # Without a capacity the call runs twice: the count-only form sizes the arrays, the second call fills them.  The dense
+    # evaluation -- nearly all of the time -- is paid twice; a caller who can bound the answer passes `capacity` and pays once.
+    cap = count_within(ctx, s, p, max_dist, max_acc, r0, r1, query) if capacity is None else int(capacity)
+    out = (np.zeros(cap, dtype=np.uint32), np.zeros(cap, dtype=np.uint32), np.zeros((cap, ncols(p)), dtype=np.float32))
+    found = dists_within_into(ctx, s, p, max_dist, max_acc, r0, r1, out, cap, query) if cap else 0
+    if capacity is None and found != cap:
+        raise RuntimeError(f"{found} pairs within the cap after {cap} were counted")
+    if capacity is not None and found > cap:   # the arrays held the first `cap`: once more with the exact size
+        return _dists_within(ctx, s, p, max_dist, max_acc, r0, r1, found, query)
+    return tuple(x[:found] for x in out)
+
+
+def self_dists_within(ctx, s, p, max_dist, max_acc=np.inf, r0=0, r1=None, capacity=None):
+    """All pairs i < j of rows [r0, r1) whose distance is within the cap, in condensed order -> (i, j, d): uint32 [n_found],
+    uint32 [n_found], f32 [n_found, ncols] -- the dense listing with lines removed (skl_self_dists_within: d[:, 0] <= max_dist,
+    for ANI d >= 1 - max_dist; core/accessory also d[:, 1] <= max_acc unless it is inf).  Always exactly n_found records.
+    capacity=None counts first and then fills arrays of the exact size (two evaluations of the rows); capacity=N evaluates
+    once into arrays of N records and repeats with the exact size only if more than N pairs passed."""
+    return _dists_within(ctx, s, p, max_dist, max_acc, r0, r1, capacity, None)
+
+
+def cross_dists_within(ctx, r, q, p, max_dist, max_acc=np.inf, r0=0, r1=None, capacity=None):
+    """The same for reference rows [r0, r1) against every query -> (i_ref, j_query, d), ascending i_ref * n_query + j_query."""
+    return _dists_within(ctx, r, p, max_dist, max_acc, r0, r1, capacity, q)
 
 
 # ---- sparse ----

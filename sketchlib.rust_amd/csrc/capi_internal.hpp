@@ -9,6 +9,7 @@
 //   capi_knn.cpp       the kNN drivers;  capi_aux.cpp  candidate lists and sketching;  capi_pairs.cpp  pair lists
 //   capi_inv.cpp       inverted query;  capi_reads.cpp  read survivors;  capi_aa.cpp  amino-acid sketching
 //   capi_finish.cpp    finishing sketch streams on the device;  capi_slab.cpp  new slabs from resident ones
+//   capi_within.cpp    the pairs of a dense call that lie within a distance cap
 // Everything declared here is SKL_INTERNAL (hidden): the library exports the functions of the public header and nothing else of the host layer.
 // How a dense call and each pair-kernel launch is shaped is decided in dense_plan.hpp (pure, no HIP), reached through kernels.h;
 // the early break's decision in eb_plan.hpp; how the kNN drivers cut and feed their bands in knn_plan.hpp (both pure, no HIP).
@@ -94,7 +95,8 @@ enum ScratchSlot : int {
     SCRATCH_COUNTS_2 = 15,         // second counts band (early break of the core/accessory kNN; odd bands of an overlapped dense call)
     SCRATCH_SKETCH_FINISHED = 16,  // GPU sketching: finished words, first signs and flags on their way to the host,
     SCRATCH_SKETCH_TARGETS = 17,   // the finish kernel's target arrays (global form)
-    SCRATCH_SLOTS = 18
+    SCRATCH_WITHIN = 18,           // pairs within a cap: running total, chunk offsets, chunk counts (within_plan.hpp)
+    SCRATCH_SLOTS = 19
 };
 
 struct skl_ctx {

@@ -14,6 +14,7 @@
 #include "finish_plan.hpp"  // device-side densify + transpose: launch rules, flag bits, the shared target rule
 #include "work_map.hpp"     // which workgroup computes what: TILE_PREFIX_INLINE, the fields below it reads and plans
 #include "inv_top_plan.hpp" // best hits of an inverted query: digits, list length, LDS bytes, the descending walk
+#include "within_plan.hpp"  // pairs within a distance cap: chunks, scan steps, the predicate, the (i, j) of a position
 
 namespace skl {
 
@@ -663,5 +664,26 @@ struct SlabGatherArgs {
     uint64_t row_vec;
 };
 hipError_t launch_slab_gather(const SlabGatherArgs &a, int n_cu, hipStream_t stream);
+
+// within.hip: the positions of a dense band that pass a distance cap, counted per chunk, scanned, scattered in position order;
+// every number below but the pointers comes from within_plan.hpp
+struct WithinArgs {
+    const float *band;            // [m][ncols] f32, 16-byte aligned base, within_band_bytes(m, ncols) readable
+    uint64_t m;                   // positions of the band, < WITHIN_BAND_PAIR_LIMIT
+    uint64_t chunks;              // within_chunks(m)
+    uint32_t ncols, self_mode;
+    uint64_t n_cols;              // columns of the pair space (self mode: the samples of the triangle)
+    uint64_t first;               // position of band[0] in the whole pair space
+    WithinPred pred;
+    uint32_t *counts;             // [chunks]
+    uint64_t *offsets;            // [chunks]
+    uint64_t *total;              // device word: passes of the bands before this one; the scan adds this band's
+    uint32_t *out_i, *out_j;      // record of slot s at [s - rebase], for s < capacity
+    float *out_d;
+    uint64_t capacity, rebase;
+};
+hipError_t launch_within_count(const WithinArgs &a, hipStream_t stream);
+hipError_t launch_within_scan(const WithinArgs &a, hipStream_t stream);
+hipError_t launch_within_scatter(const WithinArgs &a, hipStream_t stream);
 
 }  // namespace skl
