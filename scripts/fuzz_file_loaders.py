@@ -7,7 +7,7 @@ fed to `sketchlib inverted precluster --count`, `skl_dbtool info` and (the .skm,
 exit (sanitizer report, signal, time-out) is printed.
 
 Build the two sanitised binaries first (from sketchlib.rust_amd/csrc):
-  g++ -O1 -g -std=c++17 -fsanitize=address,undefined -fno-sanitize-recover=undefined host/*.cpp host/cli/*.cpp -I../../include \
+  g++ -O1 -g -std=c++17 -fsanitize=address,undefined -fno-sanitize-recover=undefined host/*.cpp host/multi/*.cpp host/cli/*.cpp -I../../include \
       -L_build -lsketchlib_dist_hip -lpthread -lz -o /tmp/sketchlib_asan
   g++ -O1 -g -std=c++17 -fsanitize=address,undefined -fno-sanitize-recover=undefined tools/dbtool_main.cpp \
       $(ls host/*.cpp | grep -v -e distances.cpp -e sketch_gpu) -lpthread -lz -o /tmp/dbtool_asan

@@ -13,8 +13,8 @@ pytestmark = pytest.mark.gpu
 CLI = os.path.join(ROOT, "sketchlib.rust_amd", "csrc", "_build", "sketchlib")
 
 
-def run(*args, env=None):
-    res = subprocess.run([CLI, "dist", *args], capture_output=True, text=True,
+def run(*args, env=None, timeout=None):
+    res = subprocess.run([CLI, "dist", *args], capture_output=True, text=True, timeout=timeout,
                          env=None if env is None else {**os.environ, **env})
     assert res.returncode == 0, res.stderr
     return res.stdout
@@ -243,6 +243,30 @@ def test_multi_context_synthetic(gpu_ctx, tmp_path):
                 assert run(prefix, *flags, *ties, "--devices", devices, env={"SKL_KNN_BAND_ROWS": "16"}) == want
                 if not ties:
                     assert run(prefix, *flags, "--devices", devices, env={"SKL_KNN_BAND_ROWS": "16", "SKL_KNN_DECOUPLED": "0"}) == want
+
+
+@pytest.mark.parametrize("n,devices", [(40, "0,0,0,0,0"),           # cuts 0,16,32,32,32,40: empty windows in the middle
+                                       (33, "0,0,0"),               # cuts 0,16,32,33: the last window is one row off a boundary
+                                       (47, "0,0,0,0,0,0,0,0")])    # cuts ...,32,47,47,47: two empty windows that START at n, off a boundary
+def test_multi_context_knn_window_edges(gpu_ctx, tmp_path, n, devices):
+    """The column windows the multi-device kNN cuts (csrc/host/multi_plan.hpp, knn_window_cuts; bands of 16 rows) at the sizes where
+    a window is empty, ends at n off a band boundary or starts there: decoupled windows (the default), dealt bands (canonical
+    ties) and travelling heaps (SKL_KNN_DECOUPLED=0) must each print what one device prints.  The travelling heaps wait for each
+    other on condition variables -- a mistake there hangs a run instead of failing it -- so those runs come last."""
+    from sketchlib.rust_amd import synth
+
+    kmers, ss64 = [15, 19, 23, 27, 31], 16
+    prefix, _ = _write_db(tmp_path, "w", synth.set_r(n, kmers, ss64, n_clusters=5), kmers, ss64)
+    bands = {"SKL_KNN_BAND_ROWS": "16"}
+    both = (("--knn", "7"), ("--knn", "7", "-k", "23"))
+    want = {flags: run(prefix, *flags, env=bands, timeout=120) for flags in both}
+    for flags in both:
+        assert len(want[flags].splitlines()) == n * 7
+        assert run(prefix, *flags, "--devices", devices, env=bands, timeout=120) == want[flags]
+        canonical = run(prefix, *flags, "--knn-ties", "canonical", env=bands, timeout=120)
+        assert run(prefix, *flags, "--knn-ties", "canonical", "--devices", devices, env=bands, timeout=120) == canonical
+    for flags in both:
+        assert run(prefix, *flags, "--devices", devices, env={**bands, "SKL_KNN_DECOUPLED": "0"}, timeout=120) == want[flags]
 
 
 # ---- `sketchlib inverted precluster` (SURVEY 8f row f2), as tests/inverted.rs drives it ----
