@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """hipMalloc / hipFree cost on the GPU box (ctypes on libamdhip64, no torch): 0.01-0.2 ms for 16 MB ... 8 GB -- device
-allocations are lazy, so the per-call temporaries of the candidate-list path (capi_aux.cpp) are not worth caching
+allocations are lazy, so the per-call temporaries of the candidate-list path (capi_cand.cpp) are not worth caching
 (round 4: measured before deciding NOT to move them into the context's grow-only scratch)."""
 import ctypes, time
 hip = ctypes.CDLL("libamdhip64.so")

@@ -18,6 +18,8 @@
 #include <algorithm>
 #include <vector>
 
+#include "sketch_plan.hpp"   // cut_before
+
 #if defined(__HIPCC__)
 #define SKL_AA_HD __host__ __device__
 #else
@@ -72,14 +74,8 @@ inline AaPlan aa_plan(const uint64_t *res_begin, size_t n_samples, size_t kmax, 
 inline std::vector<size_t> aa_batches(const uint64_t *res_begin, size_t n_samples, size_t nk, uint64_t num_bins,
                                       uint64_t max_sign_bytes, uint64_t max_residues)
 {
-    const uint64_t per_sample = (uint64_t)nk * num_bins * sizeof(uint64_t);
-    std::vector<size_t> cuts{0};
-    for (size_t s = 0; s < n_samples; ++s) {
-        const size_t b0 = cuts.back();
-        if (s > b0 && ((s + 1 - b0) * per_sample > max_sign_bytes || res_begin[s + 1] - res_begin[b0] > max_residues)) cuts.push_back(s);
-    }
-    cuts.push_back(n_samples);
-    return cuts;
+    return cut_before(n_samples, [&](size_t s) { return res_begin[s + 1] - res_begin[s]; },
+                      CutCaps{max_residues, (uint64_t)nk * num_bins * sizeof(uint64_t), max_sign_bytes});
 }
 
 // The sample whose items [begin[s], begin[s + 1]) hold item t: the last s with begin[s] <= t (samples without items are

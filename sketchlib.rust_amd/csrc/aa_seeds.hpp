@@ -5,6 +5,8 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "nthash.hpp"
+
 namespace skl {
 
 constexpr int AA_N_CODES = 21;   // 0 = separator, then ACDEFGHIKLMNPQRSTVWY
@@ -35,21 +37,13 @@ inline const uint64_t *aa_seed_table(int level)
     return level == 1 ? L1 : level == 2 ? L2 : level == 3 ? L3 : nullptr;
 }
 
-// the split 33 / 31-bit rotation (aahash_iterator.rs:15-21): rotate left by one, then swap bits 0 and 33
-inline uint64_t aa_srol_host(uint64_t v)
-{
-    v = (v << 1) | (v >> 63);
-    const uint64_t x = (v ^ (v >> 33)) & 1;
-    return v ^ (x | (x << 33));
-}
-
 // srol^k of each seed: what a residue contributes when it leaves a window of k (the reference tabulates these values split
 // into a 31-bit and a 33-bit half, indexed by k % 31 and k % 33: aahash_tables.rs:18-35).  srol has period lcm(33, 31) = 1023.
 inline void aa_roll_table(const uint64_t *seeds, size_t k, uint64_t out[AA_N_CODES])
 {
     for (int c = 0; c < AA_N_CODES; ++c) {
         uint64_t v = seeds[c];
-        for (size_t m = 0; m < k % 1023; ++m) v = aa_srol_host(v);
+        for (size_t m = 0; m < k % 1023; ++m) v = srol(v);   // the split rotation, nthash.hpp
         out[c] = v;
     }
 }

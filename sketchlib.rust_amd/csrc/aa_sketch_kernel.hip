@@ -20,36 +20,11 @@
 // Two forms, dealt by aa_plan.hpp: staged (a workgroup per chunk of one long sample: residues, tables and bin minima in
 // LDS) and unstaged (a thread per span of any sample, packed without padding; bins in global memory).
 #include "kernels.h"
+#include "nthash.hpp"   // srol, mod_sign, bin_of
 
 namespace skl {
 
 namespace {
-__device__ __forceinline__ uint64_t aa_srol(uint64_t v)
-{
-    v = (v << 1) | (v >> 63);
-    const uint64_t x = (v ^ (v >> 33)) & 1ull;   // swapbits033, src/hashing/mod.rs:99-103
-    return v ^ (x | (x << 33));
-}
-
-constexpr uint64_t AA_SIGN_MOD = (1ull << 61) - 1;   // src/sketch/mod.rs:36
-__device__ __forceinline__ uint64_t aa_mod_sign(uint64_t h)
-{
-    uint64_t r = (h & AA_SIGN_MOD) + (h >> 61);        // 2^61 = 1 (mod 2^61 - 1)
-    return r >= AA_SIGN_MOD ? r - AA_SIGN_MOD : r;
-}
-
-// bin = sign / bin_size: the reciprocal estimate is off by at most one (relative error 2^-52 on a quotient below 2^32), one
-// exact product settles it
-__device__ __forceinline__ uint32_t aa_bin_of(uint64_t sign, const AaSketchArgs &g, uint32_t last_bin)
-{
-    uint32_t bin = (uint32_t)((double)sign * g.inv_bin_size);
-    if (bin > last_bin) bin = last_bin;
-    const uint64_t prod = (uint64_t)bin * g.bin_size;
-    if (prod > sign) --bin;
-    else if (sign - prod >= g.bin_size && bin < last_bin) ++bin;
-    return bin;
-}
-
 constexpr uint32_t AA_TAB = 21;                                   // residue codes
 constexpr uint32_t AA_PITCH_DW = AA_SPAN_LDS / 4 + 1;             // dwords per staged row: 16 of residues + 1 of padding
 // dwords staged: the chunk, plus what the last thread's windows reach past it (k - 1 <= 255 residues), plus the look-ahead dword
@@ -121,7 +96,7 @@ __global__ __launch_bounds__(AA_WG_LDS) void aahash_binmin_lds_kernel(const AaSk
             uint32_t run = 0;   // valid residues since the last separator
             for (uint32_t i = 0; i + 1u < k; ++i) {
                 const uint32_t c = code_at(x0 + i);
-                fh = aa_srol(fh) ^ tab[c];
+                fh = srol(fh) ^ tab[c];
                 run = c ? run + 1u : 0u;
             }
             // the sample's last window under the end rule: hashed only if the residue before it is valid; for the first
@@ -146,12 +121,12 @@ __global__ __launch_bounds__(AA_WG_LDS) void aahash_binmin_lds_kernel(const AaSk
                     if (j >= n_win) break;
                     const uint32_t old_c = j ? (old_reg >> (8u * jj)) & 0xFFu : 0u;
                     const uint32_t new_c = (new_reg >> (8u * jj)) & 0xFFu;
-                    fh = aa_srol(fh) ^ tab[new_c] ^ rtab[old_c];
+                    fh = srol(fh) ^ tab[new_c] ^ rtab[old_c];
                     run = new_c ? run + 1u : 0u;
                     if (run < k) continue;   // a separator in the window: not hashed into a bin
                     if (ends_here && j + 1u == n_win && (j ? old_c : before_first) == 0u) continue;
-                    const uint64_t sign = aa_mod_sign(fh);
-                    const uint32_t bin = aa_bin_of(sign, g, last_bin);
+                    const uint64_t sign = mod_sign(fh);
+                    const uint32_t bin = bin_of(sign, g.inv_bin_size, g.bin_size, last_bin);
                     if (LDS_BINS) {
                         if (sign < lbins[bin]) atomicMin(&lbins[bin], (unsigned long long)sign);
                     } else {
@@ -207,7 +182,7 @@ __global__ __launch_bounds__(AA_WG_SHORT) void aahash_binmin_kernel(const AaSket
         uint32_t run = 0;
         for (uint32_t i = 0; i + 1u < k; ++i) {
             const uint32_t c = src[p0 + i];
-            fh = aa_srol(fh) ^ s_seed[c];
+            fh = srol(fh) ^ s_seed[c];
             run = c ? run + 1u : 0u;
         }
         const bool ends_here = g.end_rule && p0 + n_win == n_starts;
@@ -215,15 +190,15 @@ __global__ __launch_bounds__(AA_WG_SHORT) void aahash_binmin_kernel(const AaSket
         uint32_t before = ends_here && p0 != 0u ? src[p0 - 1u] : 0u;   // the residue before window j
         for (uint32_t j = 0; j < n_win; ++j) {
             const uint32_t new_c = src[p0 + j + k - 1u];
-            fh = aa_srol(fh) ^ s_seed[new_c] ^ s_roll[old_c];
+            fh = srol(fh) ^ s_seed[new_c] ^ s_roll[old_c];
             run = new_c ? run + 1u : 0u;
             const uint32_t leaving_next = src[p0 + j];
             const bool skip_last = ends_here && j + 1u == n_win && before == 0u;
             old_c = leaving_next;
             before = leaving_next;
             if (run < k || skip_last) continue;
-            const uint64_t sign = aa_mod_sign(fh);
-            const uint32_t bin = aa_bin_of(sign, g, last_bin);
+            const uint64_t sign = mod_sign(fh);
+            const uint32_t bin = bin_of(sign, g.inv_bin_size, g.bin_size, last_bin);
             if (sign < bins[bin]) atomicMin((unsigned long long *)&bins[bin], (unsigned long long)sign);
         }
     }

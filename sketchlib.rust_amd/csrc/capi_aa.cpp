@@ -3,10 +3,10 @@
 #include "capi_internal.hpp"
 
 #include <algorithm>
-#include <memory>
 #include <cstring>
 
 #include "aa_seeds.hpp"
+#include "nthash.hpp"
 
 using namespace skl;
 
@@ -84,7 +84,7 @@ static int sketch_signs_aa_impl(skl_ctx *ctx, const uint8_t *residues, const uin
     a.seeds = ds + at_seed;
     a.roll = ds + at_roll;
     a.num_bins = num_bins;
-    a.bin_size = (((1ull << 61) - 1) + num_bins - 1) / num_bins;   // SIGN_MOD.div_ceil(num_bins), sketch/mod.rs:170
+    a.bin_size = bin_size_of(num_bins);
     a.inv_bin_size = 1.0 / (double)a.bin_size;
     a.end_rule = concat_end_rule ? 1u : 0u;
     a.short_span = plan.short_span;
@@ -133,14 +133,7 @@ static int sketch_signs_aa_impl(skl_ctx *ctx, const uint8_t *residues, const uin
                        : any_staged               ? staged_name
                                                   : unstaged_name;
     if (fin) ctx->last_kernel += std::string(" + ") + finish_kernel_name(ctx, num_bins);
-    if (ctx->scratch_bytes[SCRATCH_SKETCH_BASES] + ctx->scratch_bytes[SCRATCH_SKETCH_SIGNS] > (1ull << 30)) {   // as skl_sketch_signs
-        for (int slot : {SCRATCH_SKETCH_BASES, SCRATCH_SKETCH_SIGNS}) {
-            if (ctx->scratch[slot]) HIP_TRY(hipFree(ctx->scratch[slot]));
-            ctx->scratch[slot] = nullptr;
-            ctx->scratch_bytes[slot] = 0;
-        }
-    }
-    return SKL_OK;
+    return sketch_scratch_release(ctx, false);
 }
 
 extern "C" int skl_sketch_signs_aa(skl_ctx *ctx, const uint8_t *residues, const uint64_t *res_begin, size_t n_samples,
@@ -158,15 +151,11 @@ extern "C" int skl_sketch_usigs_aa(skl_ctx *ctx, const uint8_t *residues, const 
     SKL_TRY(ctx_bind(ctx));
     if (!out_usigs || !out_flags) return fail(SKL_ERR_INVALID_ARG, "null argument");
     SKL_TRY(finish_check_bins(num_bins));
-    const FinishDest dst{out_usigs, out_first_sign, out_flags};
-    if (!ctx->knobs.sketch_finish_host) {
-        return sketch_signs_aa_impl(ctx, residues, res_begin, n_samples, kmers, nk, num_bins, level, concat_end_rule, nullptr, &dst);
-    }
-    std::unique_ptr<uint64_t[]> signs(new uint64_t[std::max<size_t>(n_samples * nk * num_bins, 1)]);   // (not zero-filled: the call writes every word)
-    SKL_TRY(sketch_signs_aa_impl(ctx, residues, res_begin, n_samples, kmers, nk, num_bins, level, concat_end_rule, signs.get(), nullptr));
-    finish_on_host(signs.get(), n_samples * nk, num_bins, dst, false);
-    ctx->last_kernel += std::string(" + ") + finish_kernel_name(ctx, num_bins);
-    return SKL_OK;
+    return sketch_finished_call(ctx, n_samples * nk, num_bins, FinishDest{out_usigs, out_first_sign, out_flags},
+                                [&](uint64_t *signs, const FinishDest *fin) {
+                                    return sketch_signs_aa_impl(ctx, residues, res_begin, n_samples, kmers, nk, num_bins, level,
+                                                                concat_end_rule, signs, fin);
+                                });
 }
 
 // the shapes a caller (and the tests) can ask for

@@ -1,5 +1,5 @@
 // capi_finish.cpp -- finishing streams of bin minima: skl_sketch_finish / skl_sketch_finish_u16 of
-// include/sketchlib_dist.h and the pieces skl_sketch_usigs_packed, skl_sketch_bins_u16_packed (capi_aux.cpp) and
+// include/sketchlib_dist.h and the pieces skl_sketch_usigs_packed, skl_sketch_bins_u16_packed (capi_sketch.cpp) and
 // skl_sketch_usigs_aa (capi_aa.cpp) put behind each batch's bin-minimum launches.  A destination with bins_u16 set asks for
 // the u16 form (an inverted index's rows, any num_bins); otherwise the 14 planes (multiples of 64).  Kernel: sketch_finish.hip; launch rules, flag bits and the host form of the two steps: finish_plan.hpp (pure).
 #include "capi_internal.hpp"

@@ -6,8 +6,8 @@
 //   capi_sketches.cpp  slabs, parameter checks, the operand / epilogue fields of a launch
 //   capi_eb.cpp        the early break's sample and the decisions a context keeps
 //   capi_dense.cpp     one pair-kernel launch, the dense executors and entry points
-//   capi_knn.cpp       the kNN drivers;  capi_aux.cpp  candidate lists and sketching;  capi_pairs.cpp  pair lists
-//   capi_inv.cpp       inverted query;  capi_reads.cpp  read survivors;  capi_aa.cpp  amino-acid sketching
+//   capi_knn.cpp       the kNN drivers;  capi_cand.cpp  candidate lists;  capi_pairs.cpp  pair lists;  capi_rccl.cpp  the RCCL gather
+//   capi_sketch.cpp    DNA sketching;  capi_reads.cpp  read survivors;  capi_aa.cpp  amino-acid sketching;  capi_inv.cpp  inverted query
 //   capi_finish.cpp    finishing sketch streams on the device;  capi_slab.cpp  new slabs from resident ones
 //   capi_within.cpp    the pairs of a dense call that lie within a distance cap
 // Everything declared here is SKL_INTERNAL (hidden): the library exports the functions of the public header and nothing else of the host layer.
@@ -19,7 +19,9 @@
 
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <map>
+#include <memory>
 #include <mutex>
 #include <set>
 #include <string>
@@ -257,3 +259,22 @@ SKL_INTERNAL int finish_fallback(const uint64_t *d_signs, uint64_t n_streams, ui
 // every stream (or only those flagged FINISH_UNFINISHED) of host signs [n_streams][num_bins] on host threads
 SKL_INTERNAL void finish_on_host(const uint64_t *signs, uint64_t n_streams, uint64_t num_bins, const FinishDest &dst, bool only_unfinished);
 SKL_INTERNAL const char *finish_kernel_name(const skl_ctx *ctx, uint64_t num_bins, bool u16 = false);   // what skl_ctx_last_kernel() says of the finish
+
+// ---- shared by the sketching entry points (capi_sketch.cpp, capi_aa.cpp) ----
+// The sketching buffers belong to the context so that a run of sketch calls does not allocate per call -- but beyond 1 GiB they
+// would sit in the way of what follows (the kNN drivers size their bands by the free memory): released, with the pinned ring of
+// the DNA upload when asked.  Both streams must be idle.
+SKL_INTERNAL int sketch_scratch_release(skl_ctx *ctx, bool pinned_ring);
+// A sketching call whose `streams` streams come back finished in dst.  impl(out_signs, fin) is the call itself: finished on the
+// device behind each batch's bin minima (out_signs null, fin = &dst), or -- SKL_SKETCH_FINISH=host -- its signs come back
+// (fin null) and host threads finish them, as callers did before.
+template <class Impl>
+inline int sketch_finished_call(skl_ctx *ctx, size_t streams, uint64_t num_bins, const FinishDest &dst, const Impl &impl)
+{
+    if (!ctx->knobs.sketch_finish_host) return impl(nullptr, &dst);
+    std::unique_ptr<uint64_t[]> signs(new uint64_t[std::max<size_t>(streams * num_bins, 1)]);   // (not zero-filled: the call writes every word)
+    SKL_TRY(impl(signs.get(), nullptr));
+    finish_on_host(signs.get(), streams, num_bins, dst, false);
+    ctx->last_kernel += std::string(" + ") + finish_kernel_name(ctx, num_bins, dst.bins_u16 != nullptr);
+    return SKL_OK;
+}

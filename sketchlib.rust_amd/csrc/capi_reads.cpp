@@ -1,12 +1,14 @@
 // capi_reads.cpp -- the entry points of include/sketchlib_dist.h for read sketching with a count filter: a
 // device-resident batch of read sets (skl_reads) and the survivors of a range of window starts under a threshold
-// table.  Kernel: read_survivors.hip.  The filter itself is replayed by the caller
+// table.  Kernel: read_survivors.hip; its span table: sketch_plan.hpp.  The filter itself is replayed by the caller
 // (csrc/host/read_filter.hpp).
 #include "capi_internal.hpp"
 
 #include <algorithm>
 #include <cstring>
 #include <vector>
+
+#include "nthash.hpp"
 
 using namespace skl;
 
@@ -24,16 +26,6 @@ struct skl_reads {
     const uint64_t *top_f = nullptr, *top_r = nullptr;
     const uint32_t *kmers = nullptr;
 };
-
-namespace {
-inline uint64_t r_rotl1(uint64_t v) { return (v << 1) | (v >> 63); }
-inline uint64_t r_srol(uint64_t v)
-{
-    v = r_rotl1(v);
-    const uint64_t x = (v ^ (v >> 33)) & 1;   // swapbits033, src/hashing/mod.rs:99-103
-    return v ^ (x | (x << 33));
-}
-}  // namespace
 
 extern "C" int skl_reads_create(skl_ctx *ctx, const uint32_t *packed, const uint64_t *code_begin, const uint64_t *offsets,
                                 const uint64_t *offset_begin, size_t n_samples, const size_t *kmers, size_t nk,
@@ -64,22 +56,12 @@ extern "C" int skl_reads_create(skl_ctx *ctx, const uint32_t *packed, const uint
         word_begin[s] = words;
         words += (code_begin[s + 1] - code_begin[s] + 15) / 16;
     }
-    static const uint64_t seeds_f[4] = {0x3c8bfbb395c60474ull, 0x3193c18562a02b4cull, 0x295549f54be24456ull,
-                                        0x20323ed082572324ull};   // src/hashing/nthash_tables.rs:4-16
     std::vector<uint64_t> top(8 * nk);
     std::vector<uint32_t> k32(nk);
     for (size_t ki = 0; ki < nk; ++ki) {
         if (kmers[ki] == 0 || kmers[ki] > 0xFFFFu) return fail(SKL_ERR_INVALID_ARG, "k-mer length out of range");
         k32[ki] = (uint32_t)kmers[ki];
-        for (int b = 0; b < 4; ++b) {
-            uint64_t f = seeds_f[b], r = seeds_f[b ^ 2];
-            for (size_t m = 1; m < kmers[ki]; ++m) {
-                f = r_srol(f);
-                r = r_srol(r);
-            }
-            top[ki * 4 + b] = f;
-            top[4 * nk + ki * 4 + b] = r;
-        }
+        nthash_top_tables(kmers[ki], top.data() + ki * 4, top.data() + 4 * nk + ki * 4);
     }
     // layout in u64 words
     const size_t w_packed = (std::max<uint64_t>(words, 1) + 1) / 2;
@@ -152,16 +134,7 @@ extern "C" int skl_reads_survivors(skl_reads *r, const uint64_t *win_begin, cons
         return fail(SKL_ERR_INVALID_ARG, "null argument");
     }
     const size_t n = r->n_samples, nk = r->nk, streams = n * nk;
-    const uint64_t span = (uint64_t)read_survivor_span();
-    std::vector<uint64_t> head(3 * n + 1, 0);   // win_begin | win_end | span_begin
-    for (size_t s = 0; s < n; ++s) {
-        const uint64_t len = r->code_begin[s + 1] - r->code_begin[s];
-        const uint64_t b = std::min(win_begin[s], len), e = std::max(b, std::min(win_end[s], len));
-        head[s] = b;
-        head[n + s] = e;
-        const uint64_t spans = ((e - b + span - 1) / span + 63) / 64 * 64;   // whole waves per sample
-        head[2 * n + s + 1] = head[2 * n + s] + spans;
-    }
+    const std::vector<uint64_t> head = read_survivor_spans(r->code_begin.data(), win_begin, win_end, n);   // win_begin | win_end | span_begin
     const uint64_t n_spans = head[3 * n];
     if (capacity > (1ull << 40) / std::max<size_t>(streams, 1)) return fail(SKL_ERR_INVALID_ARG, "capacity too large");
     const size_t at_counts = 3 * n + 1, at_thr = at_counts + streams, at_surv = at_thr + streams * r->num_bins;
@@ -194,7 +167,7 @@ extern "C" int skl_reads_survivors(skl_reads *r, const uint64_t *win_begin, cons
     a.top_f = r->top_f;
     a.top_r = r->top_r;
     a.num_bins = r->num_bins;
-    a.bin_size = (((1ull << 61) - 1) + r->num_bins - 1) / r->num_bins;   // SIGN_MOD.div_ceil(num_bins), sketch/mod.rs:170
+    a.bin_size = bin_size_of(r->num_bins);
     a.inv_bin_size = 1.0 / (double)a.bin_size;
     a.rc = r->rc;
     a.thresholds = d + at_thr;

@@ -13,8 +13,7 @@ namespace skl_host {
 
 namespace {
 
-using skl::aa_srol_host;
-inline uint64_t srol(uint64_t v) { return aa_srol_host(v); }
+using skl::srol;   // the split rotation (nthash.hpp)
 
 const std::array<uint8_t, 256> &code_table()
 {
@@ -104,7 +103,7 @@ bool aa_bin_minima(const uint8_t *codes, size_t len, size_t k, int level, bool e
     const uint64_t *seeds = aa_seeds(level);
     uint64_t roll[AA_CODES];
     aa_roll_values(level, k, roll);
-    const uint64_t bin_size = (SIGN_MOD + num_bins - 1) / num_bins;
+    const uint64_t bin_size = skl::bin_size_of(num_bins);
     // A separator has seed 0 and roll value 0, so the hash rolled straight through one is still the XOR of srol^distance(seed)
     // over the window's valid residues: exact for every window of k valid residues, and nothing is re-seeded.
     uint64_t fh = 0;

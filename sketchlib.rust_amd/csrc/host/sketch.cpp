@@ -20,23 +20,11 @@ namespace skl_host {
 
 namespace {
 
-// src/hashing/nthash_tables.rs:4-16
-const uint64_t HASH_LOOKUP[4] = {0x3c8bfbb395c60474ull, 0x3193c18562a02b4cull, 0x295549f54be24456ull,
-                                 0x20323ed082572324ull};
-const uint64_t RC_HASH_LOOKUP[4] = {0x295549f54be24456ull, 0x20323ed082572324ull, 0x3c8bfbb395c60474ull,
-                                    0x3193c18562a02b4cull};
-
-inline uint64_t rotl1(uint64_t v) { return (v << 1) | (v >> 63); }
-inline uint64_t rotr1(uint64_t v) { return (v >> 1) | (v << 63); }
-// swapbits033, src/hashing/mod.rs:99-103
-inline uint64_t swapbits033(uint64_t v)
-{
-    const uint64_t x = (v ^ (v >> 33)) & 1;
-    return v ^ (x | (x << 33));
-}
-// the split rotation ntHash rolls with (nthash_iterator.rs:368-370) and its inverse
-inline uint64_t srol(uint64_t v) { return swapbits033(rotl1(v)); }
-inline uint64_t sror(uint64_t v) { return rotr1(swapbits033(v)); }
+using skl::srol;   // the split rotation ntHash rolls with (nthash_iterator.rs:368-370) and its inverse: nthash.hpp
+using skl::sror;
+// src/hashing/nthash_tables.rs:4-16, as tables for the loops below
+const uint64_t HASH_LOOKUP[4] = {skl::hash_fwd(0), skl::hash_fwd(1), skl::hash_fwd(2), skl::hash_fwd(3)};
+const uint64_t RC_HASH_LOOKUP[4] = {skl::hash_rc(0), skl::hash_rc(1), skl::hash_rc(2), skl::hash_rc(3)};
 
 inline bool valid_base(uint8_t b)
 {
@@ -229,14 +217,7 @@ bool for_each_window(const Sequence &seq, size_t k, bool rc, F &&f)
     const size_t n = seq.codes.size();
     // srol^(k-1) of each seed: the weight of the oldest base (forward) / newest base (reverse)
     uint64_t top_f[4], top_r[4];
-    for (int b = 0; b < 4; ++b) {
-        top_f[b] = HASH_LOOKUP[b];
-        top_r[b] = RC_HASH_LOOKUP[b];
-        for (size_t m = 1; m < k; ++m) {
-            top_f[b] = srol(top_f[b]);
-            top_r[b] = srol(top_r[b]);
-        }
-    }
+    skl::nthash_top_tables(k, top_f, top_r);
     size_t off_idx = 0;
     size_t start = 0;
     bool any = false;
@@ -276,7 +257,7 @@ bool for_each_window(const Sequence &seq, size_t k, bool rc, F &&f)
 void bin_minima(const Sequence &seq, size_t k, bool rc, std::vector<uint64_t> &signs)
 {
     const uint64_t num_bins = signs.size();
-    const uint64_t bin_size = (SIGN_MOD + num_bins - 1) / num_bins;
+    const uint64_t bin_size = skl::bin_size_of(num_bins);
     if (seq.codes.size() < k) throw std::runtime_error("K-mer larger than smallest valid sequence");
     const bool any = for_each_window(seq, k, rc, [&](size_t, uint64_t sign) {
         uint64_t &slot = signs[sign / bin_size];
@@ -392,7 +373,7 @@ SketchResult sketch_sample(const InputFastx &input, const std::vector<size_t> &k
     if (total == 0) throw std::runtime_error(input.first + " has no valid sequence");
     const uint64_t ss64 = (sketch_size + 63) / 64;  // num_bins, sketch/mod.rs:49-54
     const uint64_t num_bins = ss64 * 64;
-    const uint64_t bin_size = (SIGN_MOD + num_bins - 1) / num_bins;
+    const uint64_t bin_size = skl::bin_size_of(num_bins);
     SketchResult out;
     out.usigs.assign((size_t)(ss64 * BBITS * kmers.size()), 0);
     bool densified = false;
@@ -445,7 +426,7 @@ std::vector<uint16_t> sketch_sample_inverted(const InputFastx &input, size_t k, 
     if (total == 0) throw std::runtime_error(input.first + " has no valid sequence");
     std::vector<uint64_t> signs((size_t)sketch_size, UINT64_MAX);   // exactly sketch_size bins, inverted.rs:352-357
     if (seq.reads) {   // every window through the count filter, in stream order (inverted.rs:348-361, as sketch_sample)
-        const uint64_t bin_size = (SIGN_MOD + sketch_size - 1) / sketch_size;
+        const uint64_t bin_size = skl::bin_size_of(sketch_size);
         KmerFilter filter(min_count);
         const bool any = for_each_window(seq, k, rc, [&](size_t, uint64_t sign) { offer_sign(signs.data(), bin_size, filter, sign); });
         check_read_signs(any, signs, input.first, k, min_count);

@@ -11,11 +11,12 @@
 #include <utility>
 #include <vector>
 
+#include "../nthash.hpp"
 #include "multisketch.hpp"
 
 namespace skl_host {
 
-constexpr uint64_t SIGN_MOD = (1ull << 61) - 1;  // src/sketch/mod.rs:36
+using skl::SIGN_MOD;   // src/sketch/mod.rs:36 (nthash.hpp)
 
 // (sample name, sequence files), one entry per sample (src/io.rs:20-40, rfile parsing)
 using InputFastx = std::pair<std::string, std::vector<std::string>>;

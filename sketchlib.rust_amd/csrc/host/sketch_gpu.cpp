@@ -14,10 +14,10 @@
 #include <cstring>
 #include <exception>
 #include <memory>
-#include <mutex>
 #include <stdexcept>
 #include <thread>
 
+#include "../sketch_plan.hpp"
 #include "aahash.hpp"
 #include "distances.hpp"
 #include "inverted.hpp"
@@ -45,28 +45,97 @@ void parallel_for(size_t n, size_t threads, F f)
     for (auto &t : pool) t.join();
 }
 
-// one sample's one-byte codes -> ceil(len / 16) u32 words, code c at bits 2 (c % 16) of word c / 16
-void pack_codes(const std::vector<uint8_t> &c, uint32_t *out)
+// f(i) for every i < n on host threads; the message of what f(i) threw is kept per i ("": nothing)
+template <class F>
+std::vector<std::string> try_each(size_t n, size_t threads, F f)
 {
-    const size_t whole = c.size() / 16;
-    for (size_t w = 0; w < whole; ++w) {
-        uint64_t lo, hi;
-        memcpy(&lo, c.data() + 16 * w, 8);
-        memcpy(&hi, c.data() + 16 * w + 8, 8);
-        auto squeeze = [](uint64_t v) -> uint32_t {   // 8 bytes of 2 significant bits -> 16 bits
-            v &= 0x0303030303030303ull;
-            v = (v | (v >> 6)) & 0x000F000F000F000Full;
-            v = (v | (v >> 12)) & 0x000000FF000000FFull;
-            v = (v | (v >> 24)) & 0xFFFFull;
-            return (uint32_t)v;
-        };
-        out[w] = squeeze(lo) | (squeeze(hi) << 16);
+    std::vector<std::string> error(n);
+    parallel_for(n, threads, [&](size_t i) {
+        try {
+            f(i);
+        } catch (const std::exception &e) {
+            error[i] = e.what();
+            if (error[i].empty()) error[i] = "unreadable input";
+        }
+    });
+    return error;
+}
+
+// the first error in input order: what the CPU path reports on one thread
+void raise_first(const std::vector<std::string> &error)
+{
+    for (const auto &e : error) {
+        if (!e.empty()) throw std::runtime_error(e);
     }
-    if (c.size() % 16) {
-        uint32_t word = 0;
-        for (size_t x = 16 * whole; x < c.size(); ++x) word |= (uint32_t)(c[x] & 3u) << (2u * (uint32_t)(x - 16 * whole));
-        out[whole] = word;
+}
+
+uint64_t valid_bases(const Sequence &s) { return s.acgt[0] + s.acgt[1] + s.acgt[2] + s.acgt[3]; }
+
+// 1. parse (threads): every input into seqs, every input's error kept
+std::vector<std::string> parse_inputs(const std::vector<InputFastx> &inputs, uint8_t min_qual, size_t threads, std::vector<Sequence> &seqs)
+{
+    seqs.assign(inputs.size(), Sequence());
+    return try_each(inputs.size(), threads, [&](size_t i) {
+        load_sample(inputs[i], min_qual, seqs[i]);
+        if (valid_bases(seqs[i]) == 0) throw std::runtime_error(inputs[i].first + " has no valid sequence");
+    });
+}
+
+// The batches [b0, b1) of items 0 .. n - 1 that sketch_plan.hpp cut_before cuts under `caps` (none for n = 0).
+template <class SizeOf>
+std::vector<std::pair<size_t, size_t>> batches(size_t n, SizeOf size_of, const skl::CutCaps &caps)
+{
+    std::vector<std::pair<size_t, size_t>> out;
+    const std::vector<size_t> cuts = skl::cut_before(n, size_of, caps);
+    for (size_t b = 0; n && b + 1 < cuts.size(); ++b) out.push_back({cuts[b], cuts[b + 1]});
+    return out;
+}
+
+// The samples seqs[idx[0 .. nb)] as the input of one library call: the bases at 2 bits each, 16 per word, every sample on a word
+// boundary (skl_sketch_signs_packed) -- a quarter of the bytes to gather here and to send over PCIe -- packed on host threads.
+struct PackedBatch {
+    std::vector<uint64_t> code_begin, word_begin, offset_begin, offsets;
+    std::unique_ptr<uint32_t[]> packed;   // not zero-filled
+};
+PackedBatch gather_and_pack(const std::vector<Sequence> &seqs, const size_t *idx, size_t nb, size_t threads)
+{
+    PackedBatch p;
+    p.code_begin.assign(nb + 1, 0);
+    p.word_begin.assign(nb + 1, 0);
+    p.offset_begin.assign(nb + 1, 0);
+    for (size_t i = 0; i < nb; ++i) {
+        const Sequence &s = seqs[idx[i]];
+        p.code_begin[i + 1] = p.code_begin[i] + s.codes.size();
+        p.word_begin[i + 1] = p.word_begin[i] + (s.codes.size() + 15) / 16;
+        p.offsets.insert(p.offsets.end(), s.offsets.begin(), s.offsets.end());
+        p.offset_begin[i + 1] = p.offsets.size();
     }
+    p.packed.reset(new uint32_t[std::max<uint64_t>(p.word_begin[nb], 1)]);
+    parallel_for(nb, threads, [&](size_t i) {
+        const std::vector<uint8_t> &c = seqs[idx[i]].codes;
+        skl::pack_codes(c.data(), c.size(), p.packed.get() + p.word_begin[i]);
+    });
+    return p;
+}
+
+SketchMeta make_meta(const std::string &name, size_t at, bool rc, bool reads, uint64_t seq_length, bool densified, const uint64_t *acgt,
+                     uint64_t non_acgt)
+{
+    SketchMeta m;
+    m.name = name;
+    m.rc = rc;
+    m.reads = reads;
+    m.seq_length = seq_length;
+    m.densified = densified;
+    for (int x = 0; acgt && x < 4; ++x) m.acgt[x] = acgt[x];
+    m.non_acgt = non_acgt;
+    m.index = at;
+    return m;
+}
+// ... of a DNA sample, from the densified signs[0] of each of its k-mer lengths
+SketchMeta dna_meta(const std::string &name, size_t at, const Sequence &s, bool rc, bool densified, const std::vector<uint64_t> &first_signs)
+{
+    return make_meta(name, at, rc, s.reads, s.reads ? reads_seq_length(first_signs) : valid_bases(s), densified, s.acgt, s.non_acgt);
 }
 
 struct ReadsTiming {
@@ -84,26 +153,18 @@ void reads_signs_gpu(Device &dev, const std::vector<Sequence> &seqs, const std::
                      std::vector<uint64_t> &signs, std::vector<char> &any_window, ReadsTiming &tm)
 {
     const size_t nk = kmers.size(), streams = idx.size() * nk;
-    const uint64_t bin_size = (SIGN_MOD + num_bins - 1) / num_bins;
+    const uint64_t bin_size = skl::bin_size_of(num_bins);
     const bool log_chunks = std::getenv("SKL_CLI_TIMING") != nullptr;
     uint64_t cap_len = 1ull << 20;
     if (const char *e = std::getenv("SKL_READS_CHUNK_WINDOWS")) cap_len = std::max<uint64_t>(1, std::strtoull(e, nullptr, 10));
     signs.assign(streams * num_bins, UINT64_MAX);
     any_window.assign(streams, 0);
-    std::vector<uint64_t> code_begin(idx.size() + 1, 0), word_begin(idx.size() + 1, 0), offset_begin(idx.size() + 1, 0), offsets;
+    const PackedBatch in = gather_and_pack(seqs, idx.data(), idx.size(), threads);
+    const std::vector<uint64_t> &code_begin = in.code_begin;
     uint64_t max_len = 0;
-    for (size_t i = 0; i < idx.size(); ++i) {
-        const Sequence &s = seqs[idx[i]];
-        code_begin[i + 1] = code_begin[i] + s.codes.size();
-        word_begin[i + 1] = word_begin[i] + (s.codes.size() + 15) / 16;
-        offsets.insert(offsets.end(), s.offsets.begin(), s.offsets.end());
-        offset_begin[i + 1] = offsets.size();
-        max_len = std::max<uint64_t>(max_len, s.codes.size());
-    }
-    std::vector<uint32_t> packed(std::max<uint64_t>(word_begin[idx.size()], 1));
-    parallel_for(idx.size(), threads, [&](size_t i) { pack_codes(seqs[idx[i]].codes, packed.data() + word_begin[i]); });
+    for (size_t i = 0; i < idx.size(); ++i) max_len = std::max(max_len, code_begin[i + 1] - code_begin[i]);
     skl_reads *h = nullptr;
-    if (skl_reads_create(dev.ctx(), packed.data(), code_begin.data(), offsets.data(), offset_begin.data(), idx.size(),
+    if (skl_reads_create(dev.ctx(), in.packed.get(), code_begin.data(), in.offsets.data(), in.offset_begin.data(), idx.size(),
                          kmers.data(), nk, num_bins, rc ? 1 : 0, &h) != SKL_OK) {
         throw std::runtime_error(skl_last_error());
     }
@@ -219,17 +280,7 @@ MultiSketch sketch_files_gpu_aa(Device &dev, const std::string &output_prefix, c
     auto since = [&] { return std::chrono::duration<double>(std::chrono::steady_clock::now() - t_start).count(); };
 
     std::vector<std::vector<AaSample>> per_input(inputs.size());
-    std::vector<std::string> input_error(inputs.size());
-    parallel_for(inputs.size(), threads, [&](size_t i) {
-        try {
-            per_input[i] = load_aa_samples(inputs[i], st.concat_fasta);
-        } catch (const std::exception &e) {
-            input_error[i] = e.what();
-        }
-    });
-    for (const auto &e : input_error) {
-        if (!e.empty()) throw std::runtime_error(e);
-    }
+    raise_first(try_each(inputs.size(), threads, [&](size_t i) { per_input[i] = load_aa_samples(inputs[i], st.concat_fasta); }));
     std::vector<AaSample> samples;
     for (auto &v : per_input) {
         for (auto &a : v) samples.push_back(std::move(a));
@@ -242,17 +293,8 @@ MultiSketch sketch_files_gpu_aa(Device &dev, const std::string &output_prefix, c
     std::vector<uint64_t> bins(sample_words * n, 0);
     std::vector<SketchMeta> meta(n);
     std::vector<std::string> sample_error(n);
-    constexpr uint64_t CALL_RESIDUES = 1ull << 30, CALL_SIGN_BYTES = 1ull << 30;
-    const uint64_t sign_bytes = (uint64_t)nk * num_bins * sizeof(uint64_t);
     std::vector<uint8_t> flags;
-    for (size_t b0 = 0; b0 < n;) {
-        size_t b1 = b0;
-        uint64_t residues_in_call = 0;
-        while (b1 < n && (b1 == b0 || (residues_in_call + samples[b1].codes.size() <= CALL_RESIDUES &&
-                                       (b1 - b0 + 1) * sign_bytes <= CALL_SIGN_BYTES))) {
-            residues_in_call += samples[b1].codes.size();
-            ++b1;
-        }
+    for (const auto &[b0, b1] : batches(n, [&](size_t i) { return samples[i].codes.size(); }, skl::caps_aa_call(nk, num_bins))) {
         const size_t nb = b1 - b0;
         std::vector<uint64_t> res_begin(nb + 1, 0);
         for (size_t i = 0; i < nb; ++i) res_begin[i + 1] = res_begin[i] + samples[b0 + i].codes.size();
@@ -286,21 +328,13 @@ MultiSketch sketch_files_gpu_aa(Device &dev, const std::string &output_prefix, c
                 sample_error[at] = "K-mer larger than smallest valid sequence";   // as the CPU path
                 continue;
             }
-            SketchMeta &m = meta[at];
-            m.name = a.name;
-            m.rc = rc;
-            m.reads = false;
-            m.seq_length = a.codes.size();
-            m.densified = densified;
-            m.non_acgt = a.invalid;
-            m.index = at;
+            meta[at] = make_meta(a.name, at, rc, false, a.codes.size(), densified, nullptr, a.invalid);
         }
         for (size_t at = b0; at < b1; ++at) {   // the first sample in input order that fails, as the CPU path on one thread
             if (!sample_error[at].empty()) throw std::runtime_error(sample_error[at]);
             std::vector<uint8_t>().swap(samples[at].codes);
         }
         t_finish += since() - t1;
-        b0 = b1;
     }
     const double t_before_write = since();
     MultiSketch::write_sketch_data(output_prefix, bins.data(), bins.size());
@@ -331,73 +365,26 @@ MultiSketch sketch_files_gpu(Device &dev, const std::string &output_prefix, cons
     auto since = [&] { return std::chrono::duration<double>(std::chrono::steady_clock::now() - t_start).count(); };
     double t_parse = 0, t_pack = 0, t_gpu = 0, t_finish = 0;
 
-    // 1. parse (threads)
-    std::vector<Sequence> seqs(n);
-    {
-        std::atomic<size_t> next{0};
-        std::string error;
-        std::mutex mu;
-        auto work = [&] {
-            for (;;) {
-                const size_t i = next.fetch_add(1);
-                if (i >= n) break;
-                try {
-                    load_sample(inputs[i], min_qual, seqs[i]);
-                    uint64_t total = 0;
-                    for (uint64_t c : seqs[i].acgt) total += c;
-                    if (total == 0) throw std::runtime_error(inputs[i].first + " has no valid sequence");
-                } catch (const std::exception &e) {
-                    std::lock_guard<std::mutex> lk(mu);
-                    if (error.empty()) error = e.what();
-                }
-            }
-        };
-        std::vector<std::thread> pool;
-        for (size_t t = 1; t < std::max<size_t>(1, std::min(threads, n)); ++t) pool.emplace_back(work);
-        work();
-        for (auto &t : pool) t.join();
-        if (!error.empty()) throw std::runtime_error(error);
-    }
+    std::vector<Sequence> seqs;
+    raise_first(parse_inputs(inputs, min_qual, threads, seqs));
 
     t_parse = since();
     std::vector<uint64_t> bins(sample_words * n, 0);
     std::vector<SketchMeta> meta(n);
     // densify + transpose + metadata of sample `at` from its [nk][num_bins] signs on host threads: read sets under a count
     // filter, whose signs are produced on the host
-    std::string finish_error;
-    std::mutex finish_mu;
     auto finish = [&](size_t at, const uint64_t *sample_signs, const char *any_window) {
-        try {
-            const Sequence &s = seqs[at];
-            bool densified = false;
-            std::vector<uint64_t> first_signs;
-            for (size_t ki = 0; ki < nk; ++ki) {
-                const uint64_t *src = sample_signs + ki * num_bins;
-                std::vector<uint64_t> sg(src, src + num_bins);
-                if (any_window) {
-                    check_read_signs(any_window[ki] != 0, sg, inputs[at].first, kmers[ki], min_count);
-                } else if (std::all_of(sg.begin(), sg.end(), [](uint64_t v) { return v == UINT64_MAX; })) {
-                    throw std::runtime_error("K-mer larger than smallest valid sequence");   // as the CPU path
-                }
-                densified |= densify_bin(sg);
-                first_signs.push_back(sg[0]);
-                fill_usigs(bins.data() + at * sample_words + ki * ss64 * BBITS, sg);
-            }
-            SketchMeta &m = meta[at];
-            m.name = inputs[at].first;
-            m.rc = rc;
-            m.reads = s.reads;
-            uint64_t total = 0;
-            for (uint64_t c : s.acgt) total += c;
-            m.seq_length = s.reads ? reads_seq_length(first_signs) : total;
-            m.densified = densified;
-            for (int x = 0; x < 4; ++x) m.acgt[x] = s.acgt[x];
-            m.non_acgt = s.non_acgt;
-            m.index = at;
-        } catch (const std::exception &e) {
-            std::lock_guard<std::mutex> lk(finish_mu);
-            if (finish_error.empty()) finish_error = e.what();
+        bool densified = false;
+        std::vector<uint64_t> first_signs;
+        for (size_t ki = 0; ki < nk; ++ki) {
+            const uint64_t *src = sample_signs + ki * num_bins;
+            std::vector<uint64_t> sg(src, src + num_bins);
+            check_read_signs(any_window[ki] != 0, sg, inputs[at].first, kmers[ki], min_count);
+            densified |= densify_bin(sg);
+            first_signs.push_back(sg[0]);
+            fill_usigs(bins.data() + at * sample_words + ki * ss64 * BBITS, sg);
         }
+        meta[at] = dna_meta(inputs[at].first, at, seqs[at], rc, densified, first_signs);
     };
     // read sets under a count filter go their own way; assemblies (and read sets without one) take the bin-minimum kernel and
     // the finish kernel behind it
@@ -405,27 +392,9 @@ MultiSketch sketch_files_gpu(Device &dev, const std::string &output_prefix, cons
     for (size_t i = 0; i < n; ++i) (seqs[i].reads && min_count >= 2 ? filtered : plain).push_back(i);
 
     // 2. hash + bin minima + densify + transpose on the device, in batches of at most ~4 G bases
-    constexpr uint64_t BATCH_CODES = 4ull << 30;
-    for (size_t b0 = 0; b0 < plain.size();) {
-        size_t b1 = b0;
-        uint64_t codes_in_batch = 0;
-        while (b1 < plain.size() && (b1 == b0 || codes_in_batch + seqs[plain[b1]].codes.size() <= BATCH_CODES)) {
-            codes_in_batch += seqs[plain[b1]].codes.size();
-            ++b1;
-        }
+    for (const auto &[b0, b1] : batches(plain.size(), [&](size_t i) { return seqs[plain[i]].codes.size(); }, skl::caps_dna_call())) {
         const size_t nb = b1 - b0;
-        // the bases at 2 bits each, 16 per word, every sample on a word boundary (skl_sketch_signs_packed): a quarter of the
-        // bytes to gather here and to send over PCIe
-        std::vector<uint64_t> code_begin(nb + 1, 0), word_begin(nb + 1, 0), offset_begin(nb + 1, 0), offsets;
-        for (size_t i = 0; i < nb; ++i) {
-            const Sequence &s = seqs[plain[b0 + i]];
-            code_begin[i + 1] = code_begin[i] + s.codes.size();
-            word_begin[i + 1] = word_begin[i] + (s.codes.size() + 15) / 16;
-            offsets.insert(offsets.end(), s.offsets.begin(), s.offsets.end());
-            offset_begin[i + 1] = offsets.size();
-        }
-        std::unique_ptr<uint32_t[]> packed(new uint32_t[std::max<uint64_t>(word_begin[nb], 1)]);   // not zero-filled
-        parallel_for(nb, threads, [&](size_t i) { pack_codes(seqs[plain[b0 + i]].codes, packed.get() + word_begin[i]); });
+        const PackedBatch in = gather_and_pack(seqs, plain.data() + b0, nb, threads);
         // Hash, bin minima, densify and transpose on the device.  A batch's finished words are its samples' part of the `.skd`
         // image when the samples are consecutive in input order (always, unless read sets under a count filter lie between them).
         const bool in_place = plain[b1 - 1] - plain[b0] == nb - 1;
@@ -434,34 +403,23 @@ MultiSketch sketch_files_gpu(Device &dev, const std::string &output_prefix, cons
         uint64_t *words = in_place ? bins.data() + plain[b0] * sample_words : staged_words.data();
         const double t0 = since();
         t_pack += t0 - (t_parse + t_pack + t_gpu + t_finish);
-        const int rc_ = skl_sketch_usigs_packed(dev.ctx(), packed.get(), code_begin.data(), offsets.data(), offset_begin.data(),
+        const int rc_ = skl_sketch_usigs_packed(dev.ctx(), in.packed.get(), in.code_begin.data(), in.offsets.data(), in.offset_begin.data(),
                                                 nb, kmers.data(), nk, num_bins, rc ? 1 : 0, words, first_signs.data(), flags.data());
         if (rc_ != SKL_OK) throw std::runtime_error(skl_last_error());
         t_gpu += since() - t0;
         // 3. metadata from the flags and first signs
         for (size_t i = 0; i < nb; ++i) {
             const size_t at = plain[b0 + i];
-            const Sequence &s = seqs[at];
             bool densified = false;
             for (size_t ki = 0; ki < nk; ++ki) {
                 if (flags[i * nk + ki] & SKL_FINISH_EMPTY) throw std::runtime_error("K-mer larger than smallest valid sequence");   // as the CPU path: the first such sample in input order
                 densified |= (flags[i * nk + ki] & SKL_FINISH_DENSIFIED) != 0;
             }
             if (!in_place) memcpy(bins.data() + at * sample_words, words + i * sample_words, sample_words * sizeof(uint64_t));
-            SketchMeta &m = meta[at];
-            m.name = inputs[at].first;
-            m.rc = rc;
-            m.reads = s.reads;
-            uint64_t total = 0;
-            for (uint64_t c : s.acgt) total += c;
-            m.seq_length = s.reads ? reads_seq_length(std::vector<uint64_t>(first_signs.begin() + i * nk, first_signs.begin() + (i + 1) * nk)) : total;
-            m.densified = densified;
-            for (int x = 0; x < 4; ++x) m.acgt[x] = s.acgt[x];
-            m.non_acgt = s.non_acgt;
-            m.index = at;
+            meta[at] = dna_meta(inputs[at].first, at, seqs[at], rc, densified,
+                                std::vector<uint64_t>(first_signs.begin() + i * nk, first_signs.begin() + (i + 1) * nk));
         }
         for (size_t i = b0; i < b1; ++i) Sequence().codes.swap(seqs[plain[i]].codes);   // release
-        b0 = b1;
         t_finish = since() - t_parse - t_pack - t_gpu;
     }
 
@@ -469,24 +427,15 @@ MultiSketch sketch_files_gpu(Device &dev, const std::string &output_prefix, cons
     // max(64, nk) streams (one 24 MiB filter each) and ~1 G bases.
     ReadsTiming rt;
     const double t_reads0 = since();
-    for (size_t b0 = 0; b0 < filtered.size();) {
-        size_t b1 = b0;
-        uint64_t codes_in_batch = 0;
-        while (b1 < filtered.size() &&
-               (b1 == b0 || ((b1 - b0 + 1) * nk <= std::max<size_t>(64, nk) && codes_in_batch + seqs[filtered[b1]].codes.size() <= (1ull << 30)))) {
-            codes_in_batch += seqs[filtered[b1]].codes.size();
-            ++b1;
-        }
+    for (const auto &[b0, b1] : batches(filtered.size(), [&](size_t i) { return seqs[filtered[i]].codes.size(); }, skl::caps_filtered_reads(nk))) {
         const std::vector<size_t> idx(filtered.begin() + b0, filtered.begin() + b1);
         std::vector<uint64_t> signs;
         std::vector<char> any_window;
         reads_signs_gpu(dev, seqs, idx, kmers, num_bins, rc, min_count, threads, signs, any_window, rt);
-        parallel_for(idx.size(), threads, [&](size_t i) {
+        raise_first(try_each(idx.size(), threads, [&](size_t i) {
             finish(idx[i], signs.data() + i * nk * num_bins, any_window.data() + i * nk);
-        });
-        if (!finish_error.empty()) throw std::runtime_error(finish_error);
+        }));
         for (size_t i : idx) Sequence().codes.swap(seqs[i].codes);   // release
-        b0 = b1;
     }
     const double t_reads = since() - t_reads0;
 
@@ -522,20 +471,8 @@ std::vector<std::vector<uint16_t>> sketch_inverted_gpu(Device &dev, const std::v
     auto since = [&] { return std::chrono::duration<double>(std::chrono::steady_clock::now() - t_start).count(); };
     double t_pack = 0, t_device = 0;
 
-    // 1. parse (threads)
-    std::vector<Sequence> seqs(n);
-    std::vector<std::string> error(n);
-    parallel_for(n, threads, [&](size_t i) {
-        try {
-            load_sample(inputs[i], min_qual, seqs[i]);
-            uint64_t total = 0;
-            for (uint64_t c : seqs[i].acgt) total += c;
-            if (total == 0) throw std::runtime_error(inputs[i].first + " has no valid sequence");
-        } catch (const std::exception &e) {
-            error[i] = e.what();
-            if (error[i].empty()) error[i] = "unreadable input";
-        }
-    });
+    std::vector<Sequence> seqs;
+    std::vector<std::string> error = parse_inputs(inputs, min_qual, threads, seqs);
     const double t_parse = since();
     std::vector<std::vector<uint16_t>> out(n);
     // read sets under a count filter go their own way; assemblies (and read sets without one) take the bin-minimum kernel and
@@ -546,32 +483,15 @@ std::vector<std::vector<uint16_t>> sketch_inverted_gpu(Device &dev, const std::v
     }
 
     // 2. hash + bin minima + densify + u16 on the device, in batches of at most ~4 G bases and 1 GiB of signs on the device
-    constexpr uint64_t BATCH_CODES = 4ull << 30, BATCH_SIGN_BYTES = 1ull << 30;
-    for (size_t b0 = 0; b0 < plain.size();) {
+    for (const auto &[b0, b1] : batches(plain.size(), [&](size_t i) { return seqs[plain[i]].codes.size(); }, skl::caps_u16_call(S))) {
         const double p0 = since();
-        size_t b1 = b0;
-        uint64_t codes_in_batch = 0;
-        while (b1 < plain.size() && (b1 == b0 || (codes_in_batch + seqs[plain[b1]].codes.size() <= BATCH_CODES &&
-                                                  (b1 - b0 + 1) * S * sizeof(uint64_t) <= BATCH_SIGN_BYTES))) {
-            codes_in_batch += seqs[plain[b1]].codes.size();
-            ++b1;
-        }
         const size_t nb = b1 - b0;
-        std::vector<uint64_t> code_begin(nb + 1, 0), word_begin(nb + 1, 0), offset_begin(nb + 1, 0), offsets;
-        for (size_t i = 0; i < nb; ++i) {
-            const Sequence &s = seqs[plain[b0 + i]];
-            code_begin[i + 1] = code_begin[i] + s.codes.size();
-            word_begin[i + 1] = word_begin[i] + (s.codes.size() + 15) / 16;
-            offsets.insert(offsets.end(), s.offsets.begin(), s.offsets.end());
-            offset_begin[i + 1] = offsets.size();
-        }
-        std::unique_ptr<uint32_t[]> packed(new uint32_t[std::max<uint64_t>(word_begin[nb], 1)]);   // not zero-filled
-        parallel_for(nb, threads, [&](size_t i) { pack_codes(seqs[plain[b0 + i]].codes, packed.get() + word_begin[i]); });
+        const PackedBatch in = gather_and_pack(seqs, plain.data() + b0, nb, threads);
         std::vector<uint16_t> rows(nb * S);
         std::vector<uint8_t> flags(nb, 0);
         const double d0 = since();
         t_pack += d0 - p0;
-        if (skl_sketch_bins_u16_packed(dev.ctx(), packed.get(), code_begin.data(), offsets.data(), offset_begin.data(), nb, k, S,
+        if (skl_sketch_bins_u16_packed(dev.ctx(), in.packed.get(), in.code_begin.data(), in.offsets.data(), in.offset_begin.data(), nb, k, S,
                                        rc ? 1 : 0, rows.data(), flags.data()) != SKL_OK) {
             throw std::runtime_error(skl_last_error());
         }
@@ -585,22 +505,14 @@ std::vector<std::vector<uint16_t>> sketch_inverted_gpu(Device &dev, const std::v
             }
             Sequence().codes.swap(seqs[at].codes);   // release
         }
-        b0 = b1;
     }
 
     // 2'. read sets with a count filter: survivors on the device, the filter replayed on the host (one k, sketch_size bins),
     // then the u16 finish of their signs on the device.  A batch holds at most 64 streams (one 24 MiB filter each) and ~1 G bases.
     const std::vector<size_t> kmers{k};
     ReadsTiming rt;
-    for (size_t b0 = 0; b0 < filtered.size();) {
+    for (const auto &[b0, b1] : batches(filtered.size(), [&](size_t i) { return seqs[filtered[i]].codes.size(); }, skl::caps_filtered_reads(1))) {
         const double d0 = since();
-        size_t b1 = b0;
-        uint64_t codes_in_batch = 0;
-        while (b1 < filtered.size() &&
-               (b1 == b0 || (b1 - b0 + 1 <= 64 && codes_in_batch + seqs[filtered[b1]].codes.size() <= (1ull << 30)))) {
-            codes_in_batch += seqs[filtered[b1]].codes.size();
-            ++b1;
-        }
         const std::vector<size_t> idx(filtered.begin() + b0, filtered.begin() + b1);
         std::vector<uint64_t> signs;
         std::vector<char> any_window;
@@ -623,11 +535,8 @@ std::vector<std::vector<uint16_t>> sketch_inverted_gpu(Device &dev, const std::v
             Sequence().codes.swap(seqs[idx[i]].codes);   // release
         }
         t_device += since() - d0;
-        b0 = b1;
     }
-    for (const auto &e : error) {
-        if (!e.empty()) throw std::runtime_error(e);
-    }
+    raise_first(error);
     if (t_parse_out) *t_parse_out = t_parse;
     if (t_pack_out) *t_pack_out = t_pack;
     if (t_device_out) *t_device_out = t_device;

@@ -11,6 +11,7 @@
 
 #include "dense_plan.hpp"   // slice_plan()
 #include "aa_plan.hpp"      // the amino-acid sketching call's work plan and locators
+#include "sketch_plan.hpp"  // the DNA sketching calls: kernel shapes, spans per sample, batches
 #include "finish_plan.hpp"  // device-side densify + transpose: launch rules, flag bits, the shared target rule
 #include "work_map.hpp"     // which workgroup computes what: TILE_PREFIX_INLINE, the fields below it reads and plans
 #include "inv_top_plan.hpp" // best hits of an inverted query: digits, list length, LDS bytes, the descending walk
@@ -333,7 +334,7 @@ struct CandArgs {
     uint64_t n_work;
     float *keys;                  // [n_candidates] MODE_JACCARD output per candidate
     uint32_t symmetric;           // 1: the lists are symmetric -- evaluate j > i only, store both copies
-    // consecutive work items (rows of one cluster, capi_aux.cpp) stay on ONE XCD, whose L2 then holds the candidates they
+    // consecutive work items (rows of one cluster, capi_cand.cpp) stay on ONE XCD, whose L2 then holds the candidates they
     // share: workgroup b takes the items of block (b mod XCDs) * blocks_per_xcd + b / XCDs (set by the launcher)
     uint32_t xcd_shift, blocks_per_xcd;
     uint32_t lanes_over_candidates;   // 1: round 3's form (every lane walks its own candidate); 0: lanes across the sketch (round 4)
@@ -381,16 +382,12 @@ struct SketchArgs {
     double inv_bin_size;
     int32_t rc;
     uint64_t *signs;               // [n_samples][nk][num_bins], pre-set to UINT64_MAX
-    // 1: LDS-staged kernel -- span_begin counts spans of sketch_span_lds() window starts, every
-    // sample's count padded to a multiple of sketch_wg_lds() (a workgroup never straddles samples), every
-    // k-mer length <= sketch_span_lds() + 1
+    // 1: LDS-staged kernel -- span_begin counts spans of SKETCH_SPAN_LDS window starts, every
+    // sample's count padded to a multiple of SKETCH_WG_LDS (a workgroup never straddles samples), every
+    // k-mer length <= SKETCH_SPAN_LDS + 1 (sketch_plan.hpp)
     uint32_t lds_form;
 };
 hipError_t launch_sketch_signs(const SketchArgs &args, hipStream_t stream);
-int sketch_span();
-int sketch_span_lds();
-int sketch_wg_lds();   // threads (= spans) per workgroup of the LDS-staged kernel: a sample's span count is padded to a multiple
-int sketch_lds_bins_max();   // most bins whose minima the LDS-staged kernel keeps in LDS; above it they stay in global memory
 
 // GPU sketching of amino-acid sequences (aa_sketch_kernel.hip): bin minima of the forward aaHash of every window of k valid
 // residues.  One launch = the items [first_item, first_item + n_items) of one form (aa_plan.hpp), all of samples
@@ -455,7 +452,6 @@ struct ReadSurvivorArgs {
     unsigned long long *counts;    // [n_samples * nk] survivors found (may exceed capacity), pre-zeroed
 };
 hipError_t launch_read_survivors(const ReadSurvivorArgs &args, hipStream_t stream);
-int read_survivor_span();   // window starts per thread
 
 // Candidate lists on the device (cand_gen.hip): any shared bin between index sketches.
 struct CandGenArgs {

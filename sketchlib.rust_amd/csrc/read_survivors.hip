@@ -13,36 +13,12 @@
 // step (ballot, popcount, prefix rank).  The count always advances; records past `capacity` are not
 // written, and the host repeats the call with room for them.  Vector stores only.
 #include "kernels.h"
+#include "nthash.hpp"   // srol, sror, the seeds, mod_sign
 
 namespace skl {
 
-namespace {
-__device__ __forceinline__ uint64_t rotl1(uint64_t v) { return (v << 1) | (v >> 63); }
-__device__ __forceinline__ uint64_t rotr1(uint64_t v) { return (v >> 1) | (v << 63); }
-// swapbits033, src/hashing/mod.rs:99-103
-__device__ __forceinline__ uint64_t swapbits033(uint64_t v)
-{
-    const uint64_t x = (v ^ (v >> 33)) & 1ull;
-    return v ^ (x | (x << 33));
-}
-__device__ __forceinline__ uint64_t srol(uint64_t v) { return swapbits033(rotl1(v)); }
-__device__ __forceinline__ uint64_t sror(uint64_t v) { return rotr1(swapbits033(v)); }
-// src/hashing/nthash_tables.rs:4-16 (index = 2-bit base code)
-__device__ __forceinline__ uint64_t hash_fwd(uint32_t c)
-{
-    return c == 0 ? 0x3c8bfbb395c60474ull : c == 1 ? 0x3193c18562a02b4cull : c == 2 ? 0x295549f54be24456ull : 0x20323ed082572324ull;
-}
-__device__ __forceinline__ uint64_t hash_rc(uint32_t c) { return hash_fwd(c ^ 2u); }   // complement = code ^ 2
-constexpr uint64_t SIGN_MOD_DEV = (1ull << 61) - 1;   // src/sketch/mod.rs:36
-__device__ __forceinline__ uint64_t mod_sign(uint64_t h)
-{
-    const uint64_t r = (h & SIGN_MOD_DEV) + (h >> 61);   // 2^61 = 1 (mod 2^61 - 1)
-    return r >= SIGN_MOD_DEV ? r - SIGN_MOD_DEV : r;
-}
-}  // namespace
-
-constexpr int RS_SPAN = 64;    // window starts per thread
-constexpr int RS_WG = 256;
+constexpr int RS_SPAN = READ_SURVIVOR_SPAN;    // window starts per thread (sketch_plan.hpp)
+constexpr int RS_WG = READ_SURVIVOR_WG;
 
 __global__ __launch_bounds__(RS_WG) void read_survivors_kernel(const ReadSurvivorArgs g)
 {
@@ -113,6 +89,8 @@ __global__ __launch_bounds__(RS_WG) void read_survivors_kernel(const ReadSurvivo
                 if (s + k <= next_off) {   // no break strictly inside the window (next_iterator, nthash_iterator.rs:325-346)
                     const uint64_t h = g.rc ? (fh < rh ? fh : rh) : fh;   // nthash_iterator.rs:62-68
                     sign = mod_sign(h);
+                    // bin = sign / bin_size: nthash.hpp bin_of(sign, g.inv_bin_size, g.bin_size, last_bin), spelled out -- the call
+                    // gives this kernel another block layout
                     uint32_t bin = (uint32_t)((double)sign * g.inv_bin_size);   // off by at most one; one product settles it
                     if (bin > last_bin) bin = last_bin;
                     const uint64_t prod = (uint64_t)bin * g.bin_size;
@@ -148,7 +126,5 @@ hipError_t launch_read_survivors(const ReadSurvivorArgs &args, hipStream_t strea
     hipLaunchKernelGGL(read_survivors_kernel, dim3((unsigned)blocks), dim3(RS_WG), 0, stream, args);
     return hipGetLastError();
 }
-
-int read_survivor_span() { return RS_SPAN; }
 
 }  // namespace skl

@@ -12,39 +12,12 @@
 // a 64-bit atomicMin, issued only when it would lower the bin (after the first few hundred
 // windows of a bin almost none does).
 #include "kernels.h"
+#include "nthash.hpp"   // srol, sror, the seeds, mod_sign
 
 namespace skl {
 
-namespace {
-__device__ __forceinline__ uint64_t rotl1(uint64_t v) { return (v << 1) | (v >> 63); }
-__device__ __forceinline__ uint64_t rotr1(uint64_t v) { return (v >> 1) | (v << 63); }
-// swapbits033, src/hashing/mod.rs:99-103
-__device__ __forceinline__ uint64_t swapbits033(uint64_t v)
-{
-    const uint64_t x = (v ^ (v >> 33)) & 1ull;
-    return v ^ (x | (x << 33));
-}
-__device__ __forceinline__ uint64_t srol(uint64_t v) { return swapbits033(rotl1(v)); }
-__device__ __forceinline__ uint64_t sror(uint64_t v) { return rotr1(swapbits033(v)); }
-
-// src/hashing/nthash_tables.rs:4-16 (index = 2-bit base code)
-__device__ __forceinline__ uint64_t hash_fwd(uint32_t c)
-{
-    return c == 0 ? 0x3c8bfbb395c60474ull : c == 1 ? 0x3193c18562a02b4cull : c == 2 ? 0x295549f54be24456ull : 0x20323ed082572324ull;
-}
-__device__ __forceinline__ uint64_t hash_rc(uint32_t c) { return hash_fwd(c ^ 2u); }   // complement = code ^ 2
-
-constexpr uint64_t SIGN_MOD_DEV = (1ull << 61) - 1;   // src/sketch/mod.rs:36
-__device__ __forceinline__ uint64_t mod_sign(uint64_t h)
-{
-    uint64_t r = (h & SIGN_MOD_DEV) + (h >> 61);        // 2^61 = 1 (mod 2^61 - 1)
-    return r >= SIGN_MOD_DEV ? r - SIGN_MOD_DEV : r;
-}
-}  // namespace
-
-constexpr int SKETCH_SPAN = 256;   // window starts per thread
-
-__global__ __launch_bounds__(256) void nthash_binmin_kernel(const SketchArgs g)
+// (SKETCH_SPAN window starts per thread, SKETCH_WG threads: sketch_plan.hpp)
+__global__ __launch_bounds__(SKETCH_WG) void nthash_binmin_kernel(const SketchArgs g)
 {
     if ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x >= g.n_spans) return;
     const uint64_t t = g.first_span + (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -145,11 +118,11 @@ __global__ __launch_bounds__(256) void nthash_binmin_kernel(const SketchArgs g)
 //     most one: the two `while` loops of round 3 evaluated two).
 // ---------------------------------------------------------------------------------------------
 
-constexpr int SPAN2 = 128;                    // window starts per thread
-constexpr int WG2 = 512;                      // threads (= spans) per workgroup
+constexpr int SPAN2 = SKETCH_SPAN_LDS;         // window starts per thread (sketch_plan.hpp)
+constexpr int WG2 = SKETCH_WG_LDS;            // threads (= spans) per workgroup
 constexpr int PITCH2_DW = SPAN2 / 16 + 1;     // dwords per staged row (8 of codes + 1 of padding)
 constexpr int ROWS2 = WG2 + 1;                // one more row: a window reaches k - 1 <= SPAN2 codes past its span
-constexpr int LDS_BINS_MAX = 4096;
+constexpr int LDS_BINS_MAX = SKETCH_LDS_BINS_MAX;
 
 template <bool LDS_BINS>
 __global__ __launch_bounds__(WG2) void nthash_binmin_lds_kernel(const SketchArgs g)
@@ -258,8 +231,8 @@ __global__ __launch_bounds__(WG2) void nthash_binmin_lds_kernel(const SketchArgs
                     if (j + k > next_rel) continue;   // the window spans a break (next_iterator, :325-346): not hashed into a bin
                     const uint64_t h = g.rc ? (fh < rh ? fh : rh) : fh;      // nthash_iterator.rs:62-68
                     const uint64_t sign = mod_sign(h);
-                    // bin = sign / bin_size: the reciprocal estimate is off by at most one (relative error 2^-52 on a
-                    // quotient below 2^32), one exact product settles it
+                    // bin = sign / bin_size: nthash.hpp bin_of(sign, g.inv_bin_size, g.bin_size, last_bin), spelled out -- the
+                    // call costs this kernel two registers and another block layout
                     uint32_t bin = (uint32_t)((double)sign * g.inv_bin_size);
                     if (bin > last_bin) bin = last_bin;
                     const uint64_t prod = (uint64_t)bin * g.bin_size;
@@ -289,7 +262,7 @@ __global__ __launch_bounds__(WG2) void nthash_binmin_lds_kernel(const SketchArgs
 hipError_t launch_sketch_signs(const SketchArgs &args, hipStream_t stream)
 {
     if (args.n_spans == 0) return hipSuccess;
-    const uint64_t wg = args.lds_form ? (uint64_t)WG2 : 256u;
+    const uint64_t wg = (uint64_t)(args.lds_form ? WG2 : SKETCH_WG);
     const uint64_t blocks = (args.n_spans + wg - 1) / wg;
     if (blocks >= (1ull << 31)) return hipErrorInvalidValue;
     if (args.lds_form) {
@@ -299,14 +272,9 @@ hipError_t launch_sketch_signs(const SketchArgs &args, hipStream_t stream)
             hipLaunchKernelGGL(nthash_binmin_lds_kernel<false>, dim3((unsigned)blocks), dim3(WG2), 0, stream, args);
         }
     } else {
-        hipLaunchKernelGGL(nthash_binmin_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, args);
+        hipLaunchKernelGGL(nthash_binmin_kernel, dim3((unsigned)blocks), dim3(SKETCH_WG), 0, stream, args);
     }
     return hipGetLastError();
 }
-
-int sketch_span() { return SKETCH_SPAN; }
-int sketch_span_lds() { return SPAN2; }
-int sketch_wg_lds() { return WG2; }
-int sketch_lds_bins_max() { return LDS_BINS_MAX; }
 
 }  // namespace skl

@@ -13,7 +13,10 @@ machine without a GPU.
 
 Not covered (see sketch_edge_cases.py): k = 1, 2, 3 and the bin counts are plain equality; the `++bin` branch of the
 bin correction (the reciprocal estimate below the true bin) needs a sign within about 2^-20 of a bin's upper edge in
-relative terms, which no input of this size produces -- dropping that branch fails no case here."""
+relative terms, which no input of this size produces -- dropping that branch fails no case here.  That branch is pinned on
+the CPU instead: csrc/nthash.hpp bin_of, which the kernels call or spell out, at every bin edge
+(tests/test_sketch_plan_cpu.py), where the upload batch rule restated in host_batches below is checked too
+(csrc/sketch_plan.hpp sketch_upload_batches)."""
 import numpy as np
 import pytest
 
@@ -196,8 +199,9 @@ def test_small_k(skl, gpu_ctx, k):
 
 
 def host_batches(words, setting):
-    """The batches of whole samples sketch_signs_impl cuts (csrc/capi_aux.cpp): a batch is closed behind the sample with
-    which it reaches `setting` words, unless that is the last -> ([(first, end)], cut exactly at the setting?)."""
+    """The batches of whole samples sketch_signs_impl cuts (csrc/sketch_plan.hpp sketch_upload_batches): a batch is
+    closed behind the sample with which it reaches `setting` words, unless that is the last -> ([(first, end)], cut
+    exactly at the setting?)."""
     cuts, exact = [0], False
     begin = np.concatenate([[0], np.cumsum(words)])
     for s in range(len(words)):
