@@ -76,6 +76,38 @@ __device__ __forceinline__ void skl_dma16_saddr(const void *uniform_base, uint32
 #endif
 }
 
+// One stage of pair_kernel_kslice's row staging, for pair_kslice_walk.inc: the rows of this wave's CH chunks of flat stage T
+// go into its row buffer BUF; piece p = (chunk * R + row) * 7 + q of the stage lands at slot p of the buffer.  A MACRO over
+// the walk's names (g, a0, kk0, c_begin, stages_per_k, the strides, wave, lane, lds_base, dma_lane_off), not a function:
+// as a __forceinline__ function template with those as parameters, hipcc computes the addresses differently inside the
+// walk's hot blocks of every form (profiles/kslice_split.md).
+// dma_lane_off (all forms but the A/B build's ABL & 4): the per-lane part of the source address -- which row, which of the
+// stage's CH chunks, which plane pair -- is the same in every stage; it is kept as PPL 32-bit byte offsets and a stage
+// supplies a scalar base.  A chunk past the end of the sketch -- sketch sizes that are not a multiple of 4 CH chunks -- is
+// clamped to the last one (with lane offsets: reads the next k-mer length's or the next sample's words instead, inside the
+// slab thanks to its A_PAD_ROWS zero rows) and never used.
+#define SKL_STAGE_DMA(T, BUF)                                                                \
+    do {                                                                                     \
+        const uint32_t k_ = g.k_begin + kk0 + (BIG ? 0u : (T) / stages_per_k);               \
+        const uint32_t c0_ = c_begin + (BIG ? (T) : (T) % stages_per_k) * (W * CH) + wave * CH; \
+        if constexpr ((ABL & 4) == 0) {                                                      \
+            const uint32_t cu_ = c0_ < g.ss64 ? c0_ : (g.ss64 - 1u);                         \
+            const uint64_t *base_ = g.A + (size_t)a0 * sample_stride + (size_t)k_ * kmer_stride + (size_t)cu_ * BBITS; \
+            _Pragma("unroll") for (int u = 0; u < PPL; ++u)                                  \
+                skl_dma16_saddr(base_, dma_lane_off[u], lds_base + (((uint32_t)wave * 2u + (BUF)) * (PPL * LANES) + u * 64u) * 16u); \
+        } else                                                                               \
+        _Pragma("unroll") for (int u = 0; u < PPL; ++u)                                      \
+        {   /* timing only: a tile-major row slab */                                         \
+            const uint32_t pp_ = lane + u * 64u;                                             \
+            const uint32_t p_ = pp_ < (uint32_t)PIECES ? pp_ : pp_ - (uint32_t)PIECES;       \
+            const uint32_t q_ = p_ % 7u, rc_ = p_ / 7u;                                      \
+            const uint32_t r_ = rc_ % R, c_ = rc_ / R;                                       \
+            const uint32_t cc_ = (c0_ + c_) < g.ss64 ? (c0_ + c_) : (g.ss64 - 1u);           \
+            skl_dma16(g.A + ((((size_t)(a0 / R) * g.nk + k_) * g.ss64 + cc_) * R + r_) * BBITS + 2u * q_, \
+                      lds_base + (((uint32_t)wave * 2u + (BUF)) * (PPL * LANES) + u * 64u) * 16u); \
+        }                                                                                    \
+    } while (0)
+
 __device__ __forceinline__ uint32_t skl_lds_addr(const void *p)
 {
 #if defined(__HIP_DEVICE_COMPILE__)

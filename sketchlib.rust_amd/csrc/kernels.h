@@ -130,7 +130,7 @@ struct PairArgs {
     // copies read marked stretches only, which is what lets a workgroup leave its tile unwritten (below).  Zeroed by the host.
     uint32_t *t_bits;
     uint32_t t_bits_stride;
-    // TILE PRUNING (symmetric self kNN, single-k keys, 32 x 128 k-sliced form; pair_kslice_walk.inc).  The key is monotone in
+    // TILE PRUNING (symmetric self kNN, single-k keys, 32 x 128 k-sliced form; pair_prune.hpp).  The key is monotone in
     // the mismatch count, so a pair whose count over the chunks walked SO FAR already exceeds allow = the largest count whose
     // key is still below BOTH samples' knn-th best can enter neither list, and a tile all of whose pairs are in that state
     // need not be finished: the workgroup leaves without storing (no bit above is set for it, so nothing reads its records).

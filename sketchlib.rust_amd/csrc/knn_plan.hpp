@@ -254,7 +254,7 @@ inline KnnCallPlan plan_knn_call(const KnnCall &c)
     P.row_bits_bytes = 2 * c.band_rows * P.bit_words * sizeof(uint32_t);
     P.row_bits_half = c.overlap ? c.band_rows * P.bit_words : 0;
     // ... and for the turned band one bit per (column, 32-row stretch of the band), so that BOTH merges read marked stretches
-    // only and a tile without a mark need not exist: TILE PRUNING (pair_kslice_walk.inc).  Single-k keys are monotone in the
+    // only and a tile without a mark need not exist: TILE PRUNING (pair_prune.hpp).  Single-k keys are monotone in the
     // mismatch count, so before each band a small kernel turns every sample's current knn-th best into the mismatch count
     // beyond which a pair cannot enter its list, and the pair kernel leaves a tile once every pair of it is beyond both its
     // samples' bounds on the chunks walked so far.  The bounds come from the same (possibly stale, i.e. too high) thresholds

@@ -35,7 +35,7 @@
 // Per (row, column, chunk) the instruction stream is 2 v_xor + 26 v_bitop3 (all-VGPR,
 // bank-conflict-free, see device_common.hpp) + 2 fused v_bcnt.
 // Wave timelines of this kernel: scripts/microbench/kslice_trace.hip.
-#include "device_common.hpp"
+#include "pair_prune.hpp"
 
 #include <algorithm>
 #include <cstdlib>
@@ -62,28 +62,27 @@ namespace skl {
 #define SKL_TRACE_MARK(SLOT) do { } while (0)
 #endif
 
-// (TIGHT: the 2-column form squeezed into 128 VGPRs -- packed counts, 4-deep row ring -- for 4 waves per SIMD;
-// the only form left, the parameter is kept for the kernels' names.)
+// JL, TIGHT: always 2 and true -- two columns per lane, squeezed into 128 VGPRs (packed counts, 4-deep row ring) for 4 waves
+// per SIMD; the only form left, the parameters are kept for the kernels' names.
 // MB: rows walked plane by plane together (1: row by row).  A chunk is walked in blocks of MB rows, and
 // inside a block plane pair q of all MB rows comes before plane pair q + 1 of any.  Column register
 // b[.][q] is then free -- and re-loaded with the next chunk's data -- 6/7 of a BLOCK before its first
 // use there instead of one row before: 3.4 rows of VALU work with MB = 4.  Costs 4 (MB - 1) registers
-// for the blocks' mismatch accumulators, so only the 32-row form (3 waves per SIMD, registers to
-// spare) has it.  Worth 1.2-1.4 % at n = 8 000 ... 16 000 (MB = 1 / 2 / 4 / 8: 30.34 / 29.95 / 29.98 /
+// for the blocks' mismatch accumulators.  Worth 1.2-1.4 % at n = 8 000 ... 16 000 (MB = 1 / 2 / 4 / 8: 30.34 / 29.95 / 29.98 /
 // 30.07 ms at n = 16 000, profiles/r02_ab_row_blocks.jsonl): the s_waitcnt share of the SQ counters is
 // mostly the LDS reads of a kernel that runs at the LDS's rate, not the column loads.
-// OCC: waves per SIMD the register allocator is held to (0: 4 for the tight 16-row form, 3 for the tight
-// 32-row form and for 3 columns per lane, 1 otherwise).
+// OCC: waves per SIMD the register allocator is held to (0: 4 for the 16-row form, 3 for the 32-row form).
 // BIG: sketches beyond 65 535 bins (k-sliced counts / single-k forms only): the k-mer length is walked in segments
-// whose totals fit the u16 fields and are added up in 32 bits (pair_kslice_walk.inc).
-// PRUNE: tile pruning of the symmetric self kNN (PairArgs::prune_q_*; the single-k 32 x 128 form only): at a few stage
-// boundaries every wave asks whether each pair's count on ITS chunks has reached the pair's per-wave bound, the 4 answers
-// meet in LDS, and a tile that is hopeless as a whole is left unfinished and unwritten (pair_kslice_walk.inc).
+// whose totals fit the u16 fields and are added up in 32 bits (pair_kslice_walk.inc, pair_kslice_finish.inc).
+// PRUNE: tile pruning of the symmetric self kNN (PairArgs::prune_q_*, pair_prune.hpp; the single-k 32 x 128 form only): before
+// the walk (pair_kslice_probe.inc) and at a few of its stage boundaries every wave asks whether each pair's count on ITS chunks
+// has reached the pair's per-wave bound, the 4 answers meet in LDS, and a tile that is hopeless as a whole is left unwritten.
 // FUSE: the core/accessory epilogue of a k-sliced counts launch inside the launch (PairArgs::fuse_counter): the workgroup that
 // completes a tile's k-mer lengths turns the tile's counts into (core, acc).
 template <int R, int JL, int MODE, bool KSL, int ABL = 0, bool TIGHT = false, int MB = 1, int OCC = 0, bool BIG = false, bool PRUNE = false, bool FUSE = false>
-__global__ __launch_bounds__(LANES *WAVES_PER_WG, OCC != 0 ? OCC : (TIGHT ? (R > 16 ? 3 : 4) : (JL == 3 ? 3 : 1))) void pair_kernel_kslice(const PairArgs g)
+__global__ __launch_bounds__(LANES *WAVES_PER_WG, OCC != 0 ? OCC : (R > 16 ? 3 : 4)) void pair_kernel_kslice(const PairArgs g)
 {
+    static_assert(TIGHT && JL == 2, "the chunk-split kernel ships in its packed-count form with 2 columns per lane only");
     static_assert(!PRUNE || (KSL && MODE == MODE_JACCARD && !BIG && JL == 2), "tile pruning: single-k keys, two columns per lane");
     static_assert(!FUSE || (KSL && MODE == MODE_COUNTS && !BIG && JL == 2), "fused epilogue: k-sliced counts, whole k-mer lengths");
     constexpr int W = WAVES_PER_WG;
@@ -97,8 +96,8 @@ __global__ __launch_bounds__(LANES *WAVES_PER_WG, OCC != 0 ? OCC : (TIGHT ? (R >
     static_assert(PPL * LANES - PIECES < PIECES, "tail pieces wrap at most once");
     static_assert(!KSL || MODE != MODE_COREACC, "k-sliced core/acc runs COUNTS + the epilogue kernel");
     // LDS: the row buffers [W][2][PPL * LANES] x 16 B.  The per-k reduction words of a wave
-    // (PX per lane) go into the row buffer it has just finished with, XIN per lane; with 3 and 4
-    // columns per lane the rest (PX - XIN per lane) go to an overflow region behind the row buffers.
+    // (PX per lane) go into the row buffer it has just finished with, XIN per lane; the rest (PX - XIN per lane: the
+    // 3-wave 32-row forms of the A/B build) go to an overflow region behind the row buffers.
     constexpr uint32_t BUF_U4 = PPL * LANES;
     constexpr uint32_t ROWS_U4 = W * 2 * BUF_U4;
     // (a k-sliced workgroup walks ONE k-mer length: no next stage is in flight when it reduces, so both row
@@ -109,21 +108,19 @@ __global__ __launch_bounds__(LANES *WAVES_PER_WG, OCC != 0 ? OCC : (TIGHT ? (R >
     // RED2 (the all-k 32-row form held to 4 waves per SIMD): the words that do not fit the one free buffer go
     // through it in a second phase (two more barriers per k-mer length) instead of an overflow region -- 32 KB
     // of LDS (36 KB with core/accessory's turned tile) instead of 48 KB, i.e. room for 4 workgroups per CU
-    constexpr bool RED2 = TIGHT && (!KSL || BIG) && R == 32 && OCC == 4;
+    constexpr bool RED2 = (!KSL || BIG) && R == 32 && OCC == 4;
     constexpr int RED_PHASES = RED2 ? 2 : 1;
-    // Row DMA addressed as scalar base + 32-bit per-lane offset (pair_kslice_walk.inc): the lane part of the address -- which
-    // row, chunk of the stage and plane pair a lane fetches -- never changes.  Kept as 64-bit per-lane pointers it was what the 4-wave all-k form spilled
-    // at every stage (a scratch reload waits for the column prefetch too): 5-6 % slower than 3 waves with them, 6 % FASTER without.
-    constexpr bool SADDR_DMA = TIGHT && (ABL & 4) == 0;
+    // Row DMA addressed as scalar base + 32-bit per-lane offset (SKL_STAGE_DMA, device_common.hpp).  Kept as 64-bit per-lane pointers
+    // the address was what the 4-wave all-k form spilled at every stage (a scratch reload waits for the column prefetch too):
+    // 5-6 % slower than 3 waves with them, 6 % FASTER without.
+    constexpr bool SADDR_DMA = (ABL & 4) == 0;
     constexpr int XIN_FIT = (RED_BUFS * BUF_U4 * 4 / LANES) < (uint32_t)PX ? (int)(RED_BUFS * BUF_U4 * 4 / LANES) : PX;
     constexpr int XIN = RED2 ? PX / RED_PHASES : XIN_FIT;
     static_assert(!RED2 || (XIN <= XIN_FIT && SLOTS % RED_PHASES == 0), "a phase's words fit the free row buffer");
     constexpr int XOV = RED2 ? 0 : PX - XIN;
-    constexpr uint32_t TURNED_U4 = (MODE == MODE_COREACC) ? (uint32_t)(JL * 64 * (R + 4) * 8 + 15) / 16u : 0u;   // see the turned tile below
+    constexpr uint32_t TURNED_U4 = (MODE == MODE_COREACC) ? (uint32_t)(JL * 64 * turned_pitch(R) * 8 + 15) / 16u : 0u;   // the turned tile (pair_finish.hpp)
     constexpr uint32_t RED_U4 = RED2 ? (TURNED_U4 > ROWS_U4 ? TURNED_U4 - ROWS_U4 : 0u) : (uint32_t)(W * XOV * LANES) / 4u;
-    // PRUNE: behind the row buffers, the column samples' per-wave bounds (JL * 64 words, the same values written by every
-    // wave) and two rotating rows of 4 votes
-    constexpr uint32_t PRUNE_U4 = PRUNE ? (uint32_t)(JL * LANES) / 4u + 2u + (uint32_t)R / 4u + 2u : 0u;   // column bounds, votes, row bounds, the probe's masks
+    constexpr uint32_t PRUNE_U4 = PRUNE ? prune_lds_words(R) / 4u : 0u;   // behind the row buffers (pair_prune.hpp)
     __shared__ uint4 lds_all[ROWS_U4 + RED_U4 + PRUNE_U4];
     uint4 (*lds_rows)[2][BUF_U4] = reinterpret_cast<uint4 (*)[2][BUF_U4]>(&lds_all[0]);
 
@@ -167,7 +164,7 @@ __global__ __launch_bounds__(LANES *WAVES_PER_WG, OCC != 0 ? OCC : (TIGHT ? (R >
     slice_chunk_range(g, n_slices, slice, c_begin, c_end);
     uint32_t jg, at;  // column group (JL blocks of 64), row tile
     // (tiles dealt by cost, half tiles last on every XCD: a run-time case of the lookup, in the one form whose launches ask for it)
-    constexpr bool COST_ORDER = KSL && MODE == MODE_COUNTS && R == 16 && JL == 2 && TIGHT && ABL == 0 && !FUSE;
+    constexpr bool COST_ORDER = KSL && MODE == MODE_COUNTS && R == 16 && ABL == 0 && !FUSE;
     if (COST_ORDER && g.tile_cost_order != 0u) {
         if (!lookup_tile_by_cost_at(g, xcd, slot, jg, at)) return;
     } else if (!lookup_tile_at(g, xcd, slot, jg, at)) {
@@ -200,7 +197,7 @@ __global__ __launch_bounds__(LANES *WAVES_PER_WG, OCC != 0 ? OCC : (TIGHT ? (R >
     // in block 0 (an odd number of 64-column blocks).  The chunk walk below is instantiated for the
     // three cases and chosen per workgroup (uniform branch); the skipped block's column registers are
     // never loaded and its count fields stay 0 (its pairs are invalid and never stored).
-    constexpr bool HALF_TILES = R == 16 && JL == 2 && TIGHT && ABL == 0;
+    constexpr bool HALF_TILES = R == 16 && ABL == 0;
 #ifdef SKL_AB
     // (A/B build only: SKL_HALF_TILES=0 walks every block.  The run-time condition costs the 16-row k-sliced
     // form 11 registers spilled outside its loops -- 44 B of scratch per lane, 26 MB of HBM traffic per
@@ -211,36 +208,24 @@ __global__ __launch_bounds__(LANES *WAVES_PER_WG, OCC != 0 ? OCC : (TIGHT ? (R >
 #endif
     const bool skip0 = half_ok && tile_skips_block0(g.self_mode, a0, jb0);   // (work_map.hpp: the cost order's classes are these two tests)
     const bool skip1 = half_ok && tile_skips_block1(jb0, g.n_jblocks);
-    // The walk is TEXTUALLY included once per case (pair_kslice_walk.inc; SKL_J0 / SKL_J1 = the column blocks
-    // [J0, J1) it walks), not a lambda or a function template: wrapping it in either changes hipcc's register
+    // The walk is TEXTUALLY included once per case (pair_kslice_walk.inc and the texts it includes; SKL_WALK_BLOCKS = the
+    // column blocks [J0, J1) it walks, undefined again by the text), not a lambda or a function template: wrapping it in either changes hipcc's register
     // allocation of the 32-row form (168 VGPRs + 144 B of spills per lane instead of 144 VGPRs).  No value of
     // one case is live in another, so the cases do not add to each other's register pressure.
     if constexpr (HALF_TILES) {
         if (skip0) {
-#define SKL_J0 1
-#define SKL_J1 JL
+#define SKL_WALK_BLOCKS 1, 2
 #include "pair_kslice_walk.inc"
-#undef SKL_J0
-#undef SKL_J1
         } else if (skip1) {
-#define SKL_J0 0
-#define SKL_J1 1
+#define SKL_WALK_BLOCKS 0, 1
 #include "pair_kslice_walk.inc"
-#undef SKL_J0
-#undef SKL_J1
         } else {
-#define SKL_J0 0
-#define SKL_J1 JL
+#define SKL_WALK_BLOCKS 0, 2
 #include "pair_kslice_walk.inc"
-#undef SKL_J0
-#undef SKL_J1
         }
     } else {
-#define SKL_J0 0
-#define SKL_J1 JL
+#define SKL_WALK_BLOCKS 0, 2
 #include "pair_kslice_walk.inc"
-#undef SKL_J0
-#undef SKL_J1
     }
     SKL_TRACE_MARK(3);
     if constexpr (FUSE) {

@@ -1,10 +1,12 @@
 // pair_kslice_walk.inc -- the tile walk of pair_kernel_kslice (pair_kslice.hip), included once per
-// case of column blocks [SKL_J0, SKL_J1) the workgroup walks: both blocks of the tile, or one of them
-// (half tiles: a block without a pair of the launch is neither loaded nor computed).  Everything the
-// text refers to -- template parameters, g, wave, lane, a0, jb0, kk0, c_begin, c_end, lds_all, ... --
-// is in scope at the point of inclusion.
+// case of column blocks [J0, J1) = SKL_WALK_BLOCKS the workgroup walks: both blocks of the tile, or one of
+// them (half tiles: a block without a pair of the launch is neither loaded nor computed).  It keeps what
+// depends on that case -- column prefetch, streaming loop, stage-boundary prune check, count accumulation --
+// and includes the rest: pair_kslice_probe.inc, pair_kslice_finish.inc, pair_kslice_coreacc.inc.
+// Everything the texts refer to -- template parameters, g, wave, lane, a0, jb0, kk0, c_begin, c_end,
+// lds_all, ... -- is in scope at the point of inclusion.
 {
-    constexpr int J0 = SKL_J0, J1 = SKL_J1;
+    constexpr int WALK_BLOCKS[2] = {SKL_WALK_BLOCKS}, J0 = WALK_BLOCKS[0], J1 = WALK_BLOCKS[1];
 
     const size_t kmer_stride = (size_t)g.ss64 * BBITS;
     const size_t sample_stride = kmer_stride * g.nk;
@@ -28,336 +30,26 @@
     // This wave's partial mismatch counts of the current k (its chunks only): the two columns of a row share one
     // register as u16 fields (a wave's share of one k-mer length is at most 64 * 256 mismatches per pair:
     // kslice_supported) -- R registers instead of 2 R, for one v_lshl_add_u32 more per (row, chunk).
-    static_assert(TIGHT && JL == 2, "the chunk-split kernel ships in its packed-count form with 2 columns per lane only");
-    constexpr int NCNT = R;
-    uint32_t cnt[NCNT];
+    // Word r: row r of the tile against the lane's column of block 0 (low field) and of block 1 (high field).
+    uint32_t cnt[R];
 #pragma unroll
-    for (int x = 0; x < NCNT; ++x) cnt[x] = 0;
-    // packed word x (two u16 fields) of the per-k reduction, and the pair its field h stands for
-    auto packed_word = [&](int x) -> uint32_t { return cnt[x]; };
-    auto field_pair = [](uint32_t x, uint32_t h, uint32_t &r, uint32_t &j) {
-        r = x;
-        j = h;
-    };
+    for (int x = 0; x < R; ++x) cnt[x] = 0;
     // MODE_COREACC: totals of this wave's packed slots, one word per k-mer length (two u16
     // fields per word: the slot's two pairs).  Private (scratch) memory on purpose: written
     // once per k-mer length, read once at the end, and 24 registers cheaper.
     volatile uint32_t hist[(MODE == MODE_COREACC) ? SLOTS * MAX_FUSED_K : 1];
 
-    // TILE PRUNING (PRUNE; PairArgs::prune_q_*).  q = floor(allow / 4) + 1 per sample, allow = the largest mismatch count
-    // whose key is still below that sample's knn-th best.  All 4 waves compute the same plan from the same bounds (they meet
-    // at a barrier per check).  A tile with one sample whose list is not full (q beyond any count) is neither probed nor
-    // checked: no cost outside the regime pruning is for.
+    // TILE PRUNING (pair_prune.hpp): the probe and the sparse walk before anything of the walk is requested, then checks at
+    // stage boundaries
     uint32_t prune_next = 0xFFFFFFFFu;   // stage count (t + 1) of the next stage-boundary check of the walk
     uint32_t prune_checks = 0u;          // checks so far
-    uint32_t *prune_lds = reinterpret_cast<uint32_t *>(&lds_all[ROWS_U4 + RED_U4]);   // [JL * 64] column bounds, then 2 x 4 votes
+    uint32_t *prune_lds = reinterpret_cast<uint32_t *>(&lds_all[ROWS_U4 + RED_U4]);
     if constexpr (PRUNE) {
-        static_assert(!PRUNE || CH == 1, "the probe below takes one chunk per wave and step");
-        if (g.prune_q_rows != nullptr) {
-            // Everything the probe needs is requested AT ONCE, before any of it is looked at: the bounds of the tile's columns
-            // (2 per lane) and rows (lane r: row r), and -- speculatively, the plan is not known yet -- the plane pairs of the
-            // probe's first PRE steps (rows: one 16-byte load per lane and two steps; columns: two per step).
-            constexpr uint32_t PRE = 4;                  // probe steps fetched before the plan is known
-            constexpr uint32_t ROW_BOUNDS = (uint32_t)(JL * LANES) + 8u;   // prune_lds: [0, 128) column bounds, [128, 136) votes, [136, 136 + R) row bounds
-            static_assert(64 % R == 0 && R <= 64, "a trip of the row fetch covers whole probe steps");
-            const uint32_t per_wave = (c_end - c_begin) / (uint32_t)W;   // chunks every wave has
-            const uint32_t k_ = g.k_begin + kk0;
-            uint32_t qcol[JL];
-#pragma unroll
-            for (int j = 0; j < JL; ++j) {
-                const uint32_t jc = (jb0 + (uint32_t)j) * 64u + lane;
-                qcol[j] = jc < g.nB ? g.prune_q_cols[jc] : 0u;   // (columns past the end hold no pair)
-            }
-            const uint32_t qrow = (lane < (uint32_t)R && a0 + lane < g.row_end) ? g.prune_q_rows[a0 + lane] : 0u;   // (rows past the band hold no pair)
-            auto row_pair = [&](uint32_t item) -> uint4 {   // plane pair 0 of row item % R at probe step item / R: (lo0, hi0, lo1, hi1)
-                const uint32_t step = item / (uint32_t)R, r = item % (uint32_t)R;
-                const uint32_t c_ = min(c_begin + wave + step * (uint32_t)W, g.ss64 - 1u);
-                return a0 + r < g.row_end
-                           ? *reinterpret_cast<const uint4 *>(g.A + (size_t)(a0 + r) * sample_stride + (size_t)k_ * kmer_stride + (size_t)c_ * BBITS)
-                           : make_uint4(0u, 0u, 0u, 0u);
-            };
-            auto col_pair = [&](int j, uint32_t step) -> uint4 {   // plane pair 0 of this lane's column in block j: (hi0, lo0, hi1, lo1)
-                const uint32_t jb = (jb0 + j) < g.n_jblocks ? (jb0 + j) : (g.n_jblocks - 1u);   // clamped, masked in the vote
-                const uint32_t c_ = min(c_begin + wave + step * (uint32_t)W, g.ss64 - 1u);
-                return g.B[(((size_t)jb * g.nk + k_) * g.ss64 + c_) * (7 * LANES) + lane];
-            };
-            constexpr uint32_t PRE_TRIPS = (PRE * (uint32_t)R + 63u) / 64u;
-            uint4 pre_rows[PRE_TRIPS], pre_cols[PRE][JL];
-#pragma unroll
-            for (uint32_t u = 0; u < PRE_TRIPS; ++u) pre_rows[u] = row_pair(u * 64u + lane);
-#pragma unroll
-            for (uint32_t st = 0; st < PRE; ++st) {
-#pragma unroll
-                for (int j = 0; j < JL; ++j) pre_cols[st][j] = col_pair(j, st);
-            }
-            // the bounds: column bounds and row bounds to LDS (every wave writes the same values), the largest of all of them
-            uint32_t qmax = max(qrow, max(qcol[0], qcol[JL - 1]));
-#pragma unroll
-            for (int j = 0; j < JL; ++j) prune_lds[j * LANES + lane] = qcol[j];
-            if (lane < (uint32_t)R) prune_lds[ROW_BOUNDS + lane] = qrow;
-#pragma unroll
-            for (int sh = 32; sh >= 1; sh >>= 1) qmax = max(qmax, (uint32_t)__shfl_xor((int)qmax, sh));
-            qmax = (uint32_t)__builtin_amdgcn_readfirstlane((int)qmax);
-            // (1) PLANE-PAIR PROBE, before anything of the walk is requested.  A bin that differs in ANY plane mismatches, so the
-            // mismatches seen in planes 0 and 1 alone are a lower bound of a pair's count -- and an unrelated pair shows 3/4 of
-            // its bins there (48 per chunk) for 1/7 of the loads and 1/5 of the instructions of the full comparison.  Each wave
-            // takes `need` of its own chunks (the first ones; chosen so that an unrelated pair reaches the tile's largest bound
-            // with a margin), rows staged through the wave's own (still idle) row buffer and read back by broadcast, columns as
-            // one coalesced 16-byte load per lane, chunk and column block; then the same vote as at a stage boundary.  A tile that
-            // is hopeless leaves here; one that is not starts its walk as if nothing had happened.
-            const uint32_t need = (qmax + 16u) / 44u + 1u;
-            if (need <= per_wave && need <= 16u) {   // (workgroup-uniform)
-                uint4 *prows = &lds_rows[wave][0][0];   // (this wave's own row buffers: dead until the walk's first DMA, issued after the probe)
-#pragma unroll
-                for (uint32_t u = 0; u < PRE_TRIPS; ++u) prows[u * 64u + lane] = pre_rows[u];
-                for (uint32_t item = PRE_TRIPS * 64u + lane; item < need * (uint32_t)R; item += 64u) prows[item] = row_pair(item);
-                uint32_t pc[R];
-#pragma unroll
-                for (int r = 0; r < R; ++r) pc[r] = 0u;
-                auto probe_step = [&](uint32_t step, const uint4 &b0_, const uint4 &b1_) {
-#pragma unroll
-                    for (int r = 0; r < R; ++r) {
-                        const uint4 ar = prows[step * (uint32_t)R + (uint32_t)r];   // (uniform address: one broadcast read)
-                        const uint32_t l0 = (ar.x ^ b0_.y) | (ar.z ^ b0_.w), h0 = (ar.y ^ b0_.x) | (ar.w ^ b0_.z);
-                        const uint32_t l1 = (ar.x ^ b1_.y) | (ar.z ^ b1_.w), h1 = (ar.y ^ b1_.x) | (ar.w ^ b1_.z);
-                        pc[r] += (uint32_t)(__popc(l0) + __popc(h0)) + ((uint32_t)(__popc(l1) + __popc(h1)) << 16);
-                    }
-                };
-#pragma unroll
-                for (uint32_t st = 0; st < PRE; ++st) {
-                    if (st < need) probe_step(st, pre_cols[st][0], pre_cols[st][JL - 1]);
-                }
-                if (need > PRE) {   // (bounds beyond what 4 steps show: the next step's columns are requested a step ahead)
-                    uint4 nb0 = col_pair(0, PRE), nb1 = col_pair(JL - 1, PRE);
-                    for (uint32_t step = PRE; step < need; ++step) {
-                        const uint4 b0_ = nb0, b1_ = nb1;
-                        if (step + 1u < need) {
-                            nb0 = col_pair(0, step + 1u);
-                            nb1 = col_pair(JL - 1, step + 1u);
-                        }
-                        probe_step(step, b0_, b1_);
-                    }
-                }
-                uint64_t alive = 0ull;
-                const bool col0_ok = jb0 * 64u + lane < g.nB, col1_ok = (jb0 + 1u) * 64u + lane < g.nB;
-#pragma unroll
-                for (int r = 0; r < R; ++r) {
-                    if (a0 + (uint32_t)r < g.row_end) {
-                        const uint32_t qr = prune_lds[ROW_BOUNDS + (uint32_t)r];
-                        alive |= __ballot(col0_ok && (pc[r] & 0xFFFFu) < max(qr, qcol[0]));
-                        alive |= __ballot(col1_ok && (pc[r] >> 16) < max(qr, qcol[JL - 1]));
-                    }
-                }
-                const uint32_t slot_ = (uint32_t)(JL * LANES) + (prune_checks++ & 1u) * 4u;
-                if (lane == 0u) prune_lds[slot_ + wave] = alive != 0ull ? 1u : 0u;
-                asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-                const uint4 votes_ = *reinterpret_cast<const uint4 *>(&prune_lds[slot_]);
-                if ((votes_.x | votes_.y | votes_.z | votes_.w) == 0u) {
-                    // (counted in one of 1 024 slots: sixty million adds to ONE address queue up behind each other, and a wave
-                    // does not end before its add has been taken -- that queue was most of a pruned tile's time)
-                    if (g.prune_stats != nullptr && tid == 0u) atomicAdd(&g.prune_stats[(blockIdx.x & 1023u) * 4u], 1u);
-                    return;
-                }
-                // The tile survives.  WHICH rows of it, and which of its two column blocks, still hold a pair that is not hopeless
-                // on some wave's chunks?  (a second vote, paid by the survivors only: the tiles that leave above pay what they did)
-                uint32_t rows_alive = 0xFFFFFFFFu, blks_alive = 3u;
-                if ((g.prune_flags & 1u) == 0u) {
-                    uint32_t rowmask = 0u, blkmask = 0u;
-#pragma unroll
-                    for (int r = 0; r < R; ++r) {
-                        if (a0 + (uint32_t)r < g.row_end) {
-                            const uint32_t qr = prune_lds[ROW_BOUNDS + (uint32_t)r];
-                            const uint64_t al0 = __ballot(col0_ok && (pc[r] & 0xFFFFu) < max(qr, qcol[0]));
-                            const uint64_t al1 = __ballot(col1_ok && (pc[r] >> 16) < max(qr, qcol[JL - 1]));
-                            if ((al0 | al1) != 0ull) rowmask |= 1u << r;
-                            if (al0 != 0ull) blkmask |= 1u;
-                            if (al1 != 0ull) blkmask |= 2u;
-                        }
-                    }
-                    constexpr uint32_t PROBE_VOTES = ROW_BOUNDS + (uint32_t)R;   // 4 row masks, 4 block masks (the probe's own words:
-                                                                                 // the rotating vote rows belong to the checks)
-                    if (lane == 0u) {
-                        prune_lds[PROBE_VOTES + wave] = rowmask;
-                        prune_lds[PROBE_VOTES + 4u + wave] = blkmask;
-                    }
-                    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-                    const uint4 rv_ = *reinterpret_cast<const uint4 *>(&prune_lds[PROBE_VOTES]);
-                    const uint4 bv_ = *reinterpret_cast<const uint4 *>(&prune_lds[PROBE_VOTES + 4u]);
-                    rows_alive = (uint32_t)__builtin_amdgcn_readfirstlane((int)(rv_.x | rv_.y | rv_.z | rv_.w));
-                    blks_alive = (uint32_t)__builtin_amdgcn_readfirstlane((int)(bv_.x | bv_.y | bv_.z | bv_.w));
-                }
-                // (1b) SPARSE WALK.  A tile that survives the probe usually does so for ONE pair (a relative among 4 096 pairs): every
-                // pair outside the alive rows -- and outside the alive column block -- is as hopeless as a pruned tile's.  With at
-                // most SPARSE_ROWS alive rows the wave walks its chunks for those rows only: their plane pairs staged through the
-                // wave's row buffers a batch of chunks at a time (one 16-byte load per lane and 64 pieces) and read back by
-                // broadcast, the alive blocks' columns as in the dense walk, ~60 VALU instructions per (row, block, chunk)
-                // instead of 2 000 per chunk -- the walk turns from VALU bound to bound by the column loads.  The hopeless pairs get
-                // the count "every bin differs" (the worst key there is: no mark, rejected by both lists like their true value,
-                // which lies beyond both bounds), and the tile goes through the ordinary reduction and stores.
-                constexpr uint32_t SPARSE_ROWS = 4u, SPARSE_BATCH = 16u;
-                static_assert(SPARSE_BATCH * SPARSE_ROWS * 7u <= 2u * BUF_U4, "a batch of row pieces fits the wave's two row buffers");
-                const uint32_t n_alive = (uint32_t)__popc(rows_alive);
-                if (n_alive <= SPARSE_ROWS) {   // (workgroup-uniform)
-                    uint32_t rl[SPARSE_ROWS], cs[SPARSE_ROWS];
-                    {
-                        uint32_t m_ = rows_alive;
-#pragma unroll
-                        for (uint32_t x = 0; x < SPARSE_ROWS; ++x) {
-                            rl[x] = m_ != 0u ? (uint32_t)__builtin_ctz(m_) : 0u;
-                            m_ &= m_ - 1u;
-                            cs[x] = 0u;
-                        }
-                    }
-                    const uint32_t first_c = c_begin + wave;
-                    const uint32_t n_w = first_c < c_end ? (c_end - first_c + (uint32_t)W - 1u) / (uint32_t)W : 0u;   // this wave's chunks
-                    for (uint32_t s0_ = 0; s0_ < n_w; s0_ += SPARSE_BATCH) {
-                        const uint32_t nb = min(SPARSE_BATCH, n_w - s0_);
-                        // piece ((step * n_alive + x) * 7 + q): plane pair q of alive row x at the batch's chunk `step`
-                        for (uint32_t item = lane; item < nb * n_alive * 7u; item += 64u) {
-                            const uint32_t q_ = item % 7u, sx_ = item / 7u, x_ = sx_ % n_alive, st_ = sx_ / n_alive;
-                            const uint32_t r_ = x_ == 0u ? rl[0] : (x_ == 1u ? rl[1] : (x_ == 2u ? rl[2] : rl[3]));
-                            const uint32_t c_ = first_c + (s0_ + st_) * (uint32_t)W;
-                            prows[item] = *reinterpret_cast<const uint4 *>(g.A + (size_t)(a0 + r_) * sample_stride + (size_t)k_ * kmer_stride +
-                                                                           (size_t)c_ * BBITS + 2u * q_);
-                        }
-                        for (uint32_t st_ = 0; st_ < nb; ++st_) {
-                            const uint32_t c_ = first_c + (s0_ + st_) * (uint32_t)W;
-                            uint4 bb[JL][7];
-#pragma unroll
-                            for (int j = 0; j < JL; ++j) {
-                                if ((blks_alive >> j) & 1u) {
-                                    const uint32_t jb = (jb0 + j) < g.n_jblocks ? (jb0 + j) : (g.n_jblocks - 1u);
-                                    const uint4 *bp = g.B + (((size_t)jb * g.nk + k_) * g.ss64 + c_) * (7 * LANES) + lane;
-#pragma unroll
-                                    for (int q = 0; q < 7; ++q) bb[j][q] = bp[q * LANES];
-                                }
-                            }
-#pragma unroll
-                            for (uint32_t x = 0; x < SPARSE_ROWS; ++x) {
-                                if (x < n_alive) {
-                                    uint4 ar[7];
-#pragma unroll
-                                    for (int q = 0; q < 7; ++q) ar[q] = prows[(st_ * n_alive + x) * 7u + (uint32_t)q];   // (uniform address: broadcast)
-#pragma unroll
-                                    for (int j = 0; j < JL; ++j) {
-                                        if ((blks_alive >> j) & 1u) {
-                                            uint32_t mlo = ar[0].x ^ bb[j][0].y, mhi = ar[0].y ^ bb[j][0].x;
-                                            mlo = acc_mismatch_vvv(mlo, ar[0].z, bb[j][0].w);
-                                            mhi = acc_mismatch_vvv(mhi, ar[0].w, bb[j][0].z);
-#pragma unroll
-                                            for (int q = 1; q < 7; ++q) {
-                                                mlo = acc_mismatch_vvv(mlo, ar[q].x, bb[j][q].y);
-                                                mhi = acc_mismatch_vvv(mhi, ar[q].y, bb[j][q].x);
-                                                mlo = acc_mismatch_vvv(mlo, ar[q].z, bb[j][q].w);
-                                                mhi = acc_mismatch_vvv(mhi, ar[q].w, bb[j][q].z);
-                                            }
-                                            cs[x] += (uint32_t)(__popc(mlo) + __popc(mhi)) << (16 * j);
-                                        }
-                                    }
-                                }
-                            }
-                        }
-                    }
-                    // The alive rows' partial counts meet in LDS (each wave's first row buffer, which its staging is done with),
-                    // and ONE wave finishes the tile: at most 4 rows x 2 blocks of keys per lane instead of the 32 x 2 of the
-                    // ordinary reduction.  Only what can be read is written: an alive row's alive blocks to the band (a block
-                    // of a row is read by the merge only if a key in it marks it -- and a hopeless pair cannot), and for the
-                    // turned copy the 32-row stretch of the columns an alive key marks (the other rows of such a stretch hold
-                    // the worst key there is, like their true value rejected by the column's list).
-                    static_assert(R == 32 && KSL && !BIG && MODE == MODE_JACCARD, "the sparse finish is written for the 32-row single-k form");
-                    const uint32_t all_ = n_w * 64u;   // this wave's share of "every bin differs", for the fields of a block that is not alive
-                    const uint32_t dead_fields = ((blks_alive & 1u) ? 0u : all_) | ((blks_alive & 2u) ? 0u : all_ << 16);
-                    uint32_t *spw = reinterpret_cast<uint32_t *>(&lds_all[0]);
-#pragma unroll
-                    for (uint32_t x = 0; x < SPARSE_ROWS; ++x) spw[((wave * 2u) * (BUF_U4 * 4u)) + x * LANES + lane] = cs[x] | dead_fields;
-                    __syncthreads();
-                    if (wave != 0u) return;
-                    if (g.prune_stats != nullptr && lane == 0u) atomicAdd(&g.prune_stats[(blockIdx.x & 1023u) * 4u + 3u], 1u);
-                    const float v_dead = g.dtab[0];   // no bin in common
-                    float val[SPARSE_ROWS][JL];
-#pragma unroll
-                    for (uint32_t x = 0; x < SPARSE_ROWS; ++x) {
-#pragma unroll
-                        for (int h = 0; h < JL; ++h) val[x][h] = v_dead;
-                        if (x < n_alive) {
-                            uint32_t total = 0u;
-#pragma unroll
-                            for (uint32_t w = 0; w < (uint32_t)W; ++w) total += spw[((w * 2u) * (BUF_U4 * 4u)) + x * LANES + lane];
-                            const uint32_t i_ = a0 + rl[x];
-                            const uint32_t thr_ = g.r_thr[(size_t)(i_ - g.row_begin) * g.r_thr_stride];
-#pragma unroll
-                            for (int h = 0; h < JL; ++h) {
-                                if ((blks_alive >> h) & 1u) {
-                                    const uint32_t jc_ = (jb0 + (uint32_t)h) * 64u + lane;
-                                    const bool valid_ = pair_valid(g, i_, jc_);
-                                    float v = __builtin_inff();
-                                    if (valid_) {
-                                        v = g.dtab[g.ss64 * 64u - (h ? (total >> 16) : (total & 0xFFFFu))];   // (jaccard_out_value without a completeness correction: pruning launches have none)
-                                        ((float *)g.out)[pair_out_index(g, i_, jc_)] = v;
-                                    }
-                                    if (__ballot(valid_ && sortable_bits(v) < thr_) != 0ull && lane == 0u) {
-                                        atomicOr(&g.r_bits[(size_t)(i_ - g.row_begin) * g.r_bits_stride + ((jb0 + (uint32_t)h) >> 5)],
-                                                 1u << ((jb0 + (uint32_t)h) & 31u));
-                                    }
-                                    val[x][h] = v;
-                                }
-                            }
-                        }
-                    }
-                    if (g.out_t != nullptr && min((jb0 + (uint32_t)JL) * 64u, g.nB) > g.t_col_begin) {
-#pragma unroll
-                        for (int h = 0; h < JL; ++h) {
-                            const uint32_t jc = (jb0 + (uint32_t)h) * 64u + lane;
-                            if (((blks_alive >> h) & 1u) && jc >= g.t_col_begin && jc < g.nB) {
-                                float best = val[0][h];
-#pragma unroll
-                                for (uint32_t x = 1; x < SPARSE_ROWS; ++x) best = fminf(best, val[x][h]);
-                                if (g.t_flag == nullptr || sortable_bits(best) < g.t_thr[(size_t)jc * g.t_thr_stride]) {
-                                    float *dst = &g.out_t[(size_t)(jc - g.t_col_begin) * g.t_stride + (a0 - g.row_begin)];
-#pragma unroll
-                                    for (uint32_t q = 0; q < (uint32_t)R / 4u; ++q) {
-                                        float4 f = make_float4(v_dead, v_dead, v_dead, v_dead);
-#pragma unroll
-                                        for (uint32_t x = 0; x < SPARSE_ROWS; ++x) {
-                                            if (x < n_alive && (rl[x] >> 2) == q) {   // (uniform)
-                                                const uint32_t e_ = rl[x] & 3u;
-                                                if (e_ == 0u) f.x = val[x][h];
-                                                else if (e_ == 1u) f.y = val[x][h];
-                                                else if (e_ == 2u) f.z = val[x][h];
-                                                else f.w = val[x][h];
-                                            }
-                                        }
-                                        *reinterpret_cast<float4 *>(dst + 4u * q) = f;
-                                    }
-                                    if (g.t_flag != nullptr) {
-                                        g.t_flag[jc] = g.t_flag_value;
-                                        if (g.t_bits != nullptr) {
-                                            const uint32_t tb = (a0 - g.row_begin) >> 5;   // (a 32-row tile is one stretch)
-                                            atomicOr(&g.t_bits[(size_t)jc * g.t_bits_stride + (tb >> 5)], 1u << (tb & 31u));
-                                        }
-                                    }
-                                }
-                            }
-                        }
-                    }
-                    return;
-                }
-            }
-            // (2) ... and checks at stage boundaries of the walk, for the tiles the probe could not settle (bounds beyond what its
-            // chunks can show: after s stages an unrelated pair has 64 s mismatches on every wave, 63 s with a chance match or two).
-            // The first check sits where the tile's largest bound is reached, the next ones 1.5 x later each.
-            const uint32_t s0 = max(1u, (qmax + 63u * CH - 1u) / (63u * CH));
-            if (s0 < n_stages) prune_next = s0;
-        }
+        static_assert(!PRUNE || CH == 1, "the probe takes one chunk per wave and step");
+#include "pair_kslice_probe.inc"
     }
 
-    // Row staging: global -> LDS DMA (global_load_lds_dwordx4): piece p = (chunk*R + row)*7 + q
-    // of this wave's stage lands at slot p of the wave's buffer.  Chunks past the end of the
-    // sketch are clamped to the last one and never used.
-    // (SADDR_DMA: the per-lane part of the source address -- which row, which of the stage's CH chunks, which plane pair --
-    // is the same in every stage; it is kept as PPL 32-bit byte offsets and a stage supplies a scalar base.  A chunk past
-    // the end of the sketch -- sketch sizes that are not a multiple of 4 CH chunks -- reads the next k-mer length's or the
-    // next sample's words instead: inside the slab thanks to its A_PAD_ROWS zero rows, and never used)
+    // Row staging: global -> LDS DMA (SKL_STAGE_DMA, device_common.hpp), with the per-lane byte offsets of its source kept
     uint32_t dma_lane_off[SADDR_DMA ? PPL : 1];
     if constexpr (SADDR_DMA) {
 #pragma unroll
@@ -368,31 +60,6 @@
             dma_lane_off[u] = (uint32_t)(((size_t)(rc_ % R) * sample_stride + (size_t)(rc_ / R) * BBITS + 2u * (p_ % 7u)) * sizeof(uint64_t));
         }
     }
-#define SKL_STAGE_DMA(T, BUF)                                                                \
-    do {                                                                                     \
-        const uint32_t k_ = g.k_begin + kk0 + (BIG ? 0u : (T) / stages_per_k);               \
-        const uint32_t c0_ = c_begin + (BIG ? (T) : (T) % stages_per_k) * (W * CH) + wave * CH; \
-        if constexpr (SADDR_DMA) {                                                           \
-            const uint32_t cu_ = c0_ < g.ss64 ? c0_ : (g.ss64 - 1u);                         \
-            const uint64_t *base_ = g.A + (size_t)a0 * sample_stride + (size_t)k_ * kmer_stride + (size_t)cu_ * BBITS; \
-            _Pragma("unroll") for (int u = 0; u < PPL; ++u)                                  \
-                skl_dma16_saddr(base_, dma_lane_off[u], lds_base + (((uint32_t)wave * 2u + (BUF)) * (PPL * LANES) + u * 64u) * 16u); \
-        } else                                                                               \
-        _Pragma("unroll") for (int u = 0; u < PPL; ++u)                                      \
-        {                                                                                    \
-            const uint32_t pp_ = lane + u * 64u;                                             \
-            const uint32_t p_ = pp_ < (uint32_t)PIECES ? pp_ : pp_ - (uint32_t)PIECES;       \
-            const uint32_t q_ = p_ % 7u, rc_ = p_ / 7u;                                      \
-            const uint32_t r_ = rc_ % R, c_ = rc_ / R;                                       \
-            const uint32_t cc_ = (c0_ + c_) < g.ss64 ? (c0_ + c_) : (g.ss64 - 1u);           \
-            const uint64_t *src_ = (ABL & 4)                                                 \
-                ? g.A + ((((size_t)(a0 / R) * g.nk + k_) * g.ss64 + cc_) * R + r_) * BBITS + 2u * q_ /* timing only: a tile-major row slab */ \
-                : g.A + (size_t)(a0 + r_) * sample_stride +                                  \
-                      (size_t)k_ * kmer_stride + (size_t)cc_ * BBITS + 2u * q_;               \
-            skl_dma16(src_, lds_base + (((uint32_t)wave * 2u + (BUF)) * (PPL * LANES) + u * 64u) * 16u); \
-        }                                                                                    \
-    } while (0)
-
     const uint32_t lds_base = __builtin_amdgcn_readfirstlane(skl_lds_addr(&lds_all[0]));
     SKL_STAGE_DMA(0u, 0);
 
@@ -552,12 +219,11 @@
 #pragma unroll
                     for (int r = 0; r < R; ++r) {
                         if (a0 + (uint32_t)r < g.row_end) {   // (uniform; rows past the band hold no pair)
-                            const uint32_t qr = prune_lds[(uint32_t)(JL * LANES) + 8u + (uint32_t)r];
-                            alive |= __ballot(col0_ok && (cnt[r] & 0xFFFFu) < max(qr, qc0));
-                            alive |= __ballot(col1_ok && (cnt[r] >> 16) < max(qr, qc1));
+                            const AliveBallots al = alive_pairs(cnt[r], prune_lds[PRUNE_ROW_BOUNDS + (uint32_t)r], qc0, qc1, col0_ok, col1_ok);
+                            alive |= al.blk0 | al.blk1;
                         }
                     }
-                    const uint32_t slot_ = (uint32_t)(JL * LANES) + (prune_checks++ & 1u) * 4u;   // (two rotating rows of votes: one barrier per check)
+                    const uint32_t slot_ = PRUNE_VOTES + (prune_checks++ & 1u) * 4u;
                     if (lane == 0u) prune_lds[slot_ + wave] = alive != 0ull ? 1u : 0u;
                     asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");   // (no vmcnt wait: the prefetches stay in flight)
                     const uint4 votes_ = *reinterpret_cast<const uint4 *>(&prune_lds[slot_]);
@@ -577,206 +243,9 @@
             }
         }
 
-        // ---- end of a k-mer length: sum the 4 partial counts per pair through LDS ----
-        // (PRUNE: the lane id of the epilogue is made afresh -- two instructions -- instead of kept from the top of the kernel: with
-        // the probe and the sparse walk in between, the register allocator parked that one value in scratch and fetched it
-        // back before every use below, some thirty dependent scratch loads per tile)
-        if constexpr (PRUNE) asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(lane_e));
-        if (kl + 1 == n_outer) SKL_TRACE_MARK(2);
-        // The buffer this wave consumed last is dead (the next stage was prefetched into the
-        // other one), so every wave publishes into its own: [wave][buf][PX][LANES] words.
-        const uint32_t dead = (t - 1u) & 1u;
-        // word x of wave w: red_at(w, x)
-        uint32_t *red_rows = reinterpret_cast<uint32_t *>(&lds_all[0]);
-        uint32_t *red_over = reinterpret_cast<uint32_t *>(&lds_all[ROWS_U4]);
-        auto red_at = [&](uint32_t w, uint32_t x) -> uint32_t & {
-            return x < (uint32_t)XIN ? red_rows[(w * 2u + ((KSL && !BIG) ? 0u : dead)) * (BUF_U4 * 4u) + x * LANES + lane_e]
-                                     : red_over[(w * (uint32_t)XOV + (x - (uint32_t)XIN)) * LANES + lane_e];
-        };
-        // wave w finishes packed slots x = w (mod 4); fields stay below 2^16 (ss64 <= 1023)
-        float tval[(MODE == MODE_JACCARD && KSL) ? SLOTS * 2 : 1];   // this wave's keys, for out_t
-        // (RED_PHASES = 2: words [0, XIN) first, then words [XIN, PX) through the same buffer)
-#pragma unroll
-        for (int ph = 0; ph < RED_PHASES; ++ph) {
-        constexpr int XPH = PX / RED_PHASES;
-        if (ph > 0) __syncthreads();   // the previous phase's words have been summed
-#pragma unroll
-        for (int x = ph * XPH; x < (ph + 1) * XPH; ++x) red_at(wave, (uint32_t)(x - ph * XPH)) = packed_word(x);
-        if (ph == RED_PHASES - 1) {
-#pragma unroll
-            for (int x = 0; x < NCNT; ++x) cnt[x] = 0;
-        }
-        __syncthreads();
-#pragma unroll
-        for (int i = ph * (SLOTS / RED_PHASES); i < (ph + 1) * (SLOTS / RED_PHASES); ++i) {
-            const uint32_t x = (uint32_t)i * W + wave;
-            uint32_t total = 0;
-#pragma unroll
-            for (int w = 0; w < W; ++w) total += red_at((uint32_t)w, x - (uint32_t)(ph * XPH));
-            if constexpr (MODE == MODE_COREACC) {
-                // (ABL & 16, A/B build, timing only: only the last k-mer length's totals are parked -- what the kernel
-                // would cost if the per-k totals needed no memory at all; outputs wrong by construction)
-                if (!(ABL & 16) || kl + 1 == nkk) hist[i * MAX_FUSED_K + kl] = total;
-            } else if (BIG && kl + 1 < n_outer) {   // (uniform) not the last segment: add up
-                seg_acc[2 * i] = seg_acc[2 * i] + (total & 0xFFFFu);
-                seg_acc[2 * i + 1] = seg_acc[2 * i + 1] + (total >> 16);
-            } else {
-#pragma unroll
-                for (int h = 0; h < 2; ++h) {
-                    uint32_t r, j;
-                    field_pair(x, (uint32_t)h, r, j);
-                    uint32_t mism = h ? (total >> 16) : (total & 0xFFFFu);
-                    if constexpr (BIG) mism += seg_acc[2 * i + h];
-                    if constexpr (MODE == MODE_COUNTS) {
-                        if (in_tail && slice != 0u) {   // tail slices 1.. add into plane 1
-                            const uint32_t i_ = a0 + r, jc_ = (jb0 + j) * 64u + lane_e;
-                            if (pair_valid(g, i_, jc_)) {
-                                atomicAdd(&((uint32_t *)g.out)[pair_out_index(g, i_, jc_) * g.cnt_pair_stride +
-                                                               (uint64_t)(g.k_count + kk) * g.cnt_k_stride],
-                                          (c_end - c_begin) * 64u - mism);
-                            }
-                        } else if constexpr (FUSE) {   // (counts another workgroup reads back: write-through)
-                            if (g.fuse_variant & 1u) store_count(g, a0 + r, (jb0 + j) * 64u + lane_e, kk, (c_end - c_begin) * 64u, mism);   // EXPERIMENT: plain stores
-                            else store_count_agent(g, a0 + r, (jb0 + j) * 64u + lane_e, kk, (c_end - c_begin) * 64u, mism);
-                        } else {
-                            store_count<KSL && !BIG>(g, a0 + r, (jb0 + j) * 64u + lane_e, (tail_mode ? 0u : slice * g.k_count) + kk, (c_end - c_begin) * 64u, mism);
-                        }
-                    } else if constexpr (KSL) {
-                        const uint32_t i_ = a0 + r, jc_ = (jb0 + j) * 64u + lane_e;
-                        float v = __builtin_inff();
-                        const bool valid_ = pair_valid(g, i_, jc_);
-                        if (valid_) {
-                            v = jaccard_out_value(g, i_, jc_, mism);
-                            ((float *)g.out)[pair_out_index(g, i_, jc_)] = v;
-                        }
-                        if (g.r_bits != nullptr && i_ < g.row_end) {   // (wave-uniform: i_ is)
-                            // symmetric self kNN: does this 64-column block bring row i_ anything below its knn-th best?
-                            const uint32_t thr_ = g.r_thr[(size_t)(i_ - g.row_begin) * g.r_thr_stride];
-                            if (__ballot(valid_ && sortable_bits(v) < thr_) != 0ull && lane_e == 0u) {
-                                atomicOr(&g.r_bits[(size_t)(i_ - g.row_begin) * g.r_bits_stride + ((jb0 + j) >> 5)], 1u << ((jb0 + j) & 31u));
-                            }
-                        }
-                        tval[i * 2 + h] = v;
-                    } else {
-                        store_jaccard(g, a0 + r, (jb0 + j) * 64u + lane_e, mism);
-                    }
-                }
-            }
-        }
-        }
-        if constexpr (MODE == MODE_JACCARD && KSL) if (!BIG || kl + 1 == n_outer) {
-            // Symmetric self kNN: the keys of columns >= t_col_begin are also candidates of the
-            // ROW with that sample id.  The tile is turned through LDS so that a column's R keys
-            // leave as R/4 16-byte stores (one 64-byte run per column at R = 16).
-            if (g.out_t != nullptr && min((jb0 + (uint32_t)JL) * 64u, g.nB) > g.t_col_begin) {   // workgroup-uniform
-                constexpr uint32_t TP = R + 4;   // padded column pitch (floats), keeps 16-byte alignment
-                static_assert(JL * 64 * TP * 4 <= (ROWS_U4 + RED_U4) * 16, "the turned tile fits the LDS of the workgroup");
-                float *tt = reinterpret_cast<float *>(&lds_all[0]);
-                __syncthreads();   // every wave is done with the reduction words
-#pragma unroll
-                for (int i = 0; i < SLOTS; ++i) {
-#pragma unroll
-                    for (int h = 0; h < 2; ++h) {
-                        uint32_t r, j;
-                        field_pair((uint32_t)i * W + wave, (uint32_t)h, r, j);
-                        tt[(j * 64u + lane_e) * TP + r] = tval[i * 2 + h];
-                    }
-                }
-                __syncthreads();
-                constexpr uint32_t QUADS = R / 4;
-                for (uint32_t item = tid; item < (uint32_t)JL * 64u * QUADS; item += LANES * W) {
-                    const uint32_t c = item / QUADS, q = item % QUADS;
-                    const uint32_t jc = jb0 * 64u + c;
-                    if (jc >= g.t_col_begin && jc < g.nB) {
-                        const float4 v = *reinterpret_cast<const float4 *>(&tt[c * TP + 4u * q]);
-                        *reinterpret_cast<float4 *>(&g.out_t[(size_t)(jc - g.t_col_begin) * g.t_stride +
-                                                             (a0 - g.row_begin) + 4u * q]) = v;
-                        if (g.t_flag != nullptr) {   // does any of the four beat column jc's knn-th best? (invalid records are +inf)
-                            const float best = fminf(fminf(v.x, v.y), fminf(v.z, v.w));
-                            if (sortable_bits(best) < g.t_thr[(size_t)jc * g.t_thr_stride]) {
-                                g.t_flag[jc] = g.t_flag_value;
-                                if (g.t_bits != nullptr) {   // ... and in which 32-row stretch of the band
-                                    const uint32_t tb = (a0 - g.row_begin + 4u * q) >> 5;
-                                    atomicOr(&g.t_bits[(size_t)jc * g.t_bits_stride + (tb >> 5)], 1u << (tb & 31u));
-                                }
-                            }
-                        }
-                    }
-                }
-            }
-        }
-        // the next stage's DMA of every wave goes into the buffer just read: fence the reads
-        if (kl + 1 < n_outer) __syncthreads();
+#include "pair_kslice_finish.inc"
     }
-#undef SKL_STAGE_DMA
 
-    if constexpr (MODE == MODE_COREACC) {
-        // symmetric self kNN: (core, acc) of columns >= t_col_begin also leave turned, see MODE_JACCARD
-        constexpr uint32_t TP = R + 4;
-        static_assert(JL * 64 * TP * 8 <= (ROWS_U4 + RED_U4) * 16, "the turned tile fits the LDS of the workgroup");
-        const bool turned = g.out_t != nullptr && min((jb0 + (uint32_t)JL) * 64u, g.nB) > g.t_col_begin;   // workgroup-uniform
-        float2 *tt = reinterpret_cast<float2 *>(&lds_all[0]);
-        if (turned) __syncthreads();   // every wave is done with the reduction words
-        // store_coreacc() takes u16 fields, newest k lowest, as s2:s1:s0
-#pragma clang loop unroll(disable)
-        for (int i = 0; i < SLOTS; ++i) {
-            const uint32_t x = (uint32_t)i * W + wave;
-            uint32_t word[MAX_FUSED_K];   // word[f]: totals of the k-mer length f steps from the newest
-            if constexpr ((ABL & 16) != 0) {
-                const uint32_t last_ = hist[i * MAX_FUSED_K + (nkk - 1u)];
-#pragma unroll
-                for (int f = 0; f < MAX_FUSED_K; ++f) word[f] = (uint32_t)f < nkk ? last_ : 0u;
-            } else {
-#pragma unroll
-                for (int f = 0; f < MAX_FUSED_K; ++f) {
-                    word[f] = (uint32_t)f < nkk ? hist[i * MAX_FUSED_K + (nkk - 1u - f)] : 0u;
-                }
-            }
-#pragma clang loop unroll(disable)
-            for (int h = 0; h < 2; ++h) {
-                uint32_t r, j;
-                field_pair(x, (uint32_t)h, r, j);
-                const uint32_t sh = h * 16u;
-                const uint32_t s0 = ((word[0] >> sh) & 0xFFFFu) | (((word[1] >> sh) & 0xFFFFu) << 16);
-                const uint32_t s1 = ((word[2] >> sh) & 0xFFFFu) | (((word[3] >> sh) & 0xFFFFu) << 16);
-                const uint32_t s2 = ((word[4] >> sh) & 0xFFFFu) | (((word[5] >> sh) & 0xFFFFu) << 16);
-                const uint32_t i_ = a0 + r, jc_ = (jb0 + j) * 64u + lane_e;
-                float2 v = make_float2(__builtin_inff(), __builtin_inff());
-                const bool valid_ = pair_valid(g, i_, jc_);
-                if (valid_) {
-                    v = coreacc_value(g, i_, jc_, s0, s1, s2);
-                    ((float2 *)g.out)[pair_out_index(g, i_, jc_)] = v;
-                }
-                if (g.r_bits != nullptr && i_ < g.row_end) {   // see MODE_JACCARD; the key is the core distance
-                    const uint32_t thr_ = g.r_thr[(size_t)(i_ - g.row_begin) * g.r_thr_stride];
-                    if (__ballot(valid_ && sortable_bits(v.x) < thr_) != 0ull && lane_e == 0u) {
-                        atomicOr(&g.r_bits[(size_t)(i_ - g.row_begin) * g.r_bits_stride + ((jb0 + j) >> 5)], 1u << ((jb0 + j) & 31u));
-                    }
-                }
-                if (turned) tt[(j * 64u + lane_e) * TP + r] = v;
-            }
-        }
-        if (turned) {
-            __syncthreads();
-            constexpr uint32_t DUOS = R / 2;   // two records = one 16-byte store
-            for (uint32_t item = tid; item < (uint32_t)JL * 64u * DUOS; item += LANES * W) {
-                const uint32_t c = item / DUOS, q = item % DUOS;
-                const uint32_t jc = jb0 * 64u + c;
-                if (jc >= g.t_col_begin && jc < g.nB) {
-                    const float4 v = *reinterpret_cast<const float4 *>(&tt[c * TP + 2u * q]);
-                    *reinterpret_cast<float4 *>(reinterpret_cast<float2 *>(g.out_t) +
-                                                (size_t)(jc - g.t_col_begin) * g.t_stride + (a0 - g.row_begin) + 2u * q) = v;
-                    if (g.t_flag != nullptr) {   // two (core, acc) records: the key is the core distance
-                        if (sortable_bits(fminf(v.x, v.z)) < g.t_thr[(size_t)jc * g.t_thr_stride]) {
-                            g.t_flag[jc] = g.t_flag_value;
-                            if (g.t_bits != nullptr) {
-                                const uint32_t tb = (a0 - g.row_begin + 2u * q) >> 5;
-                                atomicOr(&g.t_bits[(size_t)jc * g.t_bits_stride + (tb >> 5)], 1u << (tb & 31u));
-                            }
-                        }
-                    }
-                }
-            }
-        }
-    }
+#include "pair_kslice_coreacc.inc"
 }
+#undef SKL_WALK_BLOCKS

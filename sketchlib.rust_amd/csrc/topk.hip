@@ -268,7 +268,7 @@ __device__ __forceinline__ void topk_merge_row(const TopkMergeArgs &g, const uin
     const uint32_t cols = g.cols;
     // the pair kernel marked the stretches of (1 << seg_shift) records that hold something below this row's knn-th best (as
     // of a moment ago: never too few).  Unmarked stretches are NOT candidates -- they may not even have been written (a
-    // pruned tile, pair_kslice_walk.inc)
+    // pruned tile, pair_kslice_probe.inc)
     const uint32_t *seg_bits = g.seg_bits != nullptr ? g.seg_bits + (size_t)row * g.seg_bits_stride : nullptr;
     const uint32_t seg_shift = g.seg_shift != 0u ? g.seg_shift : 6u;
     auto marked = [&](uint32_t q) { return seg_bits == nullptr || seg_marked(seg_bits, seg_shift, q); };
