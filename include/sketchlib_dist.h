@@ -272,6 +272,22 @@ int skl_ctx_early_break_stats(skl_ctx *ctx, uint64_t *pairs, uint64_t *completed
 int skl_ctx_early_break_blocks(skl_ctx *ctx, uint32_t *blk_rows, uint32_t *blk_cols, uint32_t *shift_rows, uint32_t *shift_cols,
                                int *pooled_lengths, int *mixed, uint8_t *block_lengths, size_t capacity);
 
+/* Diagnostic (no reference counterpart): the unit table of the chunk-split pair kernel.  What each workgroup of a k-sliced
+ * launch computes -- its tile, k-mer length, chunk range -- is a function of the launch's shape alone; the dense calls' launches
+ * of up to 65 536 workgroups read it from a table of 16-byte descriptors that the host builds once per shape and the context
+ * keeps (the last four shapes), instead of decoding the workgroup index in every wave.  Same results bit for bit either way.
+ * last_launch_read_one: 1 when the context's last pair-kernel launch read such a table, 0 when it decoded in the kernel;
+ * hits / builds: launches since the context was made that found their table in the cache / had it built and uploaded.  Any
+ * pointer may be null.
+ * skl_ctx_set_unit_table chooses the path for the context's later launches: SKL_UNIT_TABLE_BY_RULE (default) as above,
+ * SKL_UNIT_TABLE_NEVER the decode in the kernel everywhere, SKL_UNIT_TABLE_ALWAYS every launch whose form allows a table, the kNN
+ * drivers' bands included (tests and A/B timing; a table is then built for every new band shape). */
+#define SKL_UNIT_TABLE_BY_RULE (-1)
+#define SKL_UNIT_TABLE_NEVER 0
+#define SKL_UNIT_TABLE_ALWAYS 1
+int skl_ctx_unit_table(skl_ctx *ctx, int *last_launch_read_one, uint64_t *hits, uint64_t *builds);
+int skl_ctx_set_unit_table(skl_ctx *ctx, int mode);
+
 /* Diagnostic (no reference counterpart): tile pruning of the last skl_self_dists_knn / _partial call of the context.  The
  * whole-matrix self kNN with single-k keys (Jaccard / ANI, no completeness correction) leaves a 32 x 128 tile of the pair
  * space unfinished once every pair of it is, on the bins compared so far, already beyond both its samples' current knn-th

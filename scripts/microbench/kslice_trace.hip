@@ -85,6 +85,8 @@ int main(int argc, char **argv)
     // KT_SPAN=S: column groups numbered side by side (the library: 2); KT_INLINE=1: the prefix table in the kernel arguments (the library: 1)
     if (getenv("KT_SPAN")) g.group_span = (uint32_t)atoi(getenv("KT_SPAN"));
     if (getenv("KT_INLINE")) g.inline_prefix_ok = (uint32_t)atoi(getenv("KT_INLINE"));
+    // KT_TABLE=1: the launch reads what each workgroup computes from the host-built unit table (unit_table.hpp; the library's dense calls: 1)
+    if (getenv("KT_TABLE")) g.unit_table_ok = (uint32_t)atoi(getenv("KT_TABLE"));
     for (int i = 0; i < warm; ++i) CK(launch_pair_kernel_kslice(g, MODE_COUNTS, shape, true, ablate, ts, 0));
     CK(hipDeviceSynchronize());
     fprintf(stderr, "warm done\n");
@@ -256,6 +258,30 @@ int main(int argc, char **argv)
     stats(stream, "streaming chunks");
     stats(tail, "reduce + store");
     stats(total, "wave lifetime");
+    {   // THE HEAD, per round of workgroups (index on the XCD / workgroups resident per XCD): entry -> first row DMA issued (mark 7:
+        // the decode of the workgroup index, or the unit table's descriptor) and first request -> first rows landed.  One JSON line.
+        const uint32_t resident = (shape == 325 ? 3u : 4u) * 256u / 8u;
+        std::map<uint32_t, std::vector<double>> head, land;
+        for (size_t w = 0; w < n_waves; ++w) {
+            const uint64_t *r = &tr[w * TW];
+            if (r[3] == 0 || r[0] == 0 || r[7] == 0) continue;
+            const uint32_t round_ = (uint32_t)((w / wpw) >> 3) / resident;
+            head[round_].push_back((r[7] - r[0]) / 100.0);
+            land[round_].push_back((r[1] - r[7]) / 100.0);
+        }
+        auto med = [](std::vector<double> v) { std::sort(v.begin(), v.end()); return v[v.size() / 2]; };
+        auto p90 = [](std::vector<double> v) { std::sort(v.begin(), v.end()); return v[v.size() * 9 / 10]; };
+        printf("{\"tool\": \"kslice_trace head\", \"n\": %u, \"k_count\": %u, \"tail_slices\": %u, \"cost_order\": %u, \"unit_table\": %d, \"event_us\": %.1f, \"rounds\": [",
+               n, g.k_count, g.tail_slices, gp.tile_cost_order, ts.unit_table_used ? 1 : 0, ms * 1e3);
+        bool first_ = true;
+        for (auto &kv : head) {
+            printf("%s{\"round\": %u, \"waves\": %zu, \"entry_to_first_request_us_median\": %.2f, \"entry_to_first_request_us_p90\": %.2f, "
+                   "\"first_request_to_rows_landed_us_median\": %.2f, \"first_request_to_rows_landed_us_p90\": %.2f}",
+                   first_ ? "" : ", ", kv.first, kv.second.size(), med(kv.second), p90(kv.second), med(land[kv.first]), p90(land[kv.first]));
+            first_ = false;
+        }
+        printf("]}\n");
+    }
     // who is slow?  streaming time of first-round waves by XCD, by k-mer length, by wave-in-workgroup
     {
         std::map<int, std::pair<double, int>> by_xcc, by_k, by_wave, by_se;

@@ -73,6 +73,8 @@ _SIG = [
     ("skl_device_memcpy", C.c_int, [_P, _P, _P, C.c_size_t, C.c_int]),
     ("skl_ctx_get_knn_ties", C.c_int, [_P]),
     ("skl_ctx_early_break_stats", C.c_int, [_P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    ("skl_ctx_unit_table", C.c_int, [_P, C.POINTER(C.c_int), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    ("skl_ctx_set_unit_table", C.c_int, [_P, C.c_int]),
     ("skl_ctx_early_break_blocks", C.c_int, [_P, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32),
                                              C.POINTER(C.c_int), C.POINTER(C.c_int), _P, C.c_size_t]),
     ("skl_ctx_knn_prune_stats", C.c_int, [_P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
@@ -304,6 +306,16 @@ class Context:
             _check(load().skl_ctx_early_break_blocks(self._h, None, None, None, None, None, None, table.ctypes.data, table.size))
         return {"blocks": (br.value, bc.value), "shifts": (sr.value, sc.value), "pooled_lengths": pooled.value, "mixed": bool(mixed.value),
                 "block_lengths": table}
+
+    def unit_table(self):
+        """(the last pair launch read a unit table, launches that found theirs in the cache, launches that had one built) -- see the header."""
+        used, hits, builds = C.c_int(), C.c_uint64(), C.c_uint64()
+        _check(load().skl_ctx_unit_table(self._h, C.byref(used), C.byref(hits), C.byref(builds)))
+        return bool(used.value), hits.value, builds.value
+
+    def set_unit_table(self, mode):
+        """-1 (default): the dense calls' launches within the table's cap read a unit table; 0: none does; 1: every launch whose form allows it."""
+        _check(load().skl_ctx_set_unit_table(self._h, int(mode)))
 
     def knn_prune_stats(self, full=False):
         """(tiles, tiles left early) of the last self kNN call's prunable launches; full=True: + (stages of a whole tile,

@@ -180,6 +180,11 @@ extern "C" int skl_ctx_destroy(skl_ctx *ctx)
     if (ctx->tile_scratch.d_prefix) (void)hipFree(ctx->tile_scratch.d_prefix);
     if (ctx->tile_scratch.h_staging) (void)hipHostFree(ctx->tile_scratch.h_staging);
     if (ctx->tile_scratch.staged) (void)hipEventDestroy(ctx->tile_scratch.staged);
+    for (uint4 *d : ctx->tile_scratch.d_units) {
+        if (d) (void)hipFree(d);
+    }
+    if (ctx->tile_scratch.h_units) (void)hipHostFree(ctx->tile_scratch.h_units);
+    if (ctx->tile_scratch.units_staged) (void)hipEventDestroy(ctx->tile_scratch.units_staged);
     if (ctx->own_stream) (void)hipStreamDestroy(ctx->own_stream);
     if (ctx->aux_stream) (void)hipStreamDestroy(ctx->aux_stream);
     if (ctx->epi_stream) (void)hipStreamDestroy(ctx->epi_stream);
@@ -237,6 +242,23 @@ extern "C" int skl_ctx_early_break_stats(skl_ctx *ctx, uint64_t *pairs, uint64_t
     }
     if (pairs) *pairs = ctx->eb_pairs;
     if (completed_one_by_one) *completed_one_by_one = done;
+    return SKL_OK;
+}
+
+extern "C" int skl_ctx_set_unit_table(skl_ctx *ctx, int mode)
+{
+    if (!ctx) return fail(SKL_ERR_INVALID_ARG, "skl_ctx_set_unit_table: null context");
+    if (mode < -1 || mode > 1) return fail(SKL_ERR_INVALID_ARG, "skl_ctx_set_unit_table: mode = %d must be -1, 0 or 1", mode);
+    ctx->unit_table_mode = mode;
+    return SKL_OK;
+}
+
+extern "C" int skl_ctx_unit_table(skl_ctx *ctx, int *last_launch_read_one, uint64_t *hits, uint64_t *builds)
+{
+    if (!ctx) return fail(SKL_ERR_INVALID_ARG, "skl_ctx_unit_table: null context");
+    if (last_launch_read_one) *last_launch_read_one = ctx->last_unit_table ? 1 : 0;
+    if (hits) *hits = ctx->tile_scratch.units.hits;
+    if (builds) *builds = ctx->tile_scratch.units.builds;
     return SKL_OK;
 }
 

@@ -44,8 +44,14 @@ static hipError_t dispatch_pair_kernel(skl_ctx *ctx, const PairArgs &args_in, in
     ctx->last_kernel = pair_kernel_name(s, kslice);
     args.tile_cost_order = args_in.tile_cost_order != 0u && s.tile_cost_order && kslice ? 1u : 0u;   // (asked for by the dense calls' counts launches alone)
     if (args.tile_cost_order) ctx->last_kernel += " [tiles dealt by cost, half tiles last]";
-    if (kslice) return launch_pair_kernel_kslice(args, mode, s.shape, s.sliced_launch, s.ablate, ctx->tile_scratch, stream);
-    return launch_pair_kernel_ksplit(args, mode, s.ksplit_rows, ctx->tile_scratch, stream);
+    // the unit table: asked for by the dense calls (skl_ctx_set_unit_table 0: by nobody, 1: by every launch); the launcher gives one
+    // to the forms that read it, within its cap.  Which path ran is skl_ctx_unit_table()'s answer, not part of the kernel's description.
+    if (ctx->unit_table_mode >= 0) args.unit_table_ok = (uint32_t)ctx->unit_table_mode;
+    ctx->last_unit_table = false;
+    if (!kslice) return launch_pair_kernel_ksplit(args, mode, s.ksplit_rows, ctx->tile_scratch, stream);
+    const hipError_t e = launch_pair_kernel_kslice(args, mode, s.shape, s.sliced_launch, s.ablate, ctx->tile_scratch, stream);
+    ctx->last_unit_table = e == hipSuccess && ctx->tile_scratch.unit_table_used;
+    return e;
 }
 
 // Launch the pair kernel bracketed by HIP events on the context's stream.
@@ -152,6 +158,8 @@ static int run_counts_epilogue(skl_ctx *ctx, const skl_sketches *rows, const skl
     if (L.mixed) {
         g.xcd_interleave = 1;
         g.block_ke = plan->d_block_ke;
+        g.block_ke_host = plan->decision.block_ke.data();   // (the same table on the host: the unit table's builder reads it)
+        g.block_ke_bytes = plan->decision.block_ke.size();
         g.blk_shift_r = plan->geo.shift_r;
         g.blk_shift_c = plan->geo.shift_c;
         g.blk_cols = plan->geo.blk_cols;
@@ -169,6 +177,7 @@ static int run_counts_epilogue(skl_ctx *ctx, const skl_sketches *rows, const skl
         g.mid_band = L.mid_band ? 1u : 0u;
     }
     g.tile_cost_order = 1;   // (a request: plan_pair_shape decides)
+    g.unit_table_ok = 1;     // (a request: the launcher decides; unit_table.hpp)
     set_rows(&g, c, r0, r1, counts);
     SKL_TRY(ensure_ytab(rows));   // (before the pair launch: nothing may fail between it and the epilogue)
     // FUSED EPILOGUE (round 5): a plain k-sliced launch -- one workgroup per (tile, k-mer length), no chunk slices -- finishes
@@ -274,6 +283,7 @@ static int run_single_k_tail(skl_ctx *ctx, const skl_sketches *rows, const skl_s
     g.k_slices = 1;
     g.tail_slices = L.tail_slices;
     g.slice_chunks = L.slice_chunks;
+    g.unit_table_ok = 1;
     set_rows(&g, c, r0, r1, counts);
     void *const plane1 = (char *)counts + L.plane_bytes;
     SKL_TRY(plane1_before_launch(ctx, plane1, L.plane_bytes));
@@ -296,6 +306,7 @@ static int run_direct(skl_ctx *ctx, const skl_sketches *rows, const skl_sketches
     PairArgs g;
     SKL_TRY(fill_args(rows, cols, p, c.mode, jout, &g));
     g.tile_cost_order = 1;   // (a request: plan_pair_shape takes it for bin-match counts in self mode)
+    g.unit_table_ok = 1;     // (k-sliced counts and single-k launches within the table's cap)
     set_rows(&g, c, r0, r1, dst_dev);
     return timed_pair_launch(ctx, g, c.mode);
 }

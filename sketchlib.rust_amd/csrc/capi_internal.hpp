@@ -123,6 +123,8 @@ struct skl_ctx {
     long long timing_every = 0;         // skl_ctx_timing_enable / SKL_TIMING_EVERY: 0 = launches are not bracketed (default)
     size_t launches_seen = 0;           // pair-kernel launches since the last skl_ctx_timing_reset
     std::string last_kernel;
+    bool last_unit_table = false;       // the last pair launch read a unit table (unit_table.hpp; skl_ctx_unit_table)
+    int unit_table_mode = -1;           // skl_ctx_set_unit_table: -1 the dense calls' launches ask for a table, 0 nobody does, 1 every launch does
     // plane 1 of the counts scratch as the tail slices need it: all zero.  Valid for exactly
     // this (pointer, bytes) until anything else writes the scratch.
     const void *clean_plane1 = nullptr;

@@ -14,6 +14,7 @@
 #include "sketch_plan.hpp"  // the DNA sketching calls: kernel shapes, spans per sample, batches
 #include "finish_plan.hpp"  // device-side densify + transpose: launch rules, flag bits, the shared target rule
 #include "work_map.hpp"     // which workgroup computes what: TILE_PREFIX_INLINE, the fields below it reads and plans
+#include "unit_table.hpp"   // ... decoded once on the host: one descriptor per workgroup of a k-sliced launch, and the cache of such tables
 #include "inv_top_plan.hpp" // best hits of an inverted query: digits, list length, LDS bytes, the descending walk
 #include "within_plan.hpp"  // pairs within a distance cap: chunks, scan steps, the predicate, the (i, j) of a position
 
@@ -47,14 +48,19 @@ struct PairArgs {
     // operands
     const uint64_t *A;   // scalar operand: reference layout [nA + pad][nk][ss64][14]
     const uint4 *B;      // lane operand: [ceil(nB/64)][nk][ss64][7][64] x (2 planes x u64)
-    uint32_t nA, nB;     // valid samples on each side
+    // THE UNIT TABLE (unit_table.hpp; k-sliced launches of pair_kslice.hip): descriptor b says what workgroup b computes -- one
+    // 16-byte scalar load at the kernel's head instead of the decode of work_map.hpp.  Set by the launcher; null: the kernel
+    // decodes its workgroup index itself.  (Here, with the fields a workgroup's first requests need -- the two slab bases, nk,
+    // ss64, k_begin, n_jblocks -- so that they arrive in one scalar load of the kernel arguments.)
+    const uint4 *unit_table;
     uint32_t nk, ss64;
     uint32_t k_begin, k_count;
+    uint32_t n_jblocks;           // 64-wide column blocks
+    uint32_t self_mode;           // 1: A == B sample set, only i < j
     // pair space
     uint32_t row_begin, row_end;  // A rows computed by this launch
-    uint32_t self_mode;           // 1: A == B sample set, only i < j
+    uint32_t nA, nB;     // valid samples on each side
     uint32_t a_tiles;             // workgroup tiles along rows
-    uint32_t n_jblocks;           // 64-wide column blocks
     // balanced tile enumeration: active tiles are numbered column
     // group by column group and each XCD takes one contiguous eighth of the numbering
     uint32_t n_active_tiles;
@@ -149,6 +155,11 @@ struct PairArgs {
     // one and its rows in at most two (the larger count wins).  Null: every tile counts k_count lengths.
     const uint8_t *block_ke;
     uint32_t blk_shift_r, blk_shift_c, blk_cols;
+    // host side of the unit table: the caller's request (the dense calls; capi_dense.cpp applies skl_ctx_set_unit_table), and the host's
+    // own copy of block_ke (block_ke_bytes of it), which the table's builder reads
+    uint32_t unit_table_ok;
+    const uint8_t *block_ke_host;
+    uint64_t block_ke_bytes;
     // FUSED CORE/ACCESSORY EPILOGUE of a k-sliced MODE_COUNTS launch (one workgroup per (tile, k-mer length), no chunk slices;
     // pair_kslice.hip, FUSE): every workgroup stores its k-mer length's counts write-through, then ONE lane adds 1 to
     // fuse_counter[tile] (agent scope, returning); the workgroup whose add completes the tile's k_count arrivals reads the
@@ -169,7 +180,7 @@ struct PairArgs {
     double tolerance;             // ln(2 / (sketch_size * 64))   jaccard.rs:75
     double kf[MAX_FUSED_K];       // k-mer lengths as f64
 };
-static_assert(sizeof(PairArgs) == 536,"PairArgs is the pair kernels' argument: its layout is pinned");
+static_assert(sizeof(PairArgs) == 560,"PairArgs is the pair kernels' argument: its layout is pinned");
 
 // Device buffer the launchers may use for the tile-prefix table (owned by the context).
 struct TileScratch {
@@ -178,12 +189,23 @@ struct TileScratch {
     hipEvent_t staged = nullptr;   // recorded after each upload: h_staging may be rewritten once it fired
     size_t capacity = 0;           // entries
     uint64_t cached_key[4] = {~0ull, ~0ull, ~0ull, ~0ull};
+    std::vector<uint32_t> h_prefix;   // the prefix table of the last plan_tiles() call, on the host (the unit table's builder reads it)
+    // unit tables of k-sliced launches (unit_table.hpp): the cache's entries on the device, UNIT_TABLE_MAX_WG descriptors each,
+    // allocated on first use; one pinned staging buffer with its event, as above
+    UnitCache units;
+    uint4 *d_units[UNIT_CACHE_ENTRIES] = {};
+    uint4 *h_units = nullptr;
+    hipEvent_t units_staged = nullptr;
+    bool unit_table_used = false;     // the last launch_pair_kernel_kslice() call read a unit table
 };
 
 // The tile map of work_map.hpp (plan_tile_geometry + plan_tile_numbering) for tiles of rows_per_tile x cols_per_group
 // written into `args`; uploads the prefix table (self mode) on `stream`.  Returns the grid size (0 = nothing to do).
 hipError_t plan_tiles(PairArgs &args, uint32_t rows_per_tile, uint32_t cols_per_group,
                       TileScratch &scratch, hipStream_t stream, uint64_t *grid_out);
+// The unit table of a planned k-sliced launch (args after plan_tiles + plan_kslice_grid, n_wg workgroups of R-row tiles): from
+// the cache, or built (unit_table.hpp), staged in pinned memory and uploaded on `stream`; sets args.unit_table.
+hipError_t stage_unit_table(PairArgs &args, uint32_t R, bool counts, uint64_t n_wg, TileScratch &scratch, hipStream_t stream);
 
 // K-split variant for small launches (pair_ksplit.hip): rows_per_tile in {4, 8}.
 hipError_t launch_pair_kernel_ksplit(const PairArgs &args, int mode, int rows_per_tile,

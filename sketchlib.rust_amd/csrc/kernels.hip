@@ -77,6 +77,42 @@ hipError_t plan_tiles(PairArgs &args, uint32_t rows_per_tile, uint32_t cols_per_
         }
         args.tile_prefix = scratch.d_prefix;
     }
+    scratch.h_prefix.swap(prefix);
+    return hipSuccess;
+}
+
+// The unit table (unit_table.hpp) of the launch plan_tiles() and plan_kslice_grid() have just planned: from the context's cache
+// under the key of every field the decode reads, or built, staged and uploaded like the prefix table above.
+hipError_t stage_unit_table(PairArgs &args, uint32_t R, bool counts, uint64_t n_wg, TileScratch &scratch, hipStream_t stream)
+{
+    args.unit_table = nullptr;
+    if (!unit_table_fits(args, n_wg)) return hipSuccess;
+    const uint8_t *ke = counts ? args.block_ke_host : nullptr;
+    if (counts && args.block_ke != nullptr && ke == nullptr) return hipSuccess;   // (a per-block plan the host holds no copy of: the kernel decodes)
+    bool hit = false;
+    const int entry = scratch.units.lookup(unit_key(args, R, counts, ke, (size_t)args.block_ke_bytes, n_wg), &hit);
+    if (!hit) {
+        const size_t table_bytes = (size_t)UNIT_TABLE_MAX_WG * sizeof(UnitDesc);
+        hipError_t e = hipSuccess;
+        if (!scratch.h_units) e = hipHostMalloc((void **)&scratch.h_units, table_bytes, hipHostMallocDefault);
+        if (e == hipSuccess && !scratch.units_staged) e = hipEventCreateWithFlags(&scratch.units_staged, hipEventDisableTiming);
+        if (e == hipSuccess && !scratch.d_units[entry]) e = hipMalloc((void **)&scratch.d_units[entry], table_bytes);
+        // (the pinned buffer is rewritten only once the previous upload has read it; the entry's device table is ordered with
+        // the kernels that read its previous content by the stream)
+        if (e == hipSuccess) e = hipEventSynchronize(scratch.units_staged);
+        if (e == hipSuccess) {
+            PairArgs host = args;   // the decode reads the prefix table through the arguments: here the host's copy
+            if (host.self_mode && host.n_prefix_inline == 0u) host.tile_prefix = scratch.h_prefix.data();
+            build_unit_table(host, R, counts, ke, n_wg, reinterpret_cast<UnitDesc *>(scratch.h_units));
+            e = hipMemcpyAsync(scratch.d_units[entry], scratch.h_units, (size_t)n_wg * sizeof(UnitDesc), hipMemcpyHostToDevice, stream);
+        }
+        if (e == hipSuccess) e = hipEventRecord(scratch.units_staged, stream);
+        if (e != hipSuccess) {
+            scratch.units.drop(entry);
+            return e;
+        }
+    }
+    args.unit_table = scratch.d_units[entry];
     return hipSuccess;
 }
 

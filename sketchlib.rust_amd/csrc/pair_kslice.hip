@@ -46,7 +46,7 @@ namespace skl {
 // scripts/microbench/kslice_trace.hip: per-wave timeline (100 MHz wall clock) + hardware id,
 // and the shader-clock counter (s_memtime) at marks 1 and 2, i.e. around the streaming phase:
 // d(s_memtime) / d(wall clock) x 100 MHz is the clock the chip held meanwhile.  Record = 8 words:
-// marks 0..3, hardware id, s_memtime at marks 1 and 2.  The trace buffer rides in the dtab field
+// marks 0..3, hardware id, s_memtime at marks 1 and 2, mark 7 (the first row DMA issued).  The trace buffer rides in the dtab field
 // (unused by MODE_COUNTS); no output value depends on a stamp.
 #define skl_trace ((uint64_t *)g.dtab)
 #define SKL_TRACE_WORDS 8u
@@ -139,75 +139,115 @@ __global__ __launch_bounds__(LANES *WAVES_PER_WG, OCC != 0 ? OCC : (R > 16 ? 3 :
 
     // blockIdx -> (XCD, slot on that XCD) -> (tile slot[, k-mer length[, chunk slice]]): work_map.hpp, which also says why
     // the units of an XCD are ordered tile block by tile block and what tail slicing is
-    const uint32_t xcd = blockIdx.x & ((1u << g.xcd_shift) - 1u), s_idx = blockIdx.x >> g.xcd_shift;
-    const KsliceUnit unit = kslice_unit(g, s_idx, KSL, MODE == MODE_COUNTS);
-    if (unit.none) return;
-    const bool tail_mode = unit.tail_mode, in_tail = unit.in_tail;
-    const uint32_t slot = unit.slot, kk0 = unit.kk0, slice = unit.slice, n_slices = unit.n_slices;
+    //
+    // THE UNIT TABLE (unit_table.hpp).  None of that decode depends on data: it is a function of the launch's shape, and the
+    // shape comes back call after call.  The k-sliced counts / single-k forms therefore take it from a table the host built once
+    // (PairArgs::unit_table, descriptor blockIdx.x: ONE 16-byte scalar load, requested first thing) wherever the launcher gives
+    // them one; the decode below stays as the other run-time case -- launches past the table's cap, the kNN drivers' bands.
+    constexpr bool UNIT_TABLE = KSL && (MODE == MODE_COUNTS || MODE == MODE_JACCARD) && ABL == 0 && !BIG && !PRUNE && !FUSE;
+    uint32_t xcd = 0, slot = 0;   // (the fused epilogue's tile counter)
+    uint32_t kk0, slice, c_begin, c_end, a0, jb0;   // k index, chunk slice, chunk range of this workgroup; first row and 64-column block of its tile
+    bool in_tail, skip0 = false, skip1 = false;
+    const bool tail_mode = KSL && MODE == MODE_COUNTS && g.tail_slices > 1u;
     const uint32_t nkk = KSL ? 1u : g.k_count;                  // k-mer lengths it walks
-    // WAVE PRIORITY BY ROUND.  A SIMD issues for its oldest wave first, so the workgroups of a launch's
-    // second round -- dispatched into the slots the first round's oldest waves free -- get what three
-    // older waves leave them until those finish, and then run on alone at a lone wave's issue interval:
-    // that is the tail of every launch of 1-2.5 rounds.  Raising the priority of each later round by one
-    // (s_setprio, capped at 3) lets them work from the moment they arrive: -3 ... -4 % at 900-1 200
-    // genomes core/accessory, -7 % at 2 000 single-k (a second round of a few workgroups), +2 % at
-    // 2.5-2.7 rounds and nothing beyond, so the plan (plan_kslice_grid) asks for it up to 2.25 rounds
-    // (profiles/r02_ab_round_priority.jsonl).  Not for sliced launches (four quarter-rounds of short
-    // workgroups: +6 % at 800 genomes).
-    if (KSL && !tail_mode && g.round_size != 0u) {
-        const uint32_t round_ = s_idx / g.round_size;
-        if (round_ == 1u) __builtin_amdgcn_s_setprio(1);
-        else if (round_ == 2u) __builtin_amdgcn_s_setprio(2);
-        else if (round_ >= 3u) __builtin_amdgcn_s_setprio(3);
+    constexpr bool HALF_TILES = R == 16 && ABL == 0;   // (below: a 64-column block without a pair of the launch is not walked)
+    bool from_table = false;
+    if constexpr (UNIT_TABLE) {
+        from_table = g.unit_table != nullptr;
+        // (the two slab bases are asked for HERE, in the one batch of scalar loads that fetches the table's pointer -- left to the
+        // compiler they are loaded where the walk first uses them, a third round trip before the first row DMA)
+        asm volatile("" ::"s"(g.A), "s"(g.B));
     }
-    uint32_t c_begin, c_end;   // chunk range of this workgroup
-    slice_chunk_range(g, n_slices, slice, c_begin, c_end);
-    uint32_t jg, at;  // column group (JL blocks of 64), row tile
-    // (tiles dealt by cost, half tiles last on every XCD: a run-time case of the lookup, in the one form whose launches ask for it)
-    constexpr bool COST_ORDER = KSL && MODE == MODE_COUNTS && R == 16 && ABL == 0 && !FUSE;
-    if (COST_ORDER && g.tile_cost_order != 0u) {
-        if (!lookup_tile_by_cost_at(g, xcd, slot, jg, at)) return;
-    } else if (!lookup_tile_at(g, xcd, slot, jg, at)) {
-        return;
-    }
-    if constexpr ((ABL & 8) != 0) {   // timing only: every workgroup computes tile (0, group 1): all operands cache-hot
-        jg = 1;
-        at = 0;
-    }
-    const uint32_t jb0 = jg * JL;
-    const uint32_t a0 = g.row_begin + at * R;
-    if (jb0 >= g.n_jblocks) return;
-    if (a0 >= g.row_end) return;
-    if (g.self_mode && a0 >= (jg + 1u) * JL * 64u - 1u) return;   // tile entirely on/below the diagonal
-    if constexpr (KSL && MODE == MODE_COUNTS && !FUSE) {
-        // EARLY BREAK DECIDED PER BLOCK (PairArgs::block_ke): this workgroup counts k index kk0 of its tile; the tile's block of
-        // sample ids may want fewer lengths than the launch carries planes for
-        if (g.block_ke != nullptr) {
-            const uint32_t r_last = min(a0 + (uint32_t)R, g.row_end) - 1u;
-            const uint32_t bc = (jb0 * 64u) >> g.blk_shift_c;
-            const uint32_t ke_a = g.block_ke[(size_t)(a0 >> g.blk_shift_r) * g.blk_cols + bc];
-            const uint32_t ke_b = g.block_ke[(size_t)(r_last >> g.blk_shift_r) * g.blk_cols + bc];
-            if (kk0 >= max(ke_a, ke_b)) return;
+    if (from_table) {
+        typedef uint32_t desc_words __attribute__((ext_vector_type(4)));
+        const desc_words d_ = *(const __attribute__((address_space(4))) desc_words *)(g.unit_table + blockIdx.x);   // (uniform, read-only: a scalar load)
+        const UnitDesc d = {d_.x, d_.y, d_.z, d_.w};
+        if (unit_none(d)) return;
+        const uint32_t prio_ = unit_prio(d);   // (wave priority by round, below)
+        if (prio_ == 1u) __builtin_amdgcn_s_setprio(1);
+        else if (prio_ == 2u) __builtin_amdgcn_s_setprio(2);
+        else if (prio_ == 3u) __builtin_amdgcn_s_setprio(3);
+        a0 = d.a0;
+        jb0 = unit_jb0(d);
+        kk0 = unit_kk0(d);
+        slice = unit_slice(d);
+        c_begin = unit_c_begin(d);
+        c_end = unit_c_end(d);
+        in_tail = unit_plane1(d);   // (read as `in_tail && slice != 0`: the tail slices that add into plane 1)
+        skip0 = unit_walk(d) == UNIT_WALK_1_2;
+        skip1 = unit_walk(d) == UNIT_WALK_0_1;
+    } else {
+        xcd = blockIdx.x & ((1u << g.xcd_shift) - 1u);
+        const uint32_t s_idx = blockIdx.x >> g.xcd_shift;
+        const KsliceUnit unit = kslice_unit(g, s_idx, KSL, MODE == MODE_COUNTS);
+        if (unit.none) return;
+        in_tail = unit.in_tail;
+        slot = unit.slot;
+        kk0 = unit.kk0;
+        slice = unit.slice;
+        const uint32_t n_slices = unit.n_slices;
+        // WAVE PRIORITY BY ROUND.  A SIMD issues for its oldest wave first, so the workgroups of a launch's
+        // second round -- dispatched into the slots the first round's oldest waves free -- get what three
+        // older waves leave them until those finish, and then run on alone at a lone wave's issue interval:
+        // that is the tail of every launch of 1-2.5 rounds.  Raising the priority of each later round by one
+        // (s_setprio, capped at 3) lets them work from the moment they arrive: -3 ... -4 % at 900-1 200
+        // genomes core/accessory, -7 % at 2 000 single-k (a second round of a few workgroups), +2 % at
+        // 2.5-2.7 rounds and nothing beyond, so the plan (plan_kslice_grid) asks for it up to 2.25 rounds
+        // (profiles/r02_ab_round_priority.jsonl).  Not for sliced launches (four quarter-rounds of short
+        // workgroups: +6 % at 800 genomes).
+        if (KSL && !tail_mode && g.round_size != 0u) {
+            const uint32_t round_ = s_idx / g.round_size;
+            if (round_ == 1u) __builtin_amdgcn_s_setprio(1);
+            else if (round_ == 2u) __builtin_amdgcn_s_setprio(2);
+            else if (round_ >= 3u) __builtin_amdgcn_s_setprio(3);
         }
-    }
-    // HALF TILES (2 columns per lane).  A 64-column block of the tile that holds no pair of the launch is
-    // not walked: block 0 of a tile that straddles the diagonal when every column of it is <= the
-    // tile's first row (self mode: 4 of the 8 diagonal row tiles of every column group at 16 rows, 2 of
-    // 4 at 32 -- 6.5 % of a 1 000-genome launch's lane-pairs), block 1 when the launch's columns end
-    // in block 0 (an odd number of 64-column blocks).  The chunk walk below is instantiated for the
-    // three cases and chosen per workgroup (uniform branch); the skipped block's column registers are
-    // never loaded and its count fields stay 0 (its pairs are invalid and never stored).
-    constexpr bool HALF_TILES = R == 16 && ABL == 0;
+        slice_chunk_range(g, n_slices, slice, c_begin, c_end);
+        uint32_t jg, at;  // column group (JL blocks of 64), row tile
+        // (tiles dealt by cost, half tiles last on every XCD: a run-time case of the lookup, in the one form whose launches ask for it)
+        constexpr bool COST_ORDER = KSL && MODE == MODE_COUNTS && R == 16 && ABL == 0 && !FUSE;
+        if (COST_ORDER && g.tile_cost_order != 0u) {
+            if (!lookup_tile_by_cost_at(g, xcd, slot, jg, at)) return;
+        } else if (!lookup_tile_at(g, xcd, slot, jg, at)) {
+            return;
+        }
+        if constexpr ((ABL & 8) != 0) {   // timing only: every workgroup computes tile (0, group 1): all operands cache-hot
+            jg = 1;
+            at = 0;
+        }
+        jb0 = jg * JL;
+        a0 = g.row_begin + at * R;
+        if (jb0 >= g.n_jblocks) return;
+        if (a0 >= g.row_end) return;
+        if (g.self_mode && a0 >= (jg + 1u) * JL * 64u - 1u) return;   // tile entirely on/below the diagonal
+        if constexpr (KSL && MODE == MODE_COUNTS && !FUSE) {
+            // EARLY BREAK DECIDED PER BLOCK (PairArgs::block_ke): this workgroup counts k index kk0 of its tile; the tile's block of
+            // sample ids may want fewer lengths than the launch carries planes for
+            if (g.block_ke != nullptr) {
+                const uint32_t r_last = min(a0 + (uint32_t)R, g.row_end) - 1u;
+                const uint32_t bc = (jb0 * 64u) >> g.blk_shift_c;
+                const uint32_t ke_a = g.block_ke[(size_t)(a0 >> g.blk_shift_r) * g.blk_cols + bc];
+                const uint32_t ke_b = g.block_ke[(size_t)(r_last >> g.blk_shift_r) * g.blk_cols + bc];
+                if (kk0 >= max(ke_a, ke_b)) return;
+            }
+        }
+        // HALF TILES (2 columns per lane).  A 64-column block of the tile that holds no pair of the launch is
+        // not walked: block 0 of a tile that straddles the diagonal when every column of it is <= the
+        // tile's first row (self mode: 4 of the 8 diagonal row tiles of every column group at 16 rows, 2 of
+        // 4 at 32 -- 6.5 % of a 1 000-genome launch's lane-pairs), block 1 when the launch's columns end
+        // in block 0 (an odd number of 64-column blocks).  The chunk walk below is instantiated for the
+        // three cases and chosen per workgroup (uniform branch); the skipped block's column registers are
+        // never loaded and its count fields stay 0 (its pairs are invalid and never stored).
 #ifdef SKL_AB
-    // (A/B build only: SKL_HALF_TILES=0 walks every block.  The run-time condition costs the 16-row k-sliced
-    // form 11 registers spilled outside its loops -- 44 B of scratch per lane, 26 MB of HBM traffic per
-    // 1 000-genome launch -- so the product library does not carry it.)
-    const bool half_ok = HALF_TILES && g.no_half_tiles == 0u;
+        // (A/B build only: SKL_HALF_TILES=0 walks every block.  The run-time condition costs the 16-row k-sliced
+        // form 11 registers spilled outside its loops -- 44 B of scratch per lane, 26 MB of HBM traffic per
+        // 1 000-genome launch -- so the product library does not carry it.)
+        const bool half_ok = HALF_TILES && g.no_half_tiles == 0u;
 #else
-    constexpr bool half_ok = HALF_TILES;
+        constexpr bool half_ok = HALF_TILES;
 #endif
-    const bool skip0 = half_ok && tile_skips_block0(g.self_mode, a0, jb0);   // (work_map.hpp: the cost order's classes are these two tests)
-    const bool skip1 = half_ok && tile_skips_block1(jb0, g.n_jblocks);
+        skip0 = half_ok && tile_skips_block0(g.self_mode, a0, jb0);   // (work_map.hpp: the cost order's classes are these two tests)
+        skip1 = half_ok && tile_skips_block1(jb0, g.n_jblocks);
+    }
     // The walk is TEXTUALLY included once per case (pair_kslice_walk.inc and the texts it includes; SKL_WALK_BLOCKS = the
     // column blocks [J0, J1) it walks, undefined again by the text), not a lambda or a function template: wrapping it in either changes hipcc's register
     // allocation of the 32-row form (168 VGPRs + 144 B of spills per lane instead of 144 VGPRs).  No value of
@@ -343,6 +383,7 @@ hipError_t launch_pair_kernel_kslice(const PairArgs &args_in, int mode, int shap
                                      TileScratch &scratch, hipStream_t stream)
 {
     PairArgs args = args_in;
+    scratch.unit_table_used = false;
     if (args.row_end <= args.row_begin || args.nB == 0) return hipSuccess;
     if (!kslice_supported(args, mode, k_sliced)) return hipErrorInvalidValue;
     // beyond 65 535 bins: segments of KSLICE_SEG_CHUNKS chunks (a multiple of every form's chunks per stage)
@@ -370,6 +411,16 @@ hipError_t launch_pair_kernel_kslice(const PairArgs &args_in, int mode, int shap
     if (args.fuse_counter != nullptr && !(k_sliced && mode == MODE_COUNTS && args.k_slices == 1u && args.tail_slices <= 1u && args.seg_chunks == 0u &&
                                           (shape == 165 || shape == 325) && args.k_count <= (uint32_t)MAX_FUSED_K && args.fuse_out != nullptr)) {
         return hipErrorInvalidValue;   // (the caller skips the epilogue launch when it asks for the fused one)
+    }
+    // the unit table (UNIT_TABLE in the kernel: the k-sliced counts / single-k forms without segments, pruning, the fused
+    // epilogue or an ablation), for the callers that ask for one
+    args.unit_table = nullptr;
+    scratch.unit_table_used = false;
+    if (args.unit_table_ok != 0u && k_sliced && (mode == MODE_COUNTS || mode == MODE_JACCARD) && ablate == 0 && args.seg_chunks == 0u &&
+        args.prune_q_rows == nullptr && args.fuse_counter == nullptr && (shape == 165 || shape == 325)) {
+        const hipError_t ue = stage_unit_table(args, (uint32_t)R, mode == MODE_COUNTS, n_wg, scratch, stream);
+        if (ue != hipSuccess) return ue;
+        scratch.unit_table_used = args.unit_table != nullptr;
     }
     const dim3 grid((unsigned)n_wg);
 #ifdef SKL_AB

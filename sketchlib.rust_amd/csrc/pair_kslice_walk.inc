@@ -62,6 +62,7 @@
     }
     const uint32_t lds_base = __builtin_amdgcn_readfirstlane(skl_lds_addr(&lds_all[0]));
     SKL_STAGE_DMA(0u, 0);
+    SKL_TRACE_MARK(7);   // (trace build: the first row DMA is issued -- entry to here is the head's cost)
 
     // Next valid chunk of this wave after (kl, ts, ci) in its walk over k-mer lengths, stages
     // and chunks (wave-uniform scalar code); false when the walk is over.
