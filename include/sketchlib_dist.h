@@ -230,6 +230,34 @@ int skl_cross_dists_within(skl_ctx *ctx, const skl_sketches *ref, const skl_sket
                            size_t ref_begin, size_t ref_end, double max_first, double max_second, uint32_t *out_i,
                            uint32_t *out_j, float *out_d, uint64_t capacity, int out_on_device, uint64_t *n_found);
 
+/* ---- single-linkage clusters under a distance cap (no reference counterpart): the pairs above, followed to their components ----
+ * What dereplication, outbreak detection and "one representative per strain" ask for is not the edge list but the clusters it
+ * connects: one label per sample instead of one record per pair.  skl_self_clusters_within applies EXACTLY the pairs that
+ * skl_self_dists_within would list for rows [row_begin, row_end) with the same p, max_first and max_second -- the same
+ * PREDICATE on the same stored f32 values (ANI turns the test round, a NaN never passes, completeness vectors and
+ * completeness_cutoff apply unchanged), the same row-range and cap errors -- and joins the two samples of each; no record is
+ * written (csrc/cluster.hip: a lock-free union-find on the device behind each dense band).
+ * LABELS: one u32 per sample of the slab -- all n of them, whatever the row range.  Two samples are in one cluster when a chain of
+ * passing pairs connects them.  On return labels[i] is the LOWEST sample index of i's cluster: a property of the data alone,
+ * never of scheduling, and labels[labels[i]] == labels[i].  *n_clusters is the number of i with labels[i] == i.
+ * `labels_on_device` != 0: labels is a device pointer.  Either way the call returns with the stream idle and the labels in place.
+ * FLAGS: 0 -- the labels are set to 0..n-1 first.  SKL_CLUSTERS_CONTINUE -- the labels hold the result of earlier calls and are
+ * built upon: calls over consecutive row ranges chained this way give the whole call's labels.  The input must then satisfy
+ * labels[i] <= i for every i (any output of these two calls does); it is checked on the device before anything follows a
+ * label, and a violation is SKL_ERR_INVALID_ARG with labels unchanged.
+ * EDGES: labels or n_clusters NULL: SKL_ERR_INVALID_ARG.  A slab of 0 samples: SKL_OK, *n_clusters = 0.  A single sample or an
+ * empty row range applies no pair: the labels are still initialised (or checked and kept, with CONTINUE) and counted.  The row
+ * range is evaluated in the bands of the within calls (same budget); the labels stay on the device between them. */
+#define SKL_CLUSTERS_CONTINUE 1   /* labels hold the result of earlier calls; without it they are set to 0..n-1 first */
+int skl_self_clusters_within(skl_ctx *ctx, const skl_sketches *s, const skl_dist_params *p, size_t row_begin, size_t row_end,
+                             double max_first, double max_second, uint32_t *labels, int labels_on_device, int flags,
+                             uint64_t *n_clusters);
+/* MERGE: joins two partitions of the same n samples, for instance the results of two row ranges computed on two devices, each
+ * from the identity.  On return labels holds the clusters connected through either partition, in the same lowest-index form,
+ * and *n_clusters their number; `other` is only read.  Both arrays live on the same side (`on_device`) and both are checked
+ * as above (SKL_ERR_INVALID_ARG, labels unchanged).  No slab and no distances are involved.  n == 0: SKL_OK, *n_clusters = 0. */
+int skl_clusters_merge(skl_ctx *ctx, uint32_t *labels, const uint32_t *other, uint64_t n, int on_device, uint64_t *n_clusters);
+
 /* ---- sparse k-nearest-neighbour distances ----
  * Output rows hold `knn` items sorted ascending by key, where key = d0 for Jaccard / core for
  * CoreAcc, or 1-ANI for ANI (mod.rs:173-176).  out_d1 is written for CoreAcc only and may be NULL

@@ -101,6 +101,9 @@ _SIG = [
                                         C.c_uint64, C.c_int, C.POINTER(C.c_uint64)]),
     ("skl_cross_dists_within", C.c_int, [_P, _P, _P, C.POINTER(DistParams), C.c_size_t, C.c_size_t, C.c_double, C.c_double, _P, _P, _P,
                                          C.c_uint64, C.c_int, C.POINTER(C.c_uint64)]),
+    ("skl_self_clusters_within", C.c_int, [_P, _P, C.POINTER(DistParams), C.c_size_t, C.c_size_t, C.c_double, C.c_double, _P, C.c_int, C.c_int,
+                                           C.POINTER(C.c_uint64)]),
+    ("skl_clusters_merge", C.c_int, [_P, _P, _P, C.c_uint64, C.c_int, C.POINTER(C.c_uint64)]),
     ("skl_self_dists_knn", C.c_int, [_P, _P, C.POINTER(DistParams), C.c_size_t, _P, _P, _P,
                                      C.c_int]),
     ("skl_self_dists_knn_rows", C.c_int, [_P, _P, C.POINTER(DistParams), C.c_size_t, C.c_size_t,
@@ -542,6 +545,55 @@ def self_dists_within(ctx, s, p, max_dist, max_acc=np.inf, r0=0, r1=None, capaci
 def cross_dists_within(ctx, r, q, p, max_dist, max_acc=np.inf, r0=0, r1=None, capacity=None):
     """The same for reference rows [r0, r1) against every query -> (i_ref, j_query, d), ascending i_ref * n_query + j_query."""
     return _dists_within(ctx, r, p, max_dist, max_acc, r0, r1, capacity, q)
+
+
+# ---- single-linkage clusters under a distance cap ----
+
+CLUSTERS_CONTINUE = 1      # SKL_CLUSTERS_CONTINUE
+
+
+def clusters_within(ctx, s, p, max_dist, max_acc=np.inf, r0=0, r1=None, labels=None):
+    """skl_self_clusters_within: the pairs self_dists_within would list for rows [r0, r1), followed to their connected
+    components -> (labels uint32 [n], n_clusters); labels[i] is the lowest sample index of i's cluster.  labels=None starts
+    from the identity and returns a new numpy array; a uint32 numpy array or a device tensor of n elements (int32 bits) holds
+    the result of earlier calls, is built upon in place (SKL_CLUSTERS_CONTINUE: labels[i] <= i is checked) and returned."""
+    r1 = s.n if r1 is None else r1
+    flags = 0 if labels is None else CLUSTERS_CONTINUE
+    if labels is None:
+        labels = np.empty(s.n, dtype=np.uint32)
+    elif isinstance(labels, np.ndarray):
+        if labels.dtype != np.uint32 or not labels.flags.c_contiguous or labels.size < s.n:
+            raise ValueError("labels: a contiguous uint32 array of n elements")
+    addr, dev = _ptr(labels)
+    found = C.c_uint64(0)
+    _check(load().skl_self_clusters_within(ctx._h, s._h, C.byref(p), r0, r1, max_dist, max_acc, addr, dev, flags, C.byref(found)))
+    return labels, int(found.value)
+
+
+def clusters_merge(ctx, a, b):
+    """skl_clusters_merge: the clusters connected through either of two partitions of the same samples -> (labels, n_clusters).
+    Two numpy arrays give a new array; two device tensors are merged into `a` in place, which is returned."""
+    (_pa, dev_a), (_pb, dev_b) = _ptr(a), _ptr(b)
+    if dev_a != dev_b:
+        raise ValueError("the two partitions must live on the same side")
+    if not dev_a:
+        a = np.array(a, dtype=np.uint32, copy=True).reshape(-1)
+        b = np.ascontiguousarray(b, dtype=np.uint32).reshape(-1)
+    n = a.size if not dev_a else a.numel()
+    if n != (b.size if not dev_b else b.numel()):
+        raise ValueError("the two partitions differ in length")
+    found = C.c_uint64(0)
+    _check(load().skl_clusters_merge(ctx._h, _ptr(a)[0], _ptr(b)[0], n, dev_a, C.byref(found)))
+    return a, int(found.value)
+
+
+def dereplicate(ctx, s, p, max_dist, max_acc=np.inf):
+    """One representative per cluster under the cap -> (Sketches, ids): ids is the ascending list of the samples that are their
+    own label (the lowest index of each cluster), the new slab s.select(ids); `s` is untouched and stays on the device."""
+    labels, n_clusters = clusters_within(ctx, s, p, max_dist, max_acc)
+    ids = np.flatnonzero(labels == np.arange(s.n, dtype=np.uint32)).astype(np.uint32)
+    assert ids.size == n_clusters
+    return s.select(ids), ids
 
 
 # ---- sparse ----

@@ -9,7 +9,7 @@
 //   capi_knn.cpp       the kNN drivers;  capi_cand.cpp  candidate lists;  capi_pairs.cpp  pair lists;  capi_rccl.cpp  the RCCL gather
 //   capi_sketch.cpp    DNA sketching;  capi_reads.cpp  read survivors;  capi_aa.cpp  amino-acid sketching;  capi_inv.cpp  inverted query
 //   capi_finish.cpp    finishing sketch streams on the device;  capi_slab.cpp  new slabs from resident ones
-//   capi_within.cpp    the pairs of a dense call that lie within a distance cap
+//   capi_within.cpp    the pairs of a dense call that lie within a distance cap;  capi_clusters.cpp  the clusters those pairs connect
 // Everything declared here is SKL_INTERNAL (hidden): the library exports the functions of the public header and nothing else of the host layer.
 // How a dense call and each pair-kernel launch is shaped is decided in dense_plan.hpp (pure, no HIP), reached through kernels.h;
 // the early break's decision in eb_plan.hpp; how the kNN drivers cut and feed their bands in knn_plan.hpp (both pure, no HIP).
@@ -98,7 +98,8 @@ enum ScratchSlot : int {
     SCRATCH_SKETCH_FINISHED = 16,  // GPU sketching: finished words, first signs and flags on their way to the host,
     SCRATCH_SKETCH_TARGETS = 17,   // the finish kernel's target arrays (global form)
     SCRATCH_WITHIN = 18,           // pairs within a cap: running total, chunk offsets, chunk counts (within_plan.hpp)
-    SCRATCH_SLOTS = 19
+    SCRATCH_CLUSTER_LABELS = 19,   // clusters within a cap: error word, root count, and the label array(s) of a caller whose own are on the host (cluster_plan.hpp)
+    SCRATCH_SLOTS = 20
 };
 
 struct skl_ctx {

@@ -17,6 +17,7 @@
 #include "unit_table.hpp"   // ... decoded once on the host: one descriptor per workgroup of a k-sliced launch, and the cache of such tables
 #include "inv_top_plan.hpp" // best hits of an inverted query: digits, list length, LDS bytes, the descending walk
 #include "within_plan.hpp"  // pairs within a distance cap: chunks, scan steps, the predicate, the (i, j) of a position
+#include "cluster_plan.hpp" // clusters under a distance cap: the label form, the per-sample grids, the scratch layout
 
 namespace skl {
 
@@ -703,5 +704,27 @@ struct WithinArgs {
 hipError_t launch_within_count(const WithinArgs &a, hipStream_t stream);
 hipError_t launch_within_scan(const WithinArgs &a, hipStream_t stream);
 hipError_t launch_within_scatter(const WithinArgs &a, hipStream_t stream);
+
+// cluster.hip: single-linkage clusters under a distance cap.  labels: [n] u32 in device memory, a partition in cluster_plan.hpp's
+// form (labels[i] <= i) from the init or the check onward; the band fields are WithinArgs' (self mode only)
+struct ClusterArgs {
+    uint32_t *labels;             // [n]
+    uint64_t n;                   // samples, <= CLUSTER_MAX_SAMPLES
+    const float *band;            // union: [m][ncols] f32, 16-byte aligned base, within_band_bytes(m, ncols) readable
+    uint64_t m;                   // positions of the band, < WITHIN_BAND_PAIR_LIMIT
+    uint64_t chunks;              // within_chunks(m)
+    uint32_t ncols;
+    uint64_t first;               // condensed position of band[0]
+    WithinPred pred;
+    const uint32_t *other;        // merge: [n], checked like labels
+    uint32_t *error;              // check: device word, set to 1 by a label beyond its index (never cleared by a kernel)
+    unsigned long long *count;    // count: device word the roots are added to
+};
+hipError_t launch_cluster_init(const ClusterArgs &a, hipStream_t stream);      // labels[i] = i
+hipError_t launch_cluster_check(const ClusterArgs &a, const uint32_t *labels, hipStream_t stream);   // labels[i] <= i, or *error = 1
+hipError_t launch_cluster_union(const ClusterArgs &a, hipStream_t stream);     // the band's passing pairs
+hipError_t launch_cluster_merge(const ClusterArgs &a, hipStream_t stream);     // union(i, other[i])
+hipError_t launch_cluster_flatten(const ClusterArgs &a, hipStream_t stream);   // labels[i] = its root
+hipError_t launch_cluster_count(const ClusterArgs &a, hipStream_t stream);     // *count += roots
 
 }  // namespace skl

@@ -7,48 +7,12 @@
 //                          total the earlier bands left in device memory, which it then advances
 //   within_scatter_kernel  the count's chunking and loads again; slot = chunk offset + earlier waves + rank in the wave's ballots
 // Exact and deterministic: no atomics, no workgroup waits for another, the order of the output is the order of the positions.
-// Every number and the predicate come from within_plan.hpp, whose within_select_host() restates the three for the CPU test.
+// Every number and the predicate come from within_plan.hpp, whose within_select_host() restates the three for the CPU test; a
+// wave's loads and ballots are within_wave.hpp's, shared with cluster.hip.
 #include "kernels.h"
+#include "within_wave.hpp"
 
 namespace skl {
-
-namespace {
-
-__device__ __forceinline__ uint32_t within_lanes_below(uint64_t m)   // set bits of m below this lane
-{
-    return __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
-}
-
-// A wave's trips over its span of chunk `chunk`: the 16-byte loads and, per element of a load, the ballot of the lanes whose
-// position exists and passes.  Returns the wave's total.
-template <uint32_t NCOLS>
-struct WithinWave {
-    static constexpr uint32_t V = NCOLS == 2u ? 2u : 4u;                 // positions per load: V * NCOLS = 4 floats
-    static constexpr uint32_t TRIPS = WITHIN_WAVE_SPAN / (64u * V);
-    float4 v[TRIPS];
-    uint64_t pass[TRIPS][V];
-
-    __device__ __forceinline__ uint32_t load(const WithinArgs &a, uint64_t w0, uint32_t lane)
-    {
-        const float4 *__restrict__ src = reinterpret_cast<const float4 *>(a.band);
-        uint32_t total = 0;
-#pragma unroll
-        for (uint32_t t = 0; t < TRIPS; ++t) {
-            const uint64_t p = w0 + (uint64_t)(t * 64u + lane) * V;
-            v[t] = src[p < a.m ? p / V : 0u];   // (unconditional: it stays one 16-byte load; position 0 exists)
-            const float f[4] = {v[t].x, v[t].y, v[t].z, v[t].w};
-#pragma unroll
-            for (uint32_t e = 0; e < V; ++e) {
-                const bool keep = p + e < a.m && within_keep(a.pred, f[e * NCOLS], NCOLS == 2u ? f[e * NCOLS + 1u] : 0.0f);
-                pass[t][e] = __ballot(keep);
-                total += (uint32_t)__popcll(pass[t][e]);
-            }
-        }
-        return total;
-    }
-};
-
-}  // namespace
 
 template <uint32_t NCOLS>
 __global__ __launch_bounds__(WITHIN_THREADS) void within_count_kernel(const WithinArgs a)
@@ -57,7 +21,7 @@ __global__ __launch_bounds__(WITHIN_THREADS) void within_count_kernel(const With
     const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
     const uint64_t w0 = (uint64_t)blockIdx.x * WITHIN_CHUNK + (uint64_t)wave * WITHIN_WAVE_SPAN;
     WithinWave<NCOLS> w;
-    const uint32_t total = w0 < a.m ? w.load(a, w0, lane) : 0u;   // (wave-uniform)
+    const uint32_t total = w0 < a.m ? w.load(a.band, a.m, a.pred, w0, lane) : 0u;   // (wave-uniform)
     if (lane == 0u) wave_sum[wave] = total;
     __syncthreads();
     if (threadIdx.x == 0u) {
@@ -119,7 +83,7 @@ __global__ __launch_bounds__(WITHIN_THREADS) void within_scatter_kernel(const Wi
     const uint64_t w0 = (uint64_t)blockIdx.x * WITHIN_CHUNK + (uint64_t)wave * WITHIN_WAVE_SPAN;
     if (a.counts[blockIdx.x] == 0u) return;   // (workgroup-uniform, before any barrier)
     W w;
-    const uint32_t total = w0 < a.m ? w.load(a, w0, lane) : 0u;
+    const uint32_t total = w0 < a.m ? w.load(a.band, a.m, a.pred, w0, lane) : 0u;
     if (lane == 0u) wave_sum[wave] = total;
     __syncthreads();
     uint32_t before = 0;
