@@ -258,6 +258,41 @@ int skl_self_clusters_within(skl_ctx *ctx, const skl_sketches *s, const skl_dist
  * as above (SKL_ERR_INVALID_ARG, labels unchanged).  No slab and no distances are involved.  n == 0: SKL_OK, *n_clusters = 0. */
 int skl_clusters_merge(skl_ctx *ctx, uint32_t *labels, const uint32_t *other, uint64_t n, int on_device, uint64_t *n_clusters);
 
+/* ---- histogram of the stored values (no reference counterpart): where a collection's distances lie ----
+ * The calls above answer questions under a cap the caller already has; this one helps to choose it.  The answer to "where do the
+ * distances of this collection lie" is a few kilobytes -- a histogram -- where the dense matrix is 40 GB at 100 000 genomes.
+ * PAIRS: skl_self_dists_hist / skl_cross_dists_hist evaluate EXACTLY the pairs skl_self_dists_rows / skl_cross_dists_rows would
+ * for the same row range: the same row-range rules and out-of-bounds error; an empty range, or fewer than two samples, is SKL_OK
+ * with nothing counted; completeness vectors and completeness_cutoff apply unchanged.  The values binned are the f32 values the
+ * dense call stores -- with p->ani the first column is the ANI itself -- and the grid is on stored values in every mode.
+ * COUNTS: n0 * n1 u64, the cell (c0, c1) at c0 * n1 + c1.  One stored column (single-k Jaccard, ANI): lo1, hi1 and n1 are
+ * ignored and n1 counts as 1.  `counts_on_device` != 0: counts is a device pointer.  Either way the call returns with the stream
+ * idle and the results in place.
+ * OUTSIDE: 2 u64, always on the host.  outside[0]: the pairs with a non-NaN value off the grid in some column; outside[1]: the
+ * pairs with a NaN in some column (a NaN wins over off-grid).  sum(counts) + outside[0] + outside[1] is the number of pairs of
+ * the range.
+ * THE CELL RULE of a column, in f32 exactly as written: lo = (float)lo0, hi = (float)hi0, scale = (float)((double)n0 / ((double)hi
+ * - (double)lo)).  A value v with v < lo || v > hi is outside (so is +-inf, unless that test admits it).  Otherwise
+ * c = (uint32_t)((v - lo) * scale) -- one f32 subtract, one f32 multiply (never fused), truncation -- and c = min(c, n0 - 1): v == hi
+ * lands in the last cell, v == lo in cell 0.  The second column likewise.  numpy float32 reproduces it bit for bit.
+ * FLAGS: 0 -- counts and outside are zeroed first.  SKL_HIST_ACCUMULATE -- they hold earlier results and are added to: calls over
+ * consecutive row ranges chained this way give the whole call's histogram.  Histograms of two devices merge by plain addition.
+ * ERRORS, all SKL_ERR_INVALID_ARG with counts and outside untouched: grid, counts or outside NULL; n0 == 0, or n1 == 0 with two
+ * columns; a bound that is NaN or infinite, hi <= lo after rounding to float, or a range so narrow that scale is not a finite
+ * float; more than 2^20 cells (8 MiB of counts); unknown flag bits; a row range out of bounds.  The row range is evaluated in the
+ * bands of the within calls (same budget); nothing crosses to the host between them (csrc/hist.hip). */
+typedef struct skl_hist_grid {
+    double lo0, hi0;      /* first stored column: [lo0, hi0] cut into n0 equal cells */
+    double lo1, hi1;      /* second stored column (core/accessory only): n1 cells */
+    uint32_t n0, n1;      /* ncols == 1: lo1, hi1, n1 are ignored and n1 counts as 1 */
+} skl_hist_grid;
+#define SKL_HIST_ACCUMULATE 1   /* counts and outside hold earlier results and are added to; without it they are zeroed first */
+int skl_self_dists_hist(skl_ctx *ctx, const skl_sketches *s, const skl_dist_params *p, size_t row_begin, size_t row_end,
+                        const skl_hist_grid *grid, uint64_t *counts, int counts_on_device, int flags, uint64_t *outside);
+int skl_cross_dists_hist(skl_ctx *ctx, const skl_sketches *ref, const skl_sketches *query, const skl_dist_params *p,
+                         size_t ref_begin, size_t ref_end, const skl_hist_grid *grid, uint64_t *counts, int counts_on_device,
+                         int flags, uint64_t *outside);
+
 /* ---- sparse k-nearest-neighbour distances ----
  * Output rows hold `knn` items sorted ascending by key, where key = d0 for Jaccard / core for
  * CoreAcc, or 1-ANI for ANI (mod.rs:173-176).  out_d1 is written for CoreAcc only and may be NULL

@@ -42,6 +42,18 @@ class DistParams(C.Structure):
     ]
 
 
+class HistGrid(C.Structure):
+    """skl_hist_grid: [lo0, hi0] in n0 cells, [lo1, hi1] in n1 cells (the second column: core/accessory only)."""
+    _fields_ = [
+        ("lo0", C.c_double),
+        ("hi0", C.c_double),
+        ("lo1", C.c_double),
+        ("hi1", C.c_double),
+        ("n0", C.c_uint32),
+        ("n1", C.c_uint32),
+    ]
+
+
 # every symbol include/sketchlib_dist.h declares: (name, restype, argtypes)
 _P = C.c_void_p
 _SIG = [
@@ -104,6 +116,8 @@ _SIG = [
     ("skl_self_clusters_within", C.c_int, [_P, _P, C.POINTER(DistParams), C.c_size_t, C.c_size_t, C.c_double, C.c_double, _P, C.c_int, C.c_int,
                                            C.POINTER(C.c_uint64)]),
     ("skl_clusters_merge", C.c_int, [_P, _P, _P, C.c_uint64, C.c_int, C.POINTER(C.c_uint64)]),
+    ("skl_self_dists_hist", C.c_int, [_P, _P, C.POINTER(DistParams), C.c_size_t, C.c_size_t, C.POINTER(HistGrid), _P, C.c_int, C.c_int, _P]),
+    ("skl_cross_dists_hist", C.c_int, [_P, _P, _P, C.POINTER(DistParams), C.c_size_t, C.c_size_t, C.POINTER(HistGrid), _P, C.c_int, C.c_int, _P]),
     ("skl_self_dists_knn", C.c_int, [_P, _P, C.POINTER(DistParams), C.c_size_t, _P, _P, _P,
                                      C.c_int]),
     ("skl_self_dists_knn_rows", C.c_int, [_P, _P, C.POINTER(DistParams), C.c_size_t, C.c_size_t,
@@ -594,6 +608,40 @@ def dereplicate(ctx, s, p, max_dist, max_acc=np.inf):
     ids = np.flatnonzero(labels == np.arange(s.n, dtype=np.uint32)).astype(np.uint32)
     assert ids.size == n_clusters
     return s.select(ids), ids
+
+
+# ---- histogram of the stored values ----
+
+HIST_ACCUMULATE = 1        # SKL_HIST_ACCUMULATE
+
+
+def dists_hist(ctx, s, p, grid, r0=0, r1=None, query=None, counts=None):
+    """skl_self_dists_hist (query=None) / skl_cross_dists_hist: the histogram of the f32 values the dense call stores for rows
+    [r0, r1) -> (counts, outside, nan).  grid: (lo0, hi0, n0), or (lo0, hi0, n0, lo1, hi1, n1) for core/accessory; the cell rule is
+    the header's.  counts=None gives a new numpy uint64 array of shape (n0,) or (n0, n1); a uint64 numpy array or a device tensor
+    (int64 bits) of n0 * n1 elements is ACCUMULATED into (SKL_HIST_ACCUMULATE) and returned as the same object.  outside: the
+    pairs off the grid in some column; nan: the pairs with a NaN in some column; both of this call alone."""
+    r1 = s.n if r1 is None else r1
+    two = ncols(p) == 2
+    if len(grid) != (6 if two else 3):
+        raise ValueError("grid: (lo0, hi0, n0) for one stored column, (lo0, hi0, n0, lo1, hi1, n1) for core/accessory")
+    g = HistGrid(grid[0], grid[1], grid[3] if two else 0.0, grid[4] if two else 0.0, int(grid[2]), int(grid[5]) if two else 1)
+    cells = g.n0 * g.n1
+    flags = 0 if counts is None else HIST_ACCUMULATE
+    if counts is None:
+        counts = np.zeros((g.n0, g.n1) if two else (g.n0,), dtype=np.uint64)
+    elif isinstance(counts, np.ndarray):
+        if counts.dtype != np.uint64 or not counts.flags.c_contiguous or counts.size < cells:
+            raise ValueError("counts: a contiguous uint64 array of n0 * n1 elements")
+    elif counts.numel() < cells or counts.element_size() != 8 or not counts.is_contiguous():
+        raise ValueError("counts: a contiguous device tensor of n0 * n1 8-byte elements")
+    addr, dev = _ptr(counts)
+    outside = (C.c_uint64 * 2)(0, 0)
+    if query is None:
+        _check(load().skl_self_dists_hist(ctx._h, s._h, C.byref(p), r0, r1, C.byref(g), addr, dev, flags, outside))
+    else:
+        _check(load().skl_cross_dists_hist(ctx._h, s._h, query._h, C.byref(p), r0, r1, C.byref(g), addr, dev, flags, outside))
+    return counts, int(outside[0]), int(outside[1])
 
 
 # ---- sparse ----

@@ -18,6 +18,7 @@
 #include "inv_top_plan.hpp" // best hits of an inverted query: digits, list length, LDS bytes, the descending walk
 #include "within_plan.hpp"  // pairs within a distance cap: chunks, scan steps, the predicate, the (i, j) of a position
 #include "cluster_plan.hpp" // clusters under a distance cap: the label form, the per-sample grids, the scratch layout
+#include "hist_plan.hpp"    // histogram of a dense call's stored values: the grid, the cell rule, the launch numbers, the scratch layout
 
 namespace skl {
 
@@ -726,5 +727,17 @@ hipError_t launch_cluster_union(const ClusterArgs &a, hipStream_t stream);     /
 hipError_t launch_cluster_merge(const ClusterArgs &a, hipStream_t stream);     // union(i, other[i])
 hipError_t launch_cluster_flatten(const ClusterArgs &a, hipStream_t stream);   // labels[i] = its root
 hipError_t launch_cluster_count(const ClusterArgs &a, hipStream_t stream);     // *count += roots
+
+// hist.hip: the histogram of a dense band.  counts and outside live in device memory and are ADDED to (the caller zeroes them)
+struct HistArgs {
+    const float *band;            // [m][grid.ncols] f32, 16-byte aligned base, within_band_bytes(m, grid.ncols) readable
+    uint64_t m;                   // positions of the band, < WITHIN_BAND_PAIR_LIMIT
+    uint64_t chunks;              // hist_chunks(m)
+    HistGrid grid;                // hist_grid_make's: cells <= HIST_MAX_CELLS
+    unsigned long long *counts;   // [grid.n0 * grid.n1]
+    unsigned long long *outside;  // [2]: off the grid, NaN
+};
+// skl::hist_lds_kernel where hist_in_lds(cells), else skl::hist_global_kernel; hist_groups() workgroups
+hipError_t launch_hist(const HistArgs &a, hipStream_t stream);
 
 }  // namespace skl
