@@ -186,7 +186,7 @@ def test_reference_tie_order_with_a_reordered_index(oracle, skl, gpu_ctx, ref_ti
 
 
 def test_device_candidate_lists_many_bins_and_samples(oracle, skl, gpu_ctx):
-    """cand_gen.hip on its own terms: 5 000 samples (157 bitmap words per row, 20 per thread),
+    """cand_gen.hip on its own terms: 5 000 samples (157 bitmap words per row, one per thread),
     300 bins (more bins than waves), values that collide in one bin only, a value shared by
     everybody in one bin (a 5 000-member group), against the numpy definition."""
     kmers, ss64, n = [21], 2, 5000
