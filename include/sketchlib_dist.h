@@ -293,6 +293,42 @@ int skl_cross_dists_hist(skl_ctx *ctx, const skl_sketches *ref, const skl_sketch
                          size_t ref_begin, size_t ref_end, const skl_hist_grid *grid, uint64_t *counts, int counts_on_device,
                          int flags, uint64_t *outside);
 
+/* ---- minimum spanning tree of the distances (no reference counterpart): the whole single-linkage hierarchy in n - 1 records ----
+ * skl_self_clusters_within answers one cap; the histogram shows that there is usually more than one plausible cap.  The minimum
+ * spanning tree of the distance graph holds every answer at once: cut at any threshold it gives exactly the single-linkage
+ * clusters at that threshold, and sorted by weight it IS the single-linkage dendrogram -- 12 bytes a sample where the dense
+ * matrix is 4 TB at a million samples.  Every rule below is on the f32 values of the dense listing, so numpy reproduces the
+ * result from skl_self_dists_all alone (Kruskal over the edges sorted by the EDGE ORDER).
+ * GRAPH: the vertices are all n samples of the slab -- there is no row range, every round needs every pair.
+ * WEIGHTS: the weight of {i, j} is the f32 value the dense call stores for the pair in `column`: 0 -- the core distance, or the
+ * single-k Jaccard distance; 1 -- the accessory distance, core/accessory only.  Completeness vectors and completeness_cutoff
+ * apply unchanged.  p->ani != 0 is SKL_ERR_INVALID_ARG (the tree is defined on distances); so is column 1 with one stored
+ * column, and any other column.
+ * EDGES: a pair is an edge where w <= (float)max_dist.  max_dist = INFINITY: no cap.  A NaN weight is never an edge.  max_dist
+ * NaN or negative: SKL_ERR_INVALID_ARG, as for the within calls.  So the result is in general a spanning FOREST; with a cap and
+ * column 0 its components are exactly those of skl_self_clusters_within(max_first = max_dist, max_second = INFINITY).
+ * EDGE ORDER: edges compare by (w, i, j) with i < j, w as a float with -0.0f == +0.0f (on the device: a monotone u32 key of
+ * w + 0.0f, csrc/mst_plan.hpp).  The order is strict and total, so the minimum spanning forest under it is UNIQUE: the edges
+ * Kruskal keeps when it takes them in that order.  The result is a property of the data alone, never of scheduling.
+ * OUTPUT, all on the host: *n_edges = n minus the number of components; records r < *n_edges in ascending edge order -- the
+ * order in which single linkage merges -- with out_i[r] < out_j[r] and out_w[r] the stored f32 (as w + 0.0f: a stored -0.0f is
+ * reported as +0.0f).  The arrays have room for n - 1 records; nothing beyond *n_edges is touched.  labels may be NULL;
+ * otherwise n u32 in the form of the cluster calls: the lowest index of the sample's component, flat.  *rounds: the Boruvka
+ * rounds that added an edge (<= log2 n; each is one evaluation of the whole triangle, in the bands of the within calls).
+ * EDGE CASES: n == 0: SKL_OK, *n_edges = 0.  n == 1: SKL_OK, *n_edges = 0, labels[0] = 0.  out_i, out_j, out_w, n_edges or
+ * rounds NULL: SKL_ERR_INVALID_ARG.  More than 2^32 - 1 samples: SKL_ERR_INVALID_ARG. */
+int skl_self_mst(skl_ctx *ctx, const skl_sketches *s, const skl_dist_params *p, int column, double max_dist,
+                 uint32_t *out_i, uint32_t *out_j, float *out_w, uint32_t *labels,
+                 uint64_t *n_edges, uint32_t *rounds);
+/* CUTS: the clusters a list of edges connects among n samples -- union(edge_i[k], edge_j[k]) for every k from the identity, then
+ * flattened and counted; labels (n u32) and *n_clusters in the form of skl_self_clusters_within.  Everything lives on the host.
+ * Because the tree comes sorted by weight, "the clusters at threshold t" is this call on the prefix of its edges with w <= t:
+ * O(n) per threshold instead of a dense pass.  An index >= n is SKL_ERR_INVALID_ARG, found on the device before anything
+ * follows it, with labels untouched; so are labels or n_clusters NULL and an edge array NULL with n_edges_in > 0.  n == 0 with
+ * no edge: SKL_OK, *n_clusters = 0. */
+int skl_clusters_from_edges(skl_ctx *ctx, const uint32_t *edge_i, const uint32_t *edge_j, uint64_t n_edges_in,
+                            uint64_t n, uint32_t *labels, uint64_t *n_clusters);
+
 /* ---- sparse k-nearest-neighbour distances ----
  * Output rows hold `knn` items sorted ascending by key, where key = d0 for Jaccard / core for
  * CoreAcc, or 1-ANI for ANI (mod.rs:173-176).  out_d1 is written for CoreAcc only and may be NULL

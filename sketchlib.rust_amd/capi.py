@@ -118,6 +118,8 @@ _SIG = [
     ("skl_clusters_merge", C.c_int, [_P, _P, _P, C.c_uint64, C.c_int, C.POINTER(C.c_uint64)]),
     ("skl_self_dists_hist", C.c_int, [_P, _P, C.POINTER(DistParams), C.c_size_t, C.c_size_t, C.POINTER(HistGrid), _P, C.c_int, C.c_int, _P]),
     ("skl_cross_dists_hist", C.c_int, [_P, _P, _P, C.POINTER(DistParams), C.c_size_t, C.c_size_t, C.POINTER(HistGrid), _P, C.c_int, C.c_int, _P]),
+    ("skl_self_mst", C.c_int, [_P, _P, C.POINTER(DistParams), C.c_int, C.c_double, _P, _P, _P, _P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)]),
+    ("skl_clusters_from_edges", C.c_int, [_P, _P, _P, C.c_uint64, C.c_uint64, _P, C.POINTER(C.c_uint64)]),
     ("skl_self_dists_knn", C.c_int, [_P, _P, C.POINTER(DistParams), C.c_size_t, _P, _P, _P,
                                      C.c_int]),
     ("skl_self_dists_knn_rows", C.c_int, [_P, _P, C.POINTER(DistParams), C.c_size_t, C.c_size_t,
@@ -642,6 +644,39 @@ def dists_hist(ctx, s, p, grid, r0=0, r1=None, query=None, counts=None):
     else:
         _check(load().skl_cross_dists_hist(ctx._h, s._h, query._h, C.byref(p), r0, r1, C.byref(g), addr, dev, flags, outside))
     return counts, int(outside[0]), int(outside[1])
+
+
+# ---- minimum spanning tree of the distances ----
+
+def mst(ctx, s, p, column=0, max_dist=np.inf, labels=False):
+    """skl_self_mst: the minimum spanning forest of the graph whose edges are the pairs with a stored value <= max_dist in
+    `column` (0: core or single-k distance, 1: accessory) -> (i, j, w, rounds): uint32 [n_edges], uint32 [n_edges], f32 [n_edges]
+    in ascending (w, i, j) -- the order in which single linkage merges -- and the number of Boruvka rounds that added an edge.
+    labels=True appends the uint32 [n] component labels (lowest index of the component).  The edges with w <= t, handed to
+    clusters_from_edges, give the single-linkage clusters at threshold t."""
+    room = max(s.n - 1, 0)
+    oi, oj, ow = np.zeros(room, dtype=np.uint32), np.zeros(room, dtype=np.uint32), np.zeros(room, dtype=np.float32)
+    lab = np.zeros(s.n, dtype=np.uint32) if labels else None
+    found, rounds = C.c_uint64(0), C.c_uint32(0)
+    _check(load().skl_self_mst(ctx._h, s._h, C.byref(p), int(column), float(max_dist), oi.ctypes.data, oj.ctypes.data, ow.ctypes.data,
+                               lab.ctypes.data if labels else None, C.byref(found), C.byref(rounds)))
+    k = int(found.value)
+    out = (oi[:k], oj[:k], ow[:k], int(rounds.value))
+    return out + (lab,) if labels else out
+
+
+def clusters_from_edges(ctx, i, j, n):
+    """skl_clusters_from_edges: the components of n samples under the edges (i[k], j[k]) -> (labels uint32 [n], n_clusters), in
+    the label form of clusters_within.  On a prefix of mst()'s edges: the single-linkage clusters at that threshold."""
+    i = np.ascontiguousarray(i, dtype=np.uint32).reshape(-1)
+    j = np.ascontiguousarray(j, dtype=np.uint32).reshape(-1)
+    if i.size != j.size:
+        raise ValueError("the two edge arrays differ in length")
+    lab = np.zeros(int(n), dtype=np.uint32)
+    found = C.c_uint64(0)
+    _check(load().skl_clusters_from_edges(ctx._h, i.ctypes.data if i.size else None, j.ctypes.data if j.size else None, i.size, int(n),
+                                          lab.ctypes.data if n else None, C.byref(found)))
+    return lab, int(found.value)
 
 
 # ---- sparse ----

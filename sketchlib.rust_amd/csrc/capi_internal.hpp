@@ -10,7 +10,7 @@
 //   capi_sketch.cpp    DNA sketching;  capi_reads.cpp  read survivors;  capi_aa.cpp  amino-acid sketching;  capi_inv.cpp  inverted query
 //   capi_finish.cpp    finishing sketch streams on the device;  capi_slab.cpp  new slabs from resident ones
 //   capi_within.cpp    the pairs of a dense call that lie within a distance cap;  capi_clusters.cpp  the clusters those pairs connect
-//   capi_hist.cpp      the histogram of the values a dense call stores
+//   capi_hist.cpp      the histogram of the values a dense call stores;  capi_mst.cpp  the minimum spanning forest of the distance graph
 // Everything declared here is SKL_INTERNAL (hidden): the library exports the functions of the public header and nothing else of the host layer.
 // How a dense call and each pair-kernel launch is shaped is decided in dense_plan.hpp (pure, no HIP), reached through kernels.h;
 // the early break's decision in eb_plan.hpp; how the kNN drivers cut and feed their bands in knn_plan.hpp (both pure, no HIP).
@@ -101,7 +101,8 @@ enum ScratchSlot : int {
     SCRATCH_WITHIN = 18,           // pairs within a cap: running total, chunk offsets, chunk counts (within_plan.hpp)
     SCRATCH_CLUSTER_LABELS = 19,   // clusters within a cap: error word, root count, and the label array(s) of a caller whose own are on the host (cluster_plan.hpp)
     SCRATCH_HIST = 20,             // histogram of the stored values: the two outside words, and the counts of a caller whose own are on the host (hist_plan.hpp)
-    SCRATCH_SLOTS = 21
+    SCRATCH_MST = 21,              // minimum spanning forest: counters, labels, best / component words, edge records; the staged edges of skl_clusters_from_edges (mst_plan.hpp)
+    SCRATCH_SLOTS = 22
 };
 
 struct skl_ctx {

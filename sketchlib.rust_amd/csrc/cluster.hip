@@ -9,7 +9,8 @@
 //   cluster_merge_kernel                         union(i, other[i]) with the same device function
 //   cluster_flatten_kernel                       labels[i] becomes its root
 //   cluster_count_kernel                         the roots, exactly: a ballot and a popcount per wave, one integer atomic add per workgroup
-// The label form, the grids and the sequential restatement (cluster_labels_host) are cluster_plan.hpp's.
+// The label form, the grids and the sequential restatement (cluster_labels_host) are cluster_plan.hpp's; the device functions
+// cluster_find(), cluster_shorten() and cluster_union() live in cluster_union.hpp, which mst.hip includes too.
 //
 // 1. INVARIANT.  Every value ever stored to labels[x] is an index <= x of x's own cluster: the identity, a checked input, a hook
 //    of the root x under a LOWER root of a cluster it is being joined with, or a lower ancestor of x.  So a label only ever
@@ -37,56 +38,10 @@
 //    the flatten before the count.
 // 4. No scalar memory writes and no scalar atomics anywhere: plain C++ and vector atomics only.
 #include "kernels.h"
+#include "cluster_union.hpp"
 #include "within_wave.hpp"
 
 namespace skl {
-
-namespace {
-
-__device__ __forceinline__ uint32_t label_load(const uint32_t *labels, uint32_t x)
-{
-    return __hip_atomic_load(labels + x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-// the root of x: strictly descending (invariant 1).  *direct: labels[x] as first read
-__device__ __forceinline__ uint32_t cluster_find(const uint32_t *labels, uint32_t x, uint32_t *direct)
-{
-    uint32_t p = label_load(labels, x);
-    *direct = p;
-    while (p != x) {
-        x = p;
-        p = label_load(labels, x);
-    }
-    return x;
-}
-
-// end point x, whose label read `direct`, has root r: point it there unless it did (or is the root)
-__device__ __forceinline__ void cluster_shorten(uint32_t *labels, uint32_t x, uint32_t direct, uint32_t r)
-{
-    if (direct != r) (void)__hip_atomic_fetch_min(labels + x, r, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-__device__ __forceinline__ void cluster_union(uint32_t *labels, uint32_t a, uint32_t b)
-{
-    uint32_t da, db;
-    uint32_t ra = cluster_find(labels, a, &da), rb = cluster_find(labels, b, &db);
-    const bool same = ra == rb;   // the read-only test, before any atomic: inside a clonal cluster nearly every pair ends here
-    cluster_shorten(labels, a, da, ra);
-    cluster_shorten(labels, b, db, rb);
-    if (same) return;
-    for (;;) {
-        const uint32_t hi = ra > rb ? ra : rb, lo = ra > rb ? rb : ra;
-        const uint32_t seen = atomicCAS(labels + hi, hi, lo);
-        if (seen == hi) return;                 // hooked
-        // hi had been hooked by another lane, under seen < hi: go on from there (hi + lo falls with every turn)
-        uint32_t unused;
-        ra = cluster_find(labels, seen, &unused);
-        rb = cluster_find(labels, lo, &unused);
-        if (ra == rb) return;
-    }
-}
-
-}  // namespace
 
 __global__ __launch_bounds__(CLUSTER_THREADS) void cluster_init_kernel(const ClusterArgs a)
 {

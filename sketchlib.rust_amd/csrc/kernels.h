@@ -19,6 +19,7 @@
 #include "within_plan.hpp"  // pairs within a distance cap: chunks, scan steps, the predicate, the (i, j) of a position
 #include "cluster_plan.hpp" // clusters under a distance cap: the label form, the per-sample grids, the scratch layout
 #include "hist_plan.hpp"    // histogram of a dense call's stored values: the grid, the cell rule, the launch numbers, the scratch layout
+#include "mst_plan.hpp"     // minimum spanning forest: the edge order and its key, the predicate, the scratch layout
 
 namespace skl {
 
@@ -739,5 +740,32 @@ struct HistArgs {
 };
 // skl::hist_lds_kernel where hist_in_lds(cells), else skl::hist_global_kernel; hist_groups() workgroups
 hipError_t launch_hist(const HistArgs &a, hipStream_t stream);
+
+// mst.hip: the minimum spanning forest of the distance graph, one Boruvka round at a time.  Every array lives in device memory
+// (mst_plan.hpp's scratch layout); labels is a flat partition when the min-edge and the choosing kernels run; the band fields are
+// WithinArgs' (self mode only)
+struct MstArgs {
+    uint32_t *labels;             // [n]
+    uint64_t n;                   // samples, <= CLUSTER_MAX_SAMPLES
+    const float *band;            // min edge: [m][ncols] f32, 16-byte aligned base, within_band_bytes(m, ncols) readable
+    uint64_t m;                   // positions of the band, < WITHIN_BAND_PAIR_LIMIT
+    uint64_t chunks;              // within_chunks(m)
+    uint32_t ncols;
+    uint64_t first;               // condensed position of band[0]
+    MstPred pred;
+    uint64_t *best;               // [n] key << 32 | other end, or MST_EMPTY
+    uint64_t *comp_min;           // [n] at a root: key << 32 | lo of the component's choice, or MST_EMPTY
+    uint32_t *comp_hi;            // [n] at a root: its hi, or MST_NO_SAMPLE
+    uint32_t *rec_i, *rec_j;      // [n] the records, in the order their slots were taken
+    float *rec_w;
+    uint32_t *n_edges;            // device word: records so far
+    const uint32_t *edge_i, *edge_j;   // skl_clusters_from_edges: [n_edges_in] staged in device memory
+    uint64_t n_edges_in;
+    uint32_t *error;              // its check: device word, set to 1 by an index >= n (never cleared by a kernel)
+};
+hipError_t launch_mst_min_edge(const MstArgs &a, hipStream_t stream);         // skl::mst_min_edge_kernel: the band's live pairs into best[]
+hipError_t launch_mst_choose_and_hook(const MstArgs &a, hipStream_t stream);  // skl::mst_offer_min_kernel, mst_offer_hi_kernel, mst_append_kernel, mst_hook_kernel
+hipError_t launch_mst_edges_check(const MstArgs &a, hipStream_t stream);      // an edge index >= n: *error = 1
+hipError_t launch_mst_edges_union(const MstArgs &a, hipStream_t stream);      // union(edge_i[k], edge_j[k])
 
 }  // namespace skl

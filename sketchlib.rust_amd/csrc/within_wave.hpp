@@ -1,6 +1,6 @@
 // within_wave.hpp -- how ONE WAVE reads its span of a dense band and finds the positions that pass the cap (device code, wave64):
-// the 16-byte loads and the ballots that within.hip's count and scatter kernels and cluster.hip's union kernel share.  The
-// chunking, the predicate and the (i, j) of a position are within_plan.hpp's.
+// the 16-byte loads and the ballots that within.hip's count and scatter kernels, cluster.hip's union kernel and mst.hip's
+// min-edge kernel share.  The chunking, the cap predicate and the (i, j) of a position are within_plan.hpp's.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -26,6 +26,12 @@ struct WithinWave {
 
     __device__ __forceinline__ uint32_t load(const float *__restrict__ band, uint64_t m, const WithinPred &pred, uint64_t w0, uint32_t lane)
     {
+        return load_if(band, m, w0, lane, [&pred](float v0, float v1) { return within_keep(pred, v0, v1); });
+    }
+    // ... with any predicate keep(v0, v1) on the two stored values of a position (v1 = 0 with one column): mst.hip's is its own
+    template <typename Keep>
+    __device__ __forceinline__ uint32_t load_if(const float *__restrict__ band, uint64_t m, uint64_t w0, uint32_t lane, Keep keep_of)
+    {
         const float4 *__restrict__ src = reinterpret_cast<const float4 *>(band);
         uint32_t total = 0;
 #pragma unroll
@@ -35,7 +41,7 @@ struct WithinWave {
             const float f[4] = {v[t].x, v[t].y, v[t].z, v[t].w};
 #pragma unroll
             for (uint32_t e = 0; e < V; ++e) {
-                const bool keep = p + e < m && within_keep(pred, f[e * NCOLS], NCOLS == 2u ? f[e * NCOLS + 1u] : 0.0f);
+                const bool keep = p + e < m && keep_of(f[e * NCOLS], NCOLS == 2u ? f[e * NCOLS + 1u] : 0.0f);
                 pass[t][e] = __ballot(keep);
                 total += (uint32_t)__popcll(pass[t][e]);
             }
